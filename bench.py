@@ -14,6 +14,23 @@ child processes, before this one imports torch) and passes rank 0's line on.
 The line's `distributed` object records the backend, the process group's
 world size (checked equal to N) and every rank's own figures.
 
+A plain run (`bench.py --gpus N --steps K --warmup W`) does what `value` needs
+and no more: it sets up the main workload, makes the cold, settling and
+warm-up launches, times the K steps, flushes once (merge_ms, calls_check) and
+prints the line; its `roofline` holds only `pipelined`, priced from the timed
+steps themselves.  Everything else described below -- `kernel_ms` and the
+roofline of the kernel alone, `c2_graph`, `sustained`, `hll_filter_off`,
+`host_buffer_ingest`, the sub-workloads, `--group`, the CPU baselines and the
+Node host's OTLP rates -- is measured only with `--full`.  A plain run makes
+the launches of the kernel-alone leg untimed, so the timed steps are the same
+launches of the window either way.
+
+`--dump-outputs DIR` writes what the main workload's engine has computed once
+the last timed step is done, as a caller would receive it: the flush result's
+columns and the resident windows' HLL and count-min sketches, one
+DIR/<name>.npy each (dump_outputs).  Inputs are seeded, so two runs with the
+same arguments write the same arrays.
+
 Steps alternate over `--streams` (default 2) launch streams: the engine keeps
 two sets of per-workgroup slabs, so a launch waits only for the launch two
 back and consecutive batches overlap (the next batch's workgroups start on the
@@ -236,19 +253,29 @@ def trace_variants(w0, w1, k, seed, rank=0, world=1):
     return out
 
 
+VARIANT_BUDGET_BYTES = 112_000_000_000
+
+
 def n_variants(args, launches, device):
     """Trace-id variants to build: one per launch before the soak (--variants 0,
     the default), so every launch `value`, `kernel_ms` and a rocprofv3 trace of
     the run see is a fresh trace-id set; an explicit --variants caps it.  Each
-    variant is 16 B/span of device memory; the count is bounded by what fits in
-    half the free HBM (a 400-step trace of 10 M-span batches needs ~93 GB)."""
+    variant is 16 B/span of device memory, and the count is capped by a fixed
+    budget of 112 GB (700 variants of a 10 M-span batch: a 400-step trace needs
+    ~93 GB), after which variants repeat.  The cap depends on the arguments
+    alone, never on the memory free at the moment, so the same arguments give
+    the same inputs on every run.  Only when even that does not fit in half
+    the free HBM does the count follow the free memory; the run says so."""
     want = launches if args.variants <= 0 else min(args.variants, launches)
     import torch
-    free, _ = torch.cuda.mem_get_info(device)
     per_span = 44 if getattr(args, "fresh_cols", False) else 16  # (--fresh-cols: every column per variant)
+    want = min(want, max(2, VARIANT_BUDGET_BYTES // (per_span * args.spans)))
+    free, _ = torch.cuda.mem_get_info(device)
     fit = max(2, int(free // 2 // (per_span * args.spans)))
     if want > fit:
-        print(f"bench: {want} trace-id variants do not fit; using {fit} (variants repeat)", file=sys.stderr)
+        print(f"bench: {want} trace-id variants do not fit in the free device memory; using {fit} "
+              "(inputs now depend on the memory free, so runs are not comparable output for output)",
+              file=sys.stderr)
     return min(want, fit)
 
 
@@ -266,7 +293,51 @@ WORKLOADS = {
 }
 
 
-def run_workload(name, n, args, device, rank, world, barrier):
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(dirpath, red, sketches):
+    """--dump-outputs: one flush result (RedResult or ExpoResult) and the window
+    sketches as DIR/<name>.npy, float64 (float32 for the HLL registers).  A u64
+    column is written exactly: key ids as two 32-bit halves (key_hash_hi,
+    key_hash_lo), counters as float64 (all far below 2^53).  Over the 64 MB
+    budget (a 1 M-series flush) the per-series columns keep a fixed, seeded
+    sample of rows; series_index.npy names the rows kept."""
+    import numpy as np
+
+    os.makedirs(dirpath, exist_ok=True)
+    out = {}
+    if sketches:
+        out["window_id"] = np.array([s.window_id for s in sketches], dtype=np.float64)
+        out["hll"] = np.stack([s.hll for s in sketches]).astype(np.float32)
+        out["cms"] = np.stack([s.cms for s in sketches]).astype(np.float64)
+    series = {}
+    kh = np.asarray(red.key_hash, dtype=np.uint64)
+    series["key_hash_hi"], series["key_hash_lo"] = kh >> np.uint64(32), kh & np.uint64(0xFFFFFFFF)
+    if hasattr(red, "bucket_counts"):  # explicit buckets (RedResult)
+        for f in ("bucket_counts", "calls", "sum_ns", "sum"):
+            series[f] = getattr(red, f)
+    else:  # exponential histograms (ExpoResult): buckets padded to the widest series
+        for f in ("count", "zero_count", "sum_ns", "sum", "min", "max", "scale", "offset"):
+            series[f] = getattr(red, f)
+        width = max([len(b) for b in red.buckets] + [1])
+        bk = np.zeros((len(kh), width), dtype=np.float64)
+        for i, b in enumerate(red.buckets):
+            bk[i, : len(b)] = b
+        series["buckets"] = bk
+    rows = len(kh)
+    row_bytes = sum(8 * int(np.prod(np.shape(a)[1:])) for a in series.values())
+    keep = int((DUMP_BUDGET_BYTES - sum(a.nbytes for a in out.values())) // (row_bytes + 8))
+    if rows > keep:
+        idx = np.sort(np.random.Generator(np.random.PCG64(20240611)).choice(rows, keep, replace=False))
+        series = {k: np.asarray(a)[idx] for k, a in series.items()}
+        out["series_index"] = idx.astype(np.float64)
+    out.update({k: np.asarray(a).astype(np.float64) for k, a in series.items()})
+    for name, a in out.items():
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+
+
+def run_workload(name, n, args, device, rank, world, barrier, dump_dir=None):
     """One workload on this rank: a fresh engine, device-resident columns,
     cold first launch, warm-up, the kernel alone (serial launches, HIP events
     on the launch stream), then the timed steps over the streams.  Every
@@ -291,7 +362,7 @@ def run_workload(name, n, args, device, rank, world, barrier):
     for c in batch.columns():
         cols.append(torch.from_numpy(c.view(np.int64) if c.dtype == np.uint64 else c.view(np.int32)).to(device))
     n_iso = max(3, args.steps // 5)
-    gk = getattr(args, "graph_k", 0) if (name == "c2" and world == 1) else 0
+    gk = getattr(args, "graph_k", 0) if (name == "c2" and world == 1 and args.full) else 0
     g_calls = max(1, args.steps // gk) if gk > 0 else 0
     n_var = n_variants(args, 1 + args.settle + args.warmup + 2 * n_iso + args.steps + (2 + g_calls) * gk, device)
     variants = trace_variants(cols[3], cols[4], n_var, seed=1000 + rank, rank=rank, world=world)
@@ -345,27 +416,35 @@ def run_workload(name, n, args, device, rank, world, barrier):
     torch.cuda.synchronize(device)
     cold_ms = c0.elapsed_time(c1)
     settle_ms = [round(a.elapsed_time(b), 4) for a, b in st]
-    # 1) the kernel alone: serial launches on one stream.  kernel_ms: HIP events
-    #    around n_iso back-to-back launches, divided by n_iso (each launch's
-    #    duration plus the gap to the next); kernel_ms_bracketed: HIP events
-    #    around each launch on its own (adds the events' own cost per launch)
-    iso = [(ev(), ev()) for _ in range(n_iso)]
-    for a, b in iso:
+    # 1) the kernel alone (--full): serial launches on one stream.  kernel_ms:
+    #    HIP events around n_iso back-to-back launches, divided by n_iso (each
+    #    launch's duration plus the gap to the next); kernel_ms_bracketed: HIP
+    #    events around each launch on its own (adds the events' own cost per
+    #    launch).  A plain run makes the same 2 * n_iso launches untimed, so
+    #    its timed steps are the same launches of the window as with --full
+    kernel_ms = kernel_ms_bracketed = None
+    if args.full:
+        iso = [(ev(), ev()) for _ in range(n_iso)]
+        for a, b in iso:
+            eng.join(stream.cuda_stream)
+            a.record(stream)
+            step(0, stream)
+            eng.join(stream.cuda_stream)
+            b.record(stream)
+        k0, k1 = ev(), ev()
         eng.join(stream.cuda_stream)
-        a.record(stream)
-        step(0, stream)
-        eng.join(stream.cuda_stream)
-        b.record(stream)
-    k0, k1 = ev(), ev()
-    eng.join(stream.cuda_stream)
-    k0.record(stream)
-    for _ in range(n_iso):
-        step(0, stream)
-    eng.join(stream.cuda_stream)  # (the binned path aggregates on an engine stream)
-    k1.record(stream)
-    torch.cuda.synchronize(device)
-    kernel_ms_bracketed = sum(a.elapsed_time(b) for a, b in iso) / len(iso)
-    kernel_ms = k0.elapsed_time(k1) / n_iso
+        k0.record(stream)
+        for _ in range(n_iso):
+            step(0, stream)
+        eng.join(stream.cuda_stream)  # (the binned path aggregates on an engine stream)
+        k1.record(stream)
+        torch.cuda.synchronize(device)
+        kernel_ms_bracketed = sum(a.elapsed_time(b) for a, b in iso) / len(iso)
+        kernel_ms = k0.elapsed_time(k1) / n_iso
+    else:
+        for _ in range(2 * n_iso):
+            step(0, stream)
+        torch.cuda.synchronize(device)
     # 2) the timed steps, alternating over the streams
     start = ev()
     ends = [ev() for _ in streams]
@@ -385,6 +464,22 @@ def run_workload(name, n, args, device, rank, world, barrier):
     elapsed = time.perf_counter() - t0
     barrier()
     device_ms = max(start.elapsed_time(e_) for e_ in ends) / max(1, args.steps)
+    # what the timed path has computed once its last step is done: the flush a
+    # caller would make now, and the window sketches.  A plain run flushes here
+    # anyway; with --full the one flush comes after the graph and soak
+    # launches below, so --dump-outputs adds this one before them (the soak's
+    # launch count depends on the clock, its results are never dumped)
+    early, flush_ms, flushed_at = None, 0.0, 0
+    if world == 1 and (dump_dir or not args.full):
+        torch.cuda.synchronize(device)
+        tm = time.perf_counter()
+        early = eng.flush_exp() if exp_max else eng.flush()
+        flushed_at = launches[0]
+        torch.cuda.synchronize(device)
+        flush_ms = (time.perf_counter() - tm) * 1e3
+        if dump_dir:
+            n_win = min(16, int(batch.end_ns.max()) // 10_000_000_000 - first_window + 1)
+            dump_outputs(dump_dir, early, [eng.window_read(first_window + w) for w in range(n_win)])
     # 2b) the same launches as groups of K through sa_ingest_device_many (one
     #     HIP graph per call on small-table engines, so no dispatch gap between
     #     the K kernels); both of the engine's graphs are instantiated by two
@@ -418,7 +513,7 @@ def run_workload(name, n, args, device, rank, world, barrier):
     #    (after the timed steps, never part of value; trace-id variants repeat
     #    here, so later HLL reads raise little) -- the rate a collector holds
     soak = None
-    if args.soak_s > 0:
+    if args.full and args.soak_s > 0:
         per = max(1, int(args.soak_s / max(device_ms * 1e-3, 1e-5)) // 8)  # launches per host check
         n_soak, ts = 0, time.perf_counter()
         while True:
@@ -436,10 +531,12 @@ def run_workload(name, n, args, device, rank, world, barrier):
     own = {"rank": rank, "device": str(device), "ms_per_step": elapsed * 1e3 / max(1, args.steps),
            "kernel_ms": kernel_ms, "device_ms_per_step": device_ms}
     if world > 1:
-        t = torch.tensor([elapsed, kernel_ms, kernel_ms_bracketed, device_ms, cold_ms], dtype=torch.float64,
-                         device=device)
+        t = torch.tensor([elapsed, device_ms, cold_ms, kernel_ms or 0.0, kernel_ms_bracketed or 0.0],
+                         dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed, kernel_ms, kernel_ms_bracketed, device_ms, cold_ms = (float(x) for x in t)
+        elapsed, device_ms, cold_ms = (float(x) for x in t[:3])
+        if args.full:
+            kernel_ms, kernel_ms_bracketed = float(t[3]), float(t[4])
     # one flush (+ RCCL merge across ranks) after the timed region
     torch.cuda.synchronize(device)
     tm = time.perf_counter()
@@ -448,17 +545,21 @@ def run_workload(name, n, args, device, rank, world, barrier):
         part = EnginePartial(eng, device)
         red = merge_red(part, reset=True)
         merge_window(part, first_window + 1)
-    else:
+        if dump_dir and rank == 0:
+            dump_outputs(dump_dir, red, [])
+    elif early is None or launches[0] > flushed_at:
         red = eng.flush_exp() if exp_max else eng.flush()
+    else:
+        red = None  # (a plain run: everything was flushed after the timed steps)
     torch.cuda.synchronize(device)
-    merge_ms = (time.perf_counter() - tm) * 1e3
+    merge_ms = (time.perf_counter() - tm) * 1e3 if red is not None else flush_ms
     own["merge_ms"] = merge_ms
     per_rank = [own]
     if world > 1:  # every rank's own figures (value uses the max over ranks)
         per_rank = [None] * world
         dist.all_gather_object(per_rank, own)
     st = eng.stats()
-    calls = int(red.count.sum()) if exp_max else int(red.calls.sum())
+    calls = sum(int(r.count.sum()) if exp_max else int(r.calls.sum()) for r in (early, red) if r is not None)
     calls_ok = calls == launches[0] * n * world - st["zero_key"] * (1 if world == 1 else world)
     # the whole window from its cold start: cold + settling launches (HIP
     # events, one by one) + the timed steps (wall clock); the warm-up and the
@@ -578,6 +679,13 @@ def run_group(n, members, args, device):
 
 
 def roofline(name, n, r, traffic_path=None):
+    if r["kernel_ms"] is None:
+        # a plain run times no kernel alone (--full does): the timed steps'
+        # own device time per step against the HBM peak is all it prices
+        piped = BYTES_PER_SPAN * n / (r["device_ms"] * 1e-3) / 1e9
+        return {"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s", "bytes_per_span": BYTES_PER_SPAN,
+                "pipelined": {"streams": r["streams"], "device_ms_per_step": r["device_ms"], "achieved": piped,
+                              "frac": piped / HBM_PEAK_GBS}}
     achieved = BYTES_PER_SPAN * n / (r["kernel_ms"] * 1e-3) / 1e9
     tpath = traffic_path or os.path.join(ROOT, "profiles", "traffic.json" if name == "c2" else f"traffic_{name}.json")
     traffic, tsrc = load_traffic(tpath, name)
@@ -680,8 +788,8 @@ def main():
     ap.add_argument("--settle", type=int, default=16,
                     help="untimed launches after the cold one, before the warm-up (HLL registers settle)")
     ap.add_argument("--variants", type=int, default=0,
-                    help="distinct trace-id variants of the batch (0 = one per launch before the soak; "
-                         "N = at most N, repeating after that)")
+                    help="distinct trace-id variants of the batch (0 = one per launch before the soak, at most "
+                         "112 GB of them: 700 at 10 M spans; N = at most N; variants repeat after that)")
     ap.add_argument("--sub", default="c4,c4zipf,c2expo",
                     help="extra workloads reported as sub-objects of the line at N=1 ('' = none)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
@@ -701,6 +809,14 @@ def main():
                          "(one HIP graph per call; reported as the c2_graph sub-object; 0 = skip)")
     ap.add_argument("--no-filter-off", action="store_true",
                     help="skip the C2 kernel time with the HLL lower-bound filter off")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: the kernel alone and its "
+                         "roofline, the graph launches, the soak, the HLL filter off, the host-buffer ingest, "
+                         "the sub-workloads (--sub), --group, the CPU baselines and the Node host's OTLP rate "
+                         "(the options of those legs apply only with --full)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="write what the main workload's engine has computed after the last timed step (its "
+                         "flush result and window sketches) as DIR/<name>.npy")
     ap.add_argument("--cpu-worker", type=int, default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.cpu_worker is not None:  # child of cpu_baseline_multicore (no GPU use)
@@ -741,14 +857,14 @@ def main():
             dist.barrier()
 
     n = args.spans
-    main_r = run_workload(args.workload, n, args, device, rank, world, barrier)
+    main_r = run_workload(args.workload, n, args, device, rank, world, barrier, dump_dir=args.dump_outputs)
     eng, batch = main_r["eng"], main_r["batch"]
 
     # the host-buffer boundary (sa_ingest: the batch starts in pageable host
     # memory, PCIe H2D included), timed after the device-resident steps; it
     # is reported beside `value`, never as it
     h2d = None
-    if world == 1 and args.h2d_reps > 0:
+    if world == 1 and args.full and args.h2d_reps > 0:
         eng.ingest(batch)  # warm the staging buffers
         torch.cuda.synchronize(device)
         th = time.perf_counter()
@@ -766,7 +882,7 @@ def main():
     eng.close()
 
     subs = {}
-    if world == 1:
+    if world == 1 and args.full:
         for sub in [w for w in args.sub.split(",") if w and w != args.workload]:
             r = run_workload(sub, n, args, device, rank, world, barrier)
             r["eng"].close()
@@ -792,10 +908,10 @@ def main():
             "roofline": {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": ach / HBM_PEAK_GBS, "per": "wall-clock step (launch gaps included)"},
             "calls_check": main_r["calls_ok"]}
-    if world == 1 and args.workload == "c2" and not args.no_filter_off:
+    if world == 1 and args.full and args.workload == "c2" and not args.no_filter_off:
         extra["hll_filter_off"] = kernel_ms_filter_off(n, args, device)
         torch.cuda.empty_cache()
-    if world == 1 and args.group > 1:
+    if world == 1 and args.full and args.group > 1:
         extra["group"] = run_group(n, args.group, args, device)
         torch.cuda.empty_cache()
 
@@ -839,7 +955,7 @@ def main():
         if h2d is not None:
             result["host_buffer_ingest"] = h2d
         wl = main_r["wl"]
-        if world == 1 and not args.no_cpu_baseline and wl is not None:
+        if world == 1 and args.full and not args.no_cpu_baseline and wl is not None:
             port, conn = cpu_baseline(wl, args.cpu_seconds)
             result["cpu_baseline"] = port
             result["cpu_baseline_connector"] = conn
@@ -850,7 +966,7 @@ def main():
                 mc.update({"nproc": cores["nproc"], "affinity_cpus": cores["affinity"],
                            "cgroup_quota_cpus": cores["cgroup_quota_cpus"]})
                 result["cpu_baseline_multicore"] = mc
-        if world == 1 and args.host_otlp_spans > 0:
+        if world == 1 and args.full and args.host_otlp_spans > 0:
             # the box's usable cores (its cgroup CPU share), at most 16 decode threads
             hthreads = max(1, min(16, box_cores()["usable"]))
             result["host_otlp"] = host_otlp_rate(args.host_otlp_spans, threads=hthreads)

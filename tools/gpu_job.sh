@@ -60,7 +60,7 @@ run() {  # name, seconds, command...
   exit $rc
 }
 
-BQ="--no-cpu-baseline --host-otlp-spans 0 --h2d-reps 0"
+BQ="--full --no-cpu-baseline --host-otlp-spans 0 --h2d-reps 0"
 for step in "$@"; do
   case $step in
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
@@ -70,12 +70,12 @@ for step in "$@"; do
     stamps_*) wl=${step#stamps_}; WL=$wl run "stamps_$wl" 300 python tools/bt_stamps.py ;;
     tests) run tests 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread ;;
     tests:*) f=${step#tests:}; run "tests_$(basename "$f" .py)" 600 python -u -m pytest "$f" -m gpu -x -v --timeout 300 --timeout-method thread ;;
-    bench) run bench 500 python bench.py ;;
+    bench) run bench 500 python bench.py --full ;;
     rehearse_*) n=${step#rehearse_}; SPANAGG_BENCH_ONE_DEVICE=1 run "rehearse_n$n" 400 python -m torch.distributed.run \
         --nnodes=1 --nproc-per-node "$n" --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus "$n" --steps 10 \
-        --warmup 2 --settle 4 --soak-s 0 ;;
+        --warmup 2 --settle 4 --soak-s 0 --full ;;
     selflaunch_*) n=${step#selflaunch_}; SPANAGG_BENCH_ONE_DEVICE=1 run "selflaunch_n$n" 400 python bench.py --gpus "$n" \
-        --steps ${SL_STEPS:-20} --soak-s 0 ;;  # bench.py starts its own n ranks (no outer launcher), all on this GPU
+        --steps ${SL_STEPS:-20} --soak-s 0 --full ;;  # bench.py starts its own n ranks (no outer launcher), all on this GPU
     colbench) (cd host/node && node test/host_rate.js 2000000 --dump /tmp/req_plain.bin > /dev/null && \
         node test/host_rate.js 2000000 --events --dump /tmp/req_ev.bin > /dev/null) || exit 1
       for t in ${COL_THREADS:-1 4 8 16}; do run "colbench_t$t" 120 host/node/build/colbench /tmp/req_plain.bin --threads "$t"; done
