@@ -90,7 +90,27 @@ typedef enum { SA_UNIT_MS = 0, SA_UNIT_S = 1 } sa_unit;
 #define SA_OPT_STAMPS        (1u << 6) /* per-workgroup timestamps for sa_debug_stamps */
 #define SA_OPT_GROUP_COPY    (1u << 7) /* sa_group_create: merge through device copies, never RCCL */
 #define SA_OPT_GROUP_RCCL    (1u << 8) /* sa_group_create: RCCL even for a group of one */
-#define SA_OPT_ALL           0x1FFu
+/* Dense series indices (large explicit-bucket tables; spanagg_dense.hip): the
+ * host resolves each span's series in its own dictionary and the key_hash
+ * column of EVERY ingest call (host, async, device, device_many) carries a
+ * dense index i instead of the hash.  Index 0 stays "no series" (zero_key);
+ * 1 <= i < table_capacity is valid; a span with i >= table_capacity is
+ * counted in dropped_table_full (the next flush returns SA_EFULL), still
+ * updates its HLL register and adds nothing to the count-min.  sa_bind_ids
+ * declares which hash an index stands for; results (flush rows, count-min
+ * cells, HLL) equal the default engine's on the same spans with the real
+ * hashes.  Spans on an index that was never bound are added to
+ * dropped_table_full by the time sa_flush returns (SA_EFULL): no row, no
+ * count-min cell.  table_capacity: the next power of two >= 1.25 x
+ * key_capacity, at least 2^19.  sa_create returns SA_EINVAL with
+ * exp_max_size != 0, more than 17 buckets, n_windows > 1024, bounds the
+ * bucket bin table cannot hold, SA_OPT_PARTITIONED / ATOMIC_TABLE / EXPO_HBM /
+ * EXPO_CACHED, or a table above 2^22 slots; sa_group_create returns SA_EINVAL
+ * (groups merge by hash).  sa_gather_dense and sa_reclaim_keys return
+ * SA_ESTATE (no hash -> slot map on the device; nothing is ever full, flush
+ * never reclaims); sa_stats.n_keys is the number of bound indices. */
+#define SA_OPT_DENSE_IDS     (1u << 9)
+#define SA_OPT_ALL           0x3FFu
 
 typedef struct {
     /* histogram.explicit.buckets (sorted ascending, finite) and histogram.unit */
@@ -277,6 +297,15 @@ int sa_get_stats(sa_engine *e, sa_stats *out);
 /* Folds pending partials into the HBM table and writes the resident keys that
  * have a non-zero delta into d_keys (capacity `cap`); *n_out = count (may exceed
  * cap, in which case nothing beyond cap is written). */
+/* SA_OPT_DENSE_IDS engines: declares that index[j] is series key_hash[j]
+ * (host arrays, borrowed for the call).  Ordered on the engine stream before
+ * every later ingest on any stream.  SA_EINVAL for an index of 0 or >=
+ * table_capacity and for a key_hash of 0; SA_ESTATE on an engine without the
+ * option.  Binding an index that is already bound recycles it: allowed only
+ * with no spans ingested since the last flush (SA_ESTATE otherwise); every
+ * resident window's ERROR counts of the old series go to its count-min cells
+ * first, so the old series keeps its errors. */
+int sa_bind_ids(sa_engine *e, const uint64_t *index, const uint64_t *key_hash, uint64_t n);
 int sa_export_keys(sa_engine *e, uint64_t *d_keys, uint64_t cap, uint64_t *n_out, void *stream);
 /* d_rows[i] = [bucket counts..., sum_ns] (n_buckets+1 u64) for d_keys[i]
  * (zeros if absent). reset != 0 clears the engine's delta counters afterwards. */

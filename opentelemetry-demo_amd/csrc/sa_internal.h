@@ -373,6 +373,16 @@ constexpr size_t kBt2ScatterLds = (size_t)kPartBins * (kBtStage * 16 + 2 + 2) + 
                                   (size_t)kBt2Hot * (16 + 4 * kPartWords) + (size_t)kBtHq * 8 + 16 +
                                   (size_t)kBins * sizeof(BinEntry) + kLbMaxSub + kBt2HotErr * 8;
 static_assert(kBt2ScatterLds <= 163840, "binned scatter2 LDS");
+// Dense-index form of the binned path (spanagg_dense.hip, SA_OPT_DENSE_IDS):
+// 8-B records in 8-record stages (one 64-B chunk per flush; the stages take
+// the LDS of the binned scatter's 4 x 16 B, so kBt2ScatterLds serves both)
+// (SA_DN_STAGE=4: 32-B chunks, for A/B builds -- DESIGN.md has the measurement)
+#ifndef SA_DN_STAGE
+#define SA_DN_STAGE 8
+#endif
+constexpr uint32_t kDnStage = SA_DN_STAGE;
+static_assert(kDnStage == 4 || kDnStage == 8, "dense stage: 4 or 8 records");
+static_assert(kDnStage * 8 <= kBtStage * 16, "dense stages fit the binned scatter's LDS layout");
 
 // Geometry of the counter rows and key table for the flush-time kernels
 // (compact, gather, count-min fold): both table layouts, both row layouts.
@@ -383,6 +393,11 @@ struct RowGeom {
   uint32_t log2cap, log2sb, max_probe;
   uint64_t kmul, kinv;            // key <-> stored id (1, 1 unless binned)
   unsigned long long *base64;     // row8: u64 [cap][nbk + 1] spilled counts and sums
+  // dense-index engines (SA_OPT_DENSE_IDS): a slot's key is the hash bound to
+  // its index, 0 while unbound; the spans of a non-zero row without a key are
+  // counted in *dropped when the row is reset
+  uint32_t dense;
+  unsigned long long *dropped;
 };
 
 // Key-table layout: cap = 2^log2cap slots in buckets of 4 (log2cap in 4..31).
@@ -495,7 +510,8 @@ hipError_t launch_gather_dense(const unsigned long long *gkeys, const unsigned l
                                hipStream_t s);
 hipError_t launch_fold_errcnt(const unsigned long long *gkeys, unsigned long long *errcnt,
                               uint64_t cap, unsigned long long *cms, uint32_t d, uint32_t w,
-                              uint32_t shift, const uint64_t *seeds, uint64_t kinv, hipStream_t s);
+                              uint32_t shift, const uint64_t *seeds, uint64_t kinv, uint32_t dense,
+                              hipStream_t s);
 // binned-table path (spanagg_binned.hip)
 hipError_t prepare_ingest_bt(size_t agg_lds);
 size_t bt_agg2_lds_bytes(uint32_t log2sb, uint32_t grid);
@@ -503,6 +519,13 @@ size_t bt_agg2_lds_bytes(uint32_t log2sb, uint32_t grid);
 // stream, beside the next launch's scatter)
 hipError_t launch_bt_scatter(const IngestParams &P, hipStream_t s);
 hipError_t launch_bt_aggregate(const IngestParams &P, hipStream_t s);
+// its dense-index form (spanagg_dense.hip): the same launch pipeline
+hipError_t prepare_ingest_dn(size_t agg_lds);
+size_t dn_agg_lds_bytes(uint32_t log2sb, uint32_t grid);
+hipError_t launch_dn_scatter(const IngestParams &P, hipStream_t s);
+hipError_t launch_dn_aggregate(const IngestParams &P, hipStream_t s);
+hipError_t launch_dn_bind(unsigned long long *gkeys, const uint64_t *index, const uint64_t *key_hash, uint64_t n,
+                          uint32_t log2sb, hipStream_t s);
 hipError_t launch_reduce_errslab(uint32_t *errslab, uint32_t G, uint64_t per_wg, uint64_t ws,
                                  uint32_t log2cap, unsigned long long *errcnt_ws, hipStream_t s);
 hipError_t launch_count_keys(const unsigned long long *gkeys, uint64_t cap,

@@ -4,10 +4,12 @@
 // SA_EDEVICE when no gfx950 device is usable.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <numeric>
 #include <random>
 #include <string>
@@ -200,6 +202,16 @@ struct sa_engine {
   int sticky_rc = 0;             // a pending aggregate that failed to launch (join_checked)
   sa::IngestParams bt_pend_P{};  // its launch parameters
   unsigned long long *base64 = nullptr;
+  // Dense-index engines (SA_OPT_DENSE_IDS, spanagg_dense.hip): the binned
+  // path's tables, rows and launch pipeline (bt is set too) with the dense
+  // kernels; key_hash columns carry indices, gkeys[row of i] is the hash
+  // sa_bind_ids bound to index i (kmul = kinv = 1).  `bound`: one bit per
+  // index, kept on the host; bind_buf: sa_bind_ids' device staging.
+  bool dense = false;
+  std::vector<uint64_t> bound;
+  uint64_t n_bound = 0;
+  uint64_t *bind_buf = nullptr;
+  uint64_t bind_cap = 0;
   size_t hll_slot_bytes = 0, cms_slot_elems = 0;
   // sa_ingest: two pinned host slots and their HBM copies; a slot is refilled
   // once its event (H2D copy + aggregation of the previous use) has passed
@@ -241,6 +253,16 @@ int set_dev(sa_engine *e) {
   return SA_OK;
 }
 
+// Table slots of an engine: the next power of two >= 1.25 x key_capacity;
+// dense-index engines raise it to the binned path's smallest table.
+uint64_t table_slots(uint64_t key_capacity) {
+  return std::max<uint64_t>(16, next_pow2(key_capacity + (key_capacity + 3) / 4));
+}
+uint64_t dense_table_slots(uint64_t key_capacity) {
+  return std::max<uint64_t>(1ULL << (sa::kPartBinBits + 8), table_slots(key_capacity));
+}
+bool bounds_fit_bins(const sa_config *c);
+
 int validate_config(const sa_config *c, std::string &why) {
   if (!c) return why = "null config", SA_EINVAL;
   if (c->n_bounds > SA_MAX_BOUNDS) return why = "too many histogram bounds", SA_EINVAL;
@@ -267,6 +289,16 @@ int validate_config(const sa_config *c, std::string &why) {
 #ifndef SPANAGG_AB
   if (c->flags) return why = "SA_DIAG_* flags need the laboratory build (libspanagg_ab.so)", SA_EINVAL;
 #endif
+  if (c->options & SA_OPT_DENSE_IDS) {
+    if (c->exp_max_size != 0) return why = "SA_OPT_DENSE_IDS: explicit buckets only (exp_max_size must be 0)", SA_EINVAL;
+    if (c->n_bounds + 1 > sa::kPartMaxBk) return why = "SA_OPT_DENSE_IDS: at most 17 buckets (16 bounds)", SA_EINVAL;
+    if (c->n_windows > 1024) return why = "SA_OPT_DENSE_IDS: n_windows must be <= 1024", SA_EINVAL;
+    if (c->options & (SA_OPT_PARTITIONED | SA_OPT_ATOMIC_TABLE | SA_OPT_EXPO_HBM | SA_OPT_EXPO_CACHED))
+      return why = "SA_OPT_DENSE_IDS cannot be combined with another table path option", SA_EINVAL;
+    if (dense_table_slots(c->key_capacity) > (1ULL << 22))
+      return why = "SA_OPT_DENSE_IDS: key_capacity needs a table above 2^22 slots", SA_EINVAL;
+    if (!bounds_fit_bins(c)) return why = "SA_OPT_DENSE_IDS: the bounds do not fit the bucket bin table", SA_EINVAL;
+  }
   return SA_OK;
 }
 
@@ -295,6 +327,20 @@ static bool build_bins(const sa_engine *e, sa::BinEntry (&bins)[sa::kBins]) {
   return true;
 }
 
+namespace {
+// validate_config: the bounds' thresholds fit the bin table (needs no device)
+bool bounds_fit_bins(const sa_config *c) {
+  auto e = std::make_unique<sa_engine>();
+  e->nbk = c->n_bounds + 1;
+  if (sa_bucket_thresholds(c->bounds, c->n_bounds, c->unit, e->thr, &e->nneg) != SA_OK) return false;
+  e->npos = c->n_bounds - e->nneg;
+  sa::BinEntry bins[sa::kBins];
+  return build_bins(e.get(), bins);
+}
+}  // namespace
+
+static uint32_t bt_region_for(const sa_engine *e, uint64_t wg_chunk);
+
 static size_t counts_bytes(const sa_engine *e) {
   return e->bt ? (size_t)e->cap * sa::kRowBytes : (size_t)e->cap * sa::row_stride(e->nbk) * 8;
 }
@@ -310,6 +356,8 @@ static sa::RowGeom geom(const sa_engine *e) {
   g.kmul = e->kmul;
   g.kinv = e->kinv;
   g.base64 = e->base64;
+  g.dense = e->dense ? 1u : 0u;
+  g.dropped = e->stats + sa::kStatDropped;
   return g;
 }
 
@@ -438,7 +486,8 @@ int sa_create(const sa_config *cfg, sa_engine **out) {
 
   // buckets of 4 slots with two choices stay well-behaved up to ~90% load:
   // size for 80% at the declared capacity (the LDS mirror path needs cap <= 2048)
-  e->cap = std::max<uint64_t>(16, next_pow2(cfg->key_capacity + (cfg->key_capacity + 3) / 4));
+  e->dense = (cfg->options & SA_OPT_DENSE_IDS) != 0;
+  e->cap = e->dense ? dense_table_slots(cfg->key_capacity) : table_slots(cfg->key_capacity);
   e->log2cap = log2u(e->cap);
   const uint32_t nw = (e->nbk + 1) / 2;
   // lkeys + lsum + lcnt + deferred-HLL queue (+ its counter), see ingest_lds_kernel
@@ -508,7 +557,7 @@ int sa_create(const sa_config *cfg, sa_engine **out) {
     e->G = e->cus * 8;
     // partitioned path unless the LDS counter row is too small for the
     // buckets (SA_OPT_ATOMIC_TABLE: per-span atomics)
-    e->part = e->nbk <= sa::kPartMaxBk && !(cfg->options & SA_OPT_ATOMIC_TABLE) && !e->expo;
+    e->part = e->nbk <= sa::kPartMaxBk && !(cfg->options & SA_OPT_ATOMIC_TABLE) && !e->expo && !e->dense;
     if (e->part)
       if (hipError_t st = sa::prepare_ingest_part(); st != hipSuccess)
         return bail(fail(e, SA_EDEVICE, std::string("LDS attribute: ") + hipGetErrorString(st)));
@@ -519,6 +568,9 @@ int sa_create(const sa_config *cfg, sa_engine **out) {
     sa::BinEntry bins_probe[sa::kBins];  // the binned kernels bucket by the bin table
     e->bt = e->part && e->log2cap >= sa::kPartBinBits + 8 && e->log2cap <= sa::kPartBinBits + 11 &&
             cfg->n_windows <= 1024 && build_bins(e, bins_probe) && !(cfg->options & SA_OPT_PARTITIONED);
+    // dense-index engines (validate_config checked the geometry): the binned
+    // path's tables and pipeline with the dense kernels
+    if (e->dense) e->bt = true;
   }
 
   const uint64_t S = cfg->n_services, W = cfg->n_windows;
@@ -607,10 +659,15 @@ int sa_create(const sa_config *cfg, sa_engine **out) {
     // workgroups sized for the bin's sub-table
     e->log2sb = e->log2cap - sa::kPartBinBits;
     e->bt_grid = e->cus;
-    e->agg_lds = sa::bt_agg2_lds_bytes(e->log2sb, e->bt_grid);
+    e->agg_lds = e->dense ? sa::dn_agg_lds_bytes(e->log2sb, e->bt_grid) : sa::bt_agg2_lds_bytes(e->log2sb, e->bt_grid);
+    // the dense aggregate's u16 LDS counters: a bin's records of two record
+    // sets at the largest launch must stay below 2^16 (spanagg_dense.hip)
+    if (e->dense && 2ull * e->bt_grid * bt_region_for(e, sa::kBtMaxWgSpans) > 65535)
+      return bail(fail(e, SA_EINVAL, "SA_OPT_DENSE_IDS: too many compute units for the aggregate's u16 counters"));
     const size_t spill = (size_t)e->cap * (e->nbk + 1) * 8;
     if ((rc = alloc((void **)&e->base64, spill))) return bail(rc);  // (zeroed)
-    if (hipError_t st = sa::prepare_ingest_bt(e->agg_lds); st != hipSuccess)
+    if (e->dense) e->bound.assign((e->cap + 63) / 64, 0);
+    if (hipError_t st = e->dense ? sa::prepare_ingest_dn(e->agg_lds) : sa::prepare_ingest_bt(e->agg_lds); st != hipSuccess)
       return bail(fail(e, SA_EDEVICE, std::string("LDS attribute: ") + hipGetErrorString(st)));
     // the aggregate stream of the launch pipeline (ordered by events only)
     if (hipStreamCreateWithFlags(&e->agg_stream, hipStreamNonBlocking) != hipSuccess)
@@ -623,8 +680,8 @@ int sa_create(const sa_config *cfg, sa_engine **out) {
     // home slots), so bin occupancy does not depend on ids a sender chooses
     std::random_device rd;
     uint64_t r = ((uint64_t)rd() << 32) ^ rd();
-    if (cfg->options & SA_OPT_IDENTITY_IDS) r = 1;  // stored id = series id (tests of a full bin)
-    if (const char *kv = ab_env("SPANAGG_KMUL")) r = std::strtoull(kv, nullptr, 0);  // fixed, for A/B runs
+    if ((cfg->options & SA_OPT_IDENTITY_IDS) || e->dense) r = 1;  // stored id = series id (tests of a full bin)
+    if (const char *kv = ab_env("SPANAGG_KMUL"); kv && !e->dense) r = std::strtoull(kv, nullptr, 0);  // fixed, for A/B runs
     e->kmul = r | 1ULL;
     uint64_t x = e->kmul;  // Newton: x = x (2 - a x) doubles the correct low bits
     for (int i = 0; i < 6; ++i) x *= 2 - e->kmul * x;
@@ -673,7 +730,7 @@ void sa_destroy(sa_engine *e) {
                   (void *)e->expo_out_keys,
                   (void *)e->expo_out_rows, (void *)e->expo_out_buckets, (void *)e->hll_filt, (void *)e->xslab,
                   (void *)e->xc_lcount, (void *)e->xc_slot_of_entry, (void *)e->xc_ent, (void *)e->xcslab, (void *)e->pool_ring,
-                  (void *)e->xt_rec, (void *)e->xt_off,
+                  (void *)e->xt_rec, (void *)e->xt_off, (void *)e->bind_buf,
                   e->dstage[0], e->dstage[1]})
     if (p) (void)hipFree(p);
   for (int k = 0; k < sa_engine::kBtSets; ++k)
@@ -772,20 +829,22 @@ static int ingest_on(sa_engine *e, const sa_span_batch *b, hipStream_t s) {
 // largest launch).  Region capacity: the mean records
 // per (bin, scatter workgroup) plus 4 standard deviations and 8, in whole
 // 4-record chunks; records beyond it take the scatter's overflow table.
-static uint32_t bt_region_for(uint64_t wg_chunk) {
+static uint32_t bt_region_for(const sa_engine *e, uint64_t wg_chunk) {
   const double mu = (double)wg_chunk / sa::kPartBins;
-  return ((uint32_t)std::ceil(mu + 4.0 * std::sqrt(mu) + 8.0) + sa::kBtStage - 1) & ~(sa::kBtStage - 1);
+  const uint32_t stage = e->dense ? sa::kDnStage : sa::kBtStage;  // (dense: whole 8-record chunks)
+  return ((uint32_t)std::ceil(mu + 4.0 * std::sqrt(mu) + 8.0) + stage - 1) & ~(stage - 1);
 }
 
 static int bt_prepare_launch(sa_engine *e, uint64_t n, IngestParams &P, hipStream_t s) {
   const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(e->bt_grid, (n + 4095) / 4096));
   P.bt_grid = grid;
   P.wg_chunk = ((n + grid - 1) / grid + 3) / 4 * 4;
-  P.bt_region = bt_region_for(P.wg_chunk);
+  P.bt_region = bt_region_for(e, P.wg_chunk);
   if (!e->bt_rec[0]) {
-    const size_t recs = (size_t)sa::kPartBins * e->bt_grid * bt_region_for(sa::kBtMaxWgSpans);
+    const size_t recs = (size_t)sa::kPartBins * e->bt_grid * bt_region_for(e, sa::kBtMaxWgSpans);
+    const size_t rec_bytes = e->dense ? 8 : sizeof(ulonglong2);  // (dense records: half the bytes)
     for (int k = 0; k < sa_engine::kBtSets; ++k)
-      if (hipMalloc((void **)&e->bt_rec[k], recs * sizeof(ulonglong2)) != hipSuccess ||
+      if (hipMalloc((void **)&e->bt_rec[k], recs * rec_bytes) != hipSuccess ||
           hipMalloc((void **)&e->bt_cnt[k], (size_t)e->bt_grid * sa::kPartBins * 4) != hipSuccess)
         return fail(e, SA_ENOMEM, "binned-path record buffers hipMalloc failed");
   }
@@ -822,7 +881,7 @@ static int bt_launch_aggregate(sa_engine *e, int pend, const sa::IngestParams &P
     static long n_agg = 0;
     if (fail_at > 0 && ++n_agg == fail_at) return fail(e, SA_EDEVICE, "aggregate launch: injected failure");
   }
-  if (hipError_t st = sa::launch_bt_aggregate(A, as); st != hipSuccess)
+  if (hipError_t st = e->dense ? sa::launch_dn_aggregate(A, as) : sa::launch_bt_aggregate(A, as); st != hipSuccess)
     return fail(e, SA_EDEVICE, std::string("aggregate launch: ") + hipGetErrorString(st));
   for (int j : {pend, k})
     if (j >= 0) {
@@ -1057,7 +1116,7 @@ static int ingest_launch(sa_engine *e, const sa_span_batch *b, hipStream_t s) {
       const char *v = ab_env("SPANAGG_BT_PAIR");
       return !(v && std::atoi(v) == 0);
     }();
-    st = sa::launch_bt_scatter(P, s);
+    st = e->dense ? sa::launch_dn_scatter(P, s) : sa::launch_bt_scatter(P, s);
     if (st == hipSuccess) st = hipEventRecord(e->ev_scat[k], s);
     if (st != hipSuccess) return fail(e, SA_EDEVICE, std::string("ingest launch: ") + hipGetErrorString(st));
     if (!pipe) {
@@ -1460,6 +1519,7 @@ static int reclaim_now(sa_engine *e) {
 // interval doubles the load, which must stay near 70 % for no bin to fill
 // (at 76 % of a 2^19-slot table, 2,048 bins of 256, P(some bin full) = 2.8 %).
 static int reclaim_if_full(sa_engine *e) {
+  if (e->dense) return SA_OK;  // nothing is ever full: the host owns the index space
   SA_HIP(e, hipMemsetAsync(e->scratch, 0, 8, e->stream));
   SA_HIP(e, sa::launch_count_keys(e->gkeys, e->cap, e->scratch, e->stream));
   uint64_t nk = 0;
@@ -1526,6 +1586,7 @@ extern "C" {
 
 int sa_reclaim_keys(sa_engine *e, int force) {
   if (!e) return SA_EINVAL;
+  if (e->dense) return fail(e, SA_ESTATE, "sa_reclaim_keys: dense-index engine (the host recycles indices with sa_bind_ids)");
   if (e->unflushed) return fail(e, SA_ESTATE, "sa_reclaim_keys: spans ingested since the last flush");
   if (int rc = set_dev(e)) return rc;
   if (int rc = join_checked(e)) return rc;
@@ -1591,6 +1652,14 @@ int sa_flush(sa_engine *e, sa_red_result **out) {
   if (int rc = read_stats(e, st)) return rc;
   if (st[sa::kStatDropped] != e->dropped_seen) {
     e->dropped_seen = st[sa::kStatDropped];
+    if (e->dense) {
+      // spans on unbound indices: their ERROR counts go too (the fold clears
+      // the cells of slots without a key), before a later bind gives the
+      // index a series
+      for (uint32_t ws = 0; ws < e->cfg.n_windows; ++ws)
+        if (int rc = fold_window(e, ws, e->stream)) return rc;
+      return fail(e, SA_EFULL, "spans on an unbound or out-of-range index were dropped since the previous flush");
+    }
     return fail(e, SA_EFULL, "key table full: spans were dropped since the previous flush");
   }
   return SA_OK;
@@ -1779,7 +1848,7 @@ static int fold_window(sa_engine *e, uint64_t ws, hipStream_t s) {
   if (int rc = fold_errslab(e, ws, s)) return rc;
   SA_HIP(e, sa::launch_fold_errcnt(e->gkeys, e->errcnt + ws * e->cap, e->cap,
                                    e->cms + ws * e->cms_slot_elems, e->cfg.cms_d, e->cfg.cms_w,
-                                   64 - log2u(e->cfg.cms_w), e->d_seeds, e->kinv, s));
+                                   64 - log2u(e->cfg.cms_w), e->d_seeds, e->kinv, e->dense ? 1u : 0u, s));
   return SA_OK;
 }
 
@@ -1863,6 +1932,7 @@ int sa_get_stats(sa_engine *e, sa_stats *o) {
   uint64_t nk = 0;
   SA_HIP(e, hipMemcpyAsync(&nk, e->scratch, 8, hipMemcpyDeviceToHost, e->stream));
   if (int rc = read_stats(e, st)) return rc;
+  if (e->dense) nk = e->n_bound;  // (the bound indices, as the host declared them)
   std::memset(o, 0, sizeof *o);
   o->spans = e->spans;
   o->zero_key = st[sa::kStatZeroKey];
@@ -1879,6 +1949,53 @@ int sa_get_stats(sa_engine *e, sa_stats *o) {
     SA_HIP(e, hipStreamSynchronize(e->stream));
     o->hll_filtered = std::accumulate(f.begin(), f.end(), (uint64_t)0);
   }
+  return SA_OK;
+}
+
+int sa_bind_ids(sa_engine *e, const uint64_t *index, const uint64_t *key_hash, uint64_t n) {
+  if (!e) return SA_EINVAL;
+  if (!e->dense) return fail(e, SA_ESTATE, "sa_bind_ids: the engine was not created with SA_OPT_DENSE_IDS");
+  if (n == 0) return SA_OK;
+  if (!index || !key_hash) return fail(e, SA_EINVAL, "sa_bind_ids: null array");
+  auto is_bound = [&](uint64_t i) { return (e->bound[i >> 6] >> (i & 63)) & 1u; };
+  bool recycle = false;
+  for (uint64_t j = 0; j < n; ++j) {
+    if (index[j] == 0 || index[j] >= e->cap) return fail(e, SA_EINVAL, "sa_bind_ids: index 0 or at or past table_capacity");
+    if (key_hash[j] == 0) return fail(e, SA_EINVAL, "sa_bind_ids: key_hash 0");
+    recycle = recycle || is_bound(index[j]);
+  }
+  if (int rc = set_dev(e)) return rc;
+  if (recycle) {
+    // an index changes its series: only between a flush and the next ingest
+    // (its row is zero then), and after every resident window's per-slot
+    // ERROR counts went to the count-min under the old hash (as reclaim_now)
+    if (e->unflushed) return fail(e, SA_ESTATE, "sa_bind_ids: rebinding an index with spans ingested since the last flush");
+    if (int rc = join_checked(e)) return rc;
+    for (uint32_t ws = 0; ws < e->cfg.n_windows; ++ws)
+      if (int rc = fold_window(e, ws, e->stream)) return rc;
+  }
+  if (e->bind_cap < n) {  // (hipFree waits for the device)
+    if (e->bind_buf) (void)hipFree(e->bind_buf);
+    e->bind_buf = nullptr;
+    e->bind_cap = 0;
+    const uint64_t want = std::max<uint64_t>(n, 1u << 16);
+    if (hipMalloc((void **)&e->bind_buf, want * 16) != hipSuccess) return fail(e, SA_ENOMEM, "sa_bind_ids: staging hipMalloc failed");
+    e->bind_cap = want;
+  }
+  // on the engine stream: after the previous bind's kernel (the staging's last
+  // reader) and, through ev_ctl, before every later ingest on any stream.
+  // Earlier launches still in flight do not read the key array.
+  SA_HIP(e, hipMemcpyAsync(e->bind_buf, index, n * 8, hipMemcpyHostToDevice, e->stream));
+  SA_HIP(e, hipMemcpyAsync(e->bind_buf + e->bind_cap, key_hash, n * 8, hipMemcpyHostToDevice, e->stream));
+  SA_HIP(e, sa::launch_dn_bind(e->gkeys, e->bind_buf, e->bind_buf + e->bind_cap, n, e->log2sb, e->stream));
+  // (the arrays are the caller's again when the call returns)
+  SA_HIP(e, hipStreamSynchronize(e->stream));
+  e->ctl_dirty = true;
+  for (uint64_t j = 0; j < n; ++j)
+    if (!is_bound(index[j])) {
+      e->bound[index[j] >> 6] |= 1ULL << (index[j] & 63);
+      ++e->n_bound;
+    }
   return SA_OK;
 }
 
@@ -1906,6 +2023,7 @@ int sa_gather_dense(sa_engine *e, const uint64_t *d_keys, uint64_t n, uint64_t *
                     void *stream) {
   if (!e || (n && (!d_keys || !d_rows))) return SA_EINVAL;
   if (e->expo) return fail(e, SA_ESTATE, "merge hooks cover explicit-bucket engines only");
+  if (e->dense) return fail(e, SA_ESTATE, "sa_gather_dense: a dense-index engine has no hash -> slot map on the device");
   if (int rc = set_dev(e)) return rc;
   if (int rc = join_checked(e)) return rc;
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : e->stream;

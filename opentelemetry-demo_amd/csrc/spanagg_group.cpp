@@ -494,6 +494,10 @@ int sa_group_create(const sa_config *cfg, const int32_t *devices, uint32_t n, sa
   if (!out) return SA_EINVAL;
   *out = nullptr;
   if (!cfg || !devices || n == 0 || n > kMaxMembers) return SA_EINVAL;
+  if (cfg->options & SA_OPT_DENSE_IDS) {  // groups merge by looking keys up by hash
+    std::fprintf(stderr, "sa_group_create: SA_OPT_DENSE_IDS engines cannot form a group\n");
+    return SA_EINVAL;
+  }
   auto *g = new sa_group();
   g->cfg = *cfg;
   g->bounds.assign(cfg->bounds, cfg->bounds + cfg->n_bounds);

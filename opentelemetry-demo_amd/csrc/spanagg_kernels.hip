@@ -1724,7 +1724,18 @@ __global__ void compact_kernel(const unsigned long long *gkeys, unsigned long lo
   for (uint64_t s = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; s < cap;
        s += (uint64_t)gridDim.x * blockDim.x) {
     const unsigned long long k = gkeys[s];
-    if (!k) continue;
+    if (!k) {
+      // dense-index engines: spans on an index that was never bound -- no
+      // row is reported; a resetting pass counts them dropped and clears them
+      if (g.dense && reset && row_nonzero(gcounts, s, g)) {
+        const uint8_t *cnt = reinterpret_cast<const uint8_t *>(gcounts + s * (kRowBytes / 8) + 1);  // (row8)
+        unsigned long long calls = 0;
+        for (uint32_t b = 0; b < g.nbk; ++b) calls += cnt[b] + g.base64[s * (g.nbk + 1) + b];
+        atomicAdd(g.dropped, calls);
+        row_zero(gcounts, s, g);
+      }
+      continue;
+    }
     if (!row_nonzero(gcounts, s, g)) continue;
     // one returning atomic per wave for its emitting lanes (a million lanes
     // on one counter serialised the compaction of a 1 M-series table)
@@ -1821,12 +1832,16 @@ __global__ void count_keys_kernel(const unsigned long long *gkeys, uint64_t cap,
 // its count-min cells, then clear them (so reads are idempotent).
 __global__ void fold_errcnt_kernel(const unsigned long long *gkeys, unsigned long long *errcnt,
                                    uint64_t cap, unsigned long long *cms, uint32_t d, uint32_t w,
-                                   uint32_t shift, const uint64_t *seeds, uint64_t kinv) {
+                                   uint32_t shift, const uint64_t *seeds, uint64_t kinv, uint32_t dense) {
   for (uint64_t s = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; s < cap;
        s += (uint64_t)gridDim.x * blockDim.x) {
     const unsigned long long c = errcnt[s];
     if (!c) continue;
     const uint64_t key = gkeys[s] * kinv;
+    if (dense && key == 0) {  // dense-index engines: ERROR spans on an unbound index touch no cell
+      errcnt[s] = 0;
+      continue;
+    }
     for (uint32_t r = 0; r < d; ++r) {
       const uint64_t col = splitmix64(key ^ seeds[r]) >> shift;
       atomicAdd(cms + (uint64_t)r * w + col, c);
@@ -2073,10 +2088,11 @@ hipError_t launch_gather_dense(const unsigned long long *gkeys, const unsigned l
 
 hipError_t launch_fold_errcnt(const unsigned long long *gkeys, unsigned long long *errcnt,
                               uint64_t cap, unsigned long long *cms, uint32_t d, uint32_t w,
-                              uint32_t shift, const uint64_t *seeds, uint64_t kinv, hipStream_t s) {
+                              uint32_t shift, const uint64_t *seeds, uint64_t kinv, uint32_t dense,
+                              hipStream_t s) {
   const uint32_t block = 256;
   hipLaunchKernelGGL(fold_errcnt_kernel, dim3(grid_for(cap, block, 2048)), dim3(block), 0, s, gkeys,
-                     errcnt, cap, cms, d, w, shift, seeds, kinv);
+                     errcnt, cap, cms, d, w, shift, seeds, kinv, dense);
   return hipGetLastError();
 }
 

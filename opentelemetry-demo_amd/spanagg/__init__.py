@@ -8,8 +8,9 @@ ranks.  Importing it does not require a GPU; creating an Engine does.
 from .engine import (DEFAULT_BOUNDS_MS, Config, Engine, Group, RedResult, SketchResult, SpanBatch,
                      bucket_thresholds, hll_estimate, pack_meta, trace_words)
 from ._lib import SpanAggError, load
+from .dense import DenseIds
 
 __all__ = [
-    "DEFAULT_BOUNDS_MS", "Config", "Engine", "Group", "RedResult", "SketchResult", "SpanBatch",
+    "DEFAULT_BOUNDS_MS", "Config", "DenseIds", "Engine", "Group", "RedResult", "SketchResult", "SpanBatch",
     "SpanAggError", "bucket_thresholds", "hll_estimate", "load", "pack_meta", "trace_words",
 ]

@@ -21,6 +21,8 @@ SA_MAX_BOUNDS = 62
 # the same results, for parity tests and A/B runs
 OPT_NO_HLL_FILTER, OPT_PARTITIONED, OPT_ATOMIC_TABLE, OPT_EXPO_HBM, OPT_EXPO_CACHED = 1, 2, 4, 8, 16
 OPT_IDENTITY_IDS, OPT_STAMPS, OPT_GROUP_COPY, OPT_GROUP_RCCL = 32, 64, 128, 256
+# the key_hash column carries dense series indices (spanagg.dense.DenseIds, Engine.bind_ids)
+OPT_DENSE_IDS = 512
 STATUS_NAMES = {
     SA_OK: "SA_OK", SA_EINVAL: "SA_EINVAL", SA_ENOMEM: "SA_ENOMEM", SA_EDEVICE: "SA_EDEVICE",
     SA_EFULL: "SA_EFULL", SA_ERANGE: "SA_ERANGE", SA_ESTATE: "SA_ESTATE",
@@ -112,6 +114,7 @@ SIGNATURES = [
     ("sa_window_advance", C.c_int, [C.c_void_p, C.c_uint64]),
     ("sa_sketch_result_free", None, [C.POINTER(sa_sketch_result)]),
     ("sa_get_stats", C.c_int, [C.c_void_p, C.POINTER(sa_stats)]),
+    ("sa_bind_ids", C.c_int, [C.c_void_p, u64p, u64p, C.c_uint64]),
     ("sa_export_keys", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, u64p, C.c_void_p]),
     ("sa_gather_dense", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p]),
     ("sa_window_export", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),

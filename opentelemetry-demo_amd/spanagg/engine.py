@@ -15,6 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import SpanAggError
+from .dense import DenseIds
 
 DEFAULT_BOUNDS_MS = (2, 4, 6, 8, 10, 50, 100, 200, 400, 800, 1000, 1400, 2000, 5000, 10000, 15000)
 
@@ -244,6 +245,10 @@ class Engine:
             raise SpanAggError(rc, "sa_create failed (is a gfx950 GPU visible?)")
         self._h = h
         self.n_buckets = len(self.config.bounds) + 1
+        # dense-index engines (OPT_DENSE_IDS): the host dictionary that makes
+        # the option transparent for host batches (ingest / ingest_async)
+        self.dense = bool(self.config.options & _lib.OPT_DENSE_IDS)
+        self.ids = DenseIds(self.stats()["table_capacity"]) if self.dense else None
 
     # -- lifecycle ---------------------------------------------------------
     def close(self):
@@ -268,19 +273,46 @@ class Engine:
             raise SpanAggError(rc, f"{what}: {self.lib.sa_last_error(self._h).decode()}")
 
     # -- hot path ----------------------------------------------------------
+    def bind_ids(self, index, key_hash):
+        """sa_bind_ids (dense-index engines): index[j] stands for series
+        key_hash[j] from now on, before every later ingest."""
+        i = np.ascontiguousarray(index, dtype=np.uint64)
+        h = np.ascontiguousarray(key_hash, dtype=np.uint64)
+        if len(i) != len(h):
+            raise ValueError("bind_ids: index and key_hash differ in length")
+        self._check(self.lib.sa_bind_ids(self._h, i.ctypes.data_as(_lib.u64p), h.ctypes.data_as(_lib.u64p), len(i)),
+                    "sa_bind_ids")
+
+    def _host_columns(self, batch: SpanBatch):
+        """The columns of a host batch as the engine takes them: on a dense
+        engine the real hashes are encoded through self.ids and the new
+        (index, hash) pairs bound first."""
+        cols = batch.columns()
+        if not self.dense:
+            return cols
+        ids, new_i, new_h = self.ids.encode(batch.key_hash)
+        if len(new_i):
+            self.bind_ids(new_i, new_h)
+        return (np.ascontiguousarray(ids, dtype=np.uint64),) + tuple(cols[1:])
+
     def ingest(self, batch: SpanBatch):
-        b = _lib.sa_span_batch(*[c.ctypes.data for c in batch.columns()], len(batch))
+        cols = self._host_columns(batch)
+        b = _lib.sa_span_batch(*[c.ctypes.data for c in cols], len(batch))
         self._check(self.lib.sa_ingest(self._h, C.byref(b)), "sa_ingest")
 
     def ingest_async(self, batch: SpanBatch):
         """sa_ingest_async: columns in sa_host_alloc memory stay the engine's
         until the next ingest_async (or sync) returns."""
-        b = _lib.sa_span_batch(*[c.ctypes.data for c in batch.columns()], len(batch))
+        cols = self._host_columns(batch)
+        self._async_keepalive = cols  # (a dense engine's encoded ids, until the next call)
+        b = _lib.sa_span_batch(*[c.ctypes.data for c in cols], len(batch))
         self._check(self.lib.sa_ingest_async(self._h, C.byref(b)), "sa_ingest_async")
 
     def ingest_device(self, key, start, end, w0, w1, meta, n: Optional[int] = None,
                       stream: Optional[int] = None):
-        """Device-resident batch: torch tensors (or raw device pointers)."""
+        """Device-resident batch: torch tensors (or raw device pointers).  On
+        a dense-index engine `key` holds indices as given: the caller encodes
+        (self.ids or its own dictionary) and binds (bind_ids) first."""
         if n is None:
             n = int(key.numel())
         b = _lib.sa_span_batch(_ptr(key), _ptr(start), _ptr(end), _ptr(w0), _ptr(w1),
@@ -313,6 +345,8 @@ class Engine:
     def flush(self, allow_drops: bool = False) -> RedResult:
         out = C.POINTER(_lib.sa_red_result)()
         rc = self.lib.sa_flush(self._h, C.byref(out))
+        if self.dense:
+            self.ids.flushed()
         return _red_result(self, rc, out, allow_drops, "sa_flush", self.lib.sa_flush)
 
     def window_read(self, window_id: int) -> SketchResult:
