@@ -233,16 +233,16 @@ constexpr uint32_t kDiagBtHotAcc = 1u << 25, kDiagBtHotErr = 1u << 26, kDiagBtSe
                    kDiagBtNoStore = 1u << 28;
 constexpr uint32_t kDiagBtFlush2 = 1u << 14;
 static const void *bt_scatter2_fn(uint32_t diag) {
-  if (diag & kDiagBtFlush2) return (const void *)&bt_scatter2_kernel<64>;
-  if (diag & kDiagBtSeqStore) return (const void *)&bt_scatter2_kernel<16>;
-  if (diag & kDiagBtNoStore) return (const void *)&bt_scatter2_kernel<32>;
-  if (diag & kDiagBtHotAcc) return (const void *)&bt_scatter2_kernel<4>;
-  if (diag & kDiagBtHotErr) return (const void *)&bt_scatter2_kernel<8>;
+  if (diag & kDiagBtFlush2) return (const void *)&bt_scatter2_kernel<BtHashed, 64>;
+  if (diag & kDiagBtSeqStore) return (const void *)&bt_scatter2_kernel<BtHashed, 16>;
+  if (diag & kDiagBtNoStore) return (const void *)&bt_scatter2_kernel<BtHashed, 32>;
+  if (diag & kDiagBtHotAcc) return (const void *)&bt_scatter2_kernel<BtHashed, 4>;
+  if (diag & kDiagBtHotErr) return (const void *)&bt_scatter2_kernel<BtHashed, 8>;
   switch (diag & 3u) {
-    case 1: return (const void *)&bt_scatter2_kernel<1>;
-    case 2: return (const void *)&bt_scatter2_kernel<2>;
-    case 3: return (const void *)&bt_scatter2_kernel<3>;
-    default: return (const void *)&bt_scatter2_kernel<0>;
+    case 1: return (const void *)&bt_scatter2_kernel<BtHashed, 1>;
+    case 2: return (const void *)&bt_scatter2_kernel<BtHashed, 2>;
+    case 3: return (const void *)&bt_scatter2_kernel<BtHashed, 3>;
+    default: return (const void *)&bt_scatter2_kernel<BtHashed, 0>;
   }
 }
 

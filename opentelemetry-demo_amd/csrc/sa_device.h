@@ -1,6 +1,7 @@
 // sa_device.h -- device-side helpers shared by the gfx950 kernels of libspanagg
 // (spanagg_kernels.hip: small-table, HBM-table and round-1 partitioned paths;
-// spanagg_binned.hip: the binned-table high-cardinality path).
+// spanagg_binned.hip, spanagg_dense.hip: the binned-table high-cardinality
+// path and its dense-index form).
 #pragma once
 #include "sa_internal.h"
 
@@ -189,17 +190,22 @@ __device__ __forceinline__ SA_GLOBAL T *gbl(T *p) {
   return (SA_GLOBAL T *)p;
 }
 
-__device__ __forceinline__ void hll_raise(uint8_t *reg, uint32_t rho) {
-  SA_GLOBAL uint32_t *word =
-      gbl(reinterpret_cast<uint32_t *>(reinterpret_cast<uintptr_t>(reg) & ~uintptr_t(3)));
-  const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(reg) & 3) * 8;
-  uint32_t old = __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+// The raise itself, from a value of the word already read (`old`; sh = the
+// register's bit offset in the word).
+__device__ __forceinline__ void hll_raise_from(SA_GLOBAL uint32_t *word, uint32_t old, uint32_t sh, uint32_t rho) {
   while (((old >> sh) & 0xFFu) < rho) {  // a failed CAS refreshes `old`
     const uint32_t nw = (old & ~(0xFFu << sh)) | (rho << sh);
     if (__hip_atomic_compare_exchange_strong(word, &old, nw, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
                                              __HIP_MEMORY_SCOPE_AGENT))
       break;
   }
+}
+
+__device__ __forceinline__ void hll_raise(uint8_t *reg, uint32_t rho) {
+  SA_GLOBAL uint32_t *word =
+      gbl(reinterpret_cast<uint32_t *>(reinterpret_cast<uintptr_t>(reg) & ~uintptr_t(3)));
+  const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(reg) & 3) * 8;
+  hll_raise_from(word, __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), sh, rho);
 }
 
 // Per-lane event counters, updated arithmetically (no addressable struct, so
@@ -485,6 +491,22 @@ __device__ __forceinline__ SA_CONST const IngestParams &cold_params() {
       (SA_CONST const IngestParams *)__builtin_amdgcn_kernarg_segment_ptr();
   asm volatile("" : "+s"(kp));
   return *kp;
+}
+
+// The kernel's parameters in the kernarg segment, as a pointer.  Taken in the
+// kernel body and passed to cold paths that are real calls (__noinline__,
+// where __builtin_amdgcn_kernarg_segment_ptr -- cold_params -- is not valid),
+// so the fields only they use do not occupy scalar registers in the span loop.
+typedef SA_CONST const IngestParams *KParams;
+__device__ __forceinline__ KParams kernel_params() {
+  return (KParams)__builtin_amdgcn_kernarg_segment_ptr();
+}
+
+__device__ __forceinline__ void compiler_fence() { asm volatile("" ::: "memory"); }
+
+// This lane's rank among the set lanes of a ballot mask below it.
+__device__ __forceinline__ uint32_t lane_rank(uint64_t mask) {
+  return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
 
 __device__ __forceinline__ void cold_cms_add(uint32_t ws, uint64_t key) {

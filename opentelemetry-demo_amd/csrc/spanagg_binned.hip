@@ -8,7 +8,9 @@
 // and adds the sketch updates.
 //
 // Two kernels per launch:
-//   bt_scatter2_kernel (one 1,024-thread workgroup per CU, ~160 KiB LDS)
+//   bt_scatter2_kernel<BtHashed> (one 1,024-thread workgroup per CU, ~160 KiB
+//   LDS; the template is sa_bt_scatter.h, shared with spanagg_dense.hip, and
+//   BtHashed below is this path's part of it)
 //     streams the SoA batch once (register tile ring, 16-B nt buffer loads:
 //     the C2 kernel's skeleton), does the per-span stats and HLL work, and
 //     writes one 16-B record {m's low 53 bits | ERROR flag | window slot,
@@ -29,12 +31,10 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "sa_device.h"
+#include "sa_bt_scatter.h"
 
 namespace sa {
 namespace {
-
-__device__ __forceinline__ void compiler_fence() { asm volatile("" ::: "memory"); }
 
 // Find-or-insert m in its bin's sub-table (HBM, CAS); kNotFound when the
 // bin is full.  Plain probe reads, as g_find_insert (a stale 0 is corrected
@@ -61,15 +61,6 @@ __device__ __forceinline__ void spill_add(unsigned long long *base64, uint32_t n
   unsigned long long *row = base64 + (uint64_t)s * (nbk + 1);
   if (cnt) atomicAdd(row + bk, (unsigned long long)cnt);
   if (dsum) atomicAdd(row + nbk, dsum);
-}
-
-// The kernel's parameters in the kernarg segment.  Taken in the kernel body
-// and passed to the cold paths below (which are real calls, where
-// __builtin_amdgcn_kernarg_segment_ptr -- cold_params -- is not valid), so
-// the fields only they use do not occupy scalar registers in the span loop.
-typedef SA_CONST const IngestParams *KParams;
-__device__ __forceinline__ KParams kernel_params() {
-  return (KParams)__builtin_amdgcn_kernarg_segment_ptr();
 }
 
 // Count-min cells of one ERROR span without a key-table slot (d atomics).
@@ -102,410 +93,50 @@ __device__ __noinline__ uint32_t bt_cold_direct(KParams Q, uint64_t m, uint64_t 
   return 0u;
 }
 
-// Diagnostic per-workgroup timestamps (SPANAGG_STAMPS builds of the engine):
-// s_memrealtime (100 MHz, comparable across CUs) into dbg[base + k].
-__device__ __forceinline__ void bt_stamp(const IngestParams &P, uint64_t base, uint32_t k) {
-  if (P.dbg && threadIdx.x == 0) P.dbg[base + k] = __builtin_amdgcn_s_memrealtime();
-}
-
-__device__ __forceinline__ uint32_t lane_rank(uint64_t mask) {
-  return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
-
-// Round-synchronous scatter.  The workgroup takes its span range in rounds of
-// 2,048 spans (one 128-span tile per wave, two rounds of tiles in flight);
-// every span claims a slot of its bin's 4-record LDS stage with one LDS
-// atomic.  After a barrier each wave collects the full stages of the 128 bins
-// it owns into a list and writes them out four lanes per stage, so every
-// stage leaves as one aligned 64-B piece of a single store instruction; a
-// second barrier frees the stages for the next round.  Keys already in the
-// overflow table (the hot keys of a skewed mix) are added there directly;
-// a span whose stage is full in its round, or whose region is used up, goes
-// to the overflow table, past that the direct path.  The record layout
-// ({m's low 53 bits | ERROR flag | window slot, duration} per (bin,
-// workgroup) region) is the one bt_aggregate3_kernel reads.
-// MODE (ablation): 1 = no records, 2 = no HLL, 4 = overflow-table adds
-// skipped, 8 = overflow-table ERROR counts skipped.
-template <int MODE = 0>
-__global__ __launch_bounds__(kBtBlock) void bt_scatter2_kernel(IngestParams P) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr uint32_t kWaves = kBtBlock / 64;
-  ulonglong2 *stage = reinterpret_cast<ulonglong2 *>(smem);                          // [bins][4]
-  uint32_t *fillw = reinterpret_cast<uint32_t *>(stage + kPartBins * kBtStage);      // [bins / 2] u16 pairs
-  uint32_t *rcnw = fillw + kPartBins / 2;                                            // [bins / 2] region fills
-  uint16_t *flist = reinterpret_cast<uint16_t *>(rcnw + kPartBins / 2);              // [waves][128]
-  unsigned long long *hkey = reinterpret_cast<unsigned long long *>(flist + kWaves * 128);
-  unsigned long long *hsum = hkey + kBt2Hot;
-  uint32_t *hcnt = reinterpret_cast<uint32_t *>(hsum + kBt2Hot);  // [kBt2Hot][kPartWords] u16 pairs
-  uint2 *hq = reinterpret_cast<uint2 *>(hcnt + kBt2Hot * kPartWords);
-  uint32_t *hq_n = reinterpret_cast<uint32_t *>(hq + kBtHq);
-  BinEntry *lbins = reinterpret_cast<BinEntry *>(hq_n + 4);
-  uint2 *herr = reinterpret_cast<uint2 *>(lbins + kBins);  // [kBt2HotErr] {(ws << 8 | entry) + 1, count}
-  uint8_t *llb = reinterpret_cast<uint8_t *>(herr + kBt2HotErr);
-  const KParams kp = kernel_params();
-  const uint64_t sbase = (uint64_t)kPartBins * 8 + blockIdx.x * 8;
-  bt_stamp(P, sbase, 0);
-
-  uint64_t lo, hi;
-  wg_range_p(P, lo, hi);
-  const uint32_t len = (uint32_t)(hi - lo);
-  constexpr uint32_t kRound = kBtBlock * 2;
-  const uint32_t lane = threadIdx.x & 63u, lane_off = lane * 2;
-  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const uint32_t rounds = (len + kRound - 1) / kRound;
-  auto tstart = [&](uint32_t r) -> uint32_t { return r * kRound + wave * 128; };
-  auto tremain = [&](uint32_t t) -> uint32_t { return len > t ? len - t : 0u; };
-
-  // prologue: bin table and bounds, the first two rounds' tiles, LDS setup
-  uint4 bv = make_uint4(0, 0, 0, 0);
-  if (threadIdx.x < kBins * 2) bv = reinterpret_cast<const uint4 *>(P.bintab)[threadIdx.x];
-  const uint32_t lb_on = P.lb_n != 0 && !(MODE & 2);
-  uint32_t lbw = 0;
-  if (lb_on && threadIdx.x * 4 < P.lb_n) lbw = *reinterpret_cast<const uint32_t *>(P.hll_lb + threadIdx.x * 4);
-  SpanTile<2> buf[2];
-  Pending<2> pend, pend2;  // HLL reads of the last two rounds (compared two rounds later:
-                           // the flush stores between a read and its compare would
-                           // otherwise make that wait drain the prefetched tiles too)
-  load_tile_at<2, 2>(P, lo + tstart(0), tremain(tstart(0)), lane_off, buf[0]);
-  load_tile_at<2, 2>(P, lo + tstart(1), tremain(tstart(1)), lane_off, buf[1]);
-  {
-    uint32_t z;  // a VGPR zero keeps these vector loads
-    asm volatile("v_mov_b32 %0, 0" : "=v"(z));
-#pragma unroll
-    for (int j = 0; j < 2; ++j) pend.hv[j] = pend2.hv[j] = *reinterpret_cast<const uint32_t *>(P.hll + z);
+// The scatter's Path (sa_bt_scatter.h) for series given by hash.  The id is
+// m = key * kmul (its top bits pick the bin; key 0 has no record); a record
+// is 16 B {m's low 53 bits | ERROR flag | window slot, duration | bucket}, in
+// 4-record stages.  A span past the overflow table takes the key-table path
+// (find-or-insert, atomics into the spill array; count-min when the bin is
+// full, the span then counted as dropped), and the epilogue looks every
+// overflow-table entry up the same way.
+struct BtHashed {
+  typedef uint64_t Id;
+  typedef ulonglong2 Rec;
+  static constexpr uint32_t kStage = kBtStage;
+  static constexpr uint64_t kDurMask = kRecDurMask;
+  static constexpr uint32_t kBinLsb = kBinShift;
+  static constexpr bool kStamps = true, kLookup = true, kClampDrain = false;
+  static __device__ __forceinline__ Id id(const IngestParams &P, uint64_t key, uint32_t &, uint64_t) {
+    return key * P.kmul;
   }
-  for (uint32_t b = threadIdx.x; b < kPartBins / 2; b += kBtBlock) fillw[b] = rcnw[b] = 0;
-  for (uint32_t h = threadIdx.x; h < kBt2Hot; h += kBtBlock) hkey[h] = hsum[h] = 0;
-  for (uint32_t h = threadIdx.x; h < kBt2Hot * kPartWords; h += kBtBlock) hcnt[h] = 0;
-  if (threadIdx.x < kBt2HotErr) herr[threadIdx.x] = make_uint2(0, 0);
-  if (threadIdx.x < kBins * 2) reinterpret_cast<uint4 *>(lbins)[threadIdx.x] = bv;
-  if (lb_on && threadIdx.x * 4 < P.lb_n) reinterpret_cast<uint32_t *>(llb)[threadIdx.x] = lbw;
-  if (threadIdx.x == 0) hq_n[0] = 0;
-  __syncthreads();
-  bt_stamp(P, sbase, 1);
-
-  uint32_t n_zero = 0, n_badsvc = 0, n_oor = 0;  // wave-uniform (SGPR)
-  uint32_t n_drop = 0;                           // per lane
-  uint32_t n_filt = 0;                           // per lane: HLL updates the lower-bound filter skipped
-#pragma unroll
-  for (int j = 0; j < 2; ++j) pend.hoff[j] = pend.rho[j] = pend2.hoff[j] = pend2.rho[j] = 0;
-  const uint32_t region = P.bt_region;
-  ulonglong2 *my_rec = P.bt_rec + (uint64_t)blockIdx.x * region;  // + bin * grid * region
-  const uint64_t bin_stride = (uint64_t)P.bt_grid * region;
-
-  // overflow-table home: an even entry, probed as a pair first
-  auto hot_home = [&](uint64_t m) -> uint32_t {
-    return (uint32_t)(((uint64_t)(uint32_t)(m >> 21) * (kBt2Hot / 2)) >> 32) * 2;
-  };
-  auto hot_acc = [&](uint32_t h, uint64_t m, uint64_t d, bool err, uint32_t ws) {
-    if (MODE & 4) return;
-    const uint32_t bk = bucket_lds<1>(d, lbins, P);
-    atomicAdd(&hcnt[h * kPartWords + (bk >> 1)], 1u << ((bk & 1u) * 16));
-    atomicAdd(&hsum[h], (unsigned long long)d);
-    if (err && !(MODE & 8)) {  // ERROR count per (window slot, entry); a full table takes the key-table path
-      const uint32_t ek = ((ws << 8) | h) + 1;
-      uint32_t e = (ek * 0x9E3779B1u) >> 25;  // kBt2HotErr = 128
-      for (int pr = 0; pr < 4; ++pr, e = (e + 1) & (kBt2HotErr - 1)) {
-        uint32_t k = herr[e].x;
-        if (k == 0) k = atomicCAS(&herr[e].x, 0u, ek);
-        if (k == 0 || k == ek) {
-          atomicAdd(&herr[e].y, 1u);
-          return;
-        }
-      }
-      bt_cold_err(kp, m, ws);
-    }
-  };
-  // the overflow table: false when the key is not in it and its 8 probes
-  // are taken
-  auto hot_try = [&](uint64_t m, uint64_t d, bool err, uint32_t ws) -> bool {
-    uint32_t h = hot_home(m);
-    for (int pr = 0; pr < 8; ++pr) {
-      unsigned long long k = hkey[h];
-      if (k == 0) k = atomicCAS(&hkey[h], 0ULL, (unsigned long long)m);
-      if (k == 0 || k == m) {
-        hot_acc(h, m, d, err, ws);
-        return true;
-      }
-      h = h + 1 == kBt2Hot ? 0u : h + 1;
-    }
-    return false;
-  };
-  // a span its region cannot take: the overflow table, else the direct path
-  auto hot_add = [&](uint64_t m, uint64_t d, bool err, uint32_t ws) {
-    if (hot_try(m, d, err, ws)) return;
-    const uint32_t bk = bucket_lds<1>(d, lbins, P);
-    n_drop += bt_cold_direct(kp, m, d, bk, err, ws);
-  };
-  auto hot_rec = [&](uint32_t b, const ulonglong2 &r) {
-    const uint64_t m = ((uint64_t)b << kBinShift) | (r.x & kBinRest);
-    hot_add(m, r.y & kRecDurMask, (r.x >> 63) != 0, (uint32_t)(r.x >> kBinShift) & 1023u);
-  };
-  // claims n record positions of bin b's region (u16 pairs); positions at or
-  // past the region's end take the overflow table instead
-  auto claim = [&](uint32_t b, uint32_t n) -> uint32_t {
-    const uint32_t sh = (b & 1u) * 16;
-    return (atomicAdd(&rcnw[b >> 1], n << sh) >> sh) & 0xFFFFu;
-  };
-  auto place = [&](uint64_t m, uint64_t d, bool err, uint32_t ws) {
-    const uint32_t h0 = hot_home(m);
-    const ulonglong2 hk = *reinterpret_cast<const ulonglong2 *>(hkey + h0);
-    if (hk.x == m || hk.y == m) {
-      hot_acc(h0 + (hk.x == m ? 0u : 1u), m, d, err, ws);
-      return;
-    }
-    const uint32_t bk = bucket_lds<1>(d, lbins, P);
-    if (__builtin_expect(d > kRecDurMask, 0)) {  // beyond the record's duration bits: the direct path
-      n_drop += bt_cold_direct(kp, m, d, bk, err, ws);
-      return;
-    }
-    const uint32_t b = (uint32_t)(m >> kBinShift), sh = (b & 1u) * 16;
-    const uint32_t c = (atomicAdd(&fillw[b >> 1], 1u << sh) >> sh) & 0xFFFFu;
-    const ulonglong2 rec = make_ulonglong2((m & kBinRest) | (err ? (1ULL << 63) | ((uint64_t)ws << kBinShift) : 0ULL),
-                                           d | ((uint64_t)bk << kRecDurBits));
-    if (c < kBtStage) {
-      stage[b * kBtStage + c] = rec;
-      return;
-    }
-    // the stage is full this round.  A key that holds two or more of its
-    // slots is frequent (a hot key of a skewed mix): it moves to the overflow
-    // table; any other record is stored on its own.  (The slots may hold this
-    // round's records or, not yet overwritten, an earlier round's: either way
-    // records of this bin, which is all the test needs.)
-    uint32_t same = 0;
-#pragma unroll
-    for (uint32_t q = 0; q < kBtStage; ++q) same += ((stage[b * kBtStage + q].x ^ rec.x) & kBinRest) == 0 ? 1u : 0u;
-    // (a frequent key the full overflow table cannot take stays a record:
-    // the per-span direct path is only for a region that is used up)
-    if (same >= 2 && hot_try(m, d, err, ws)) return;
-    const uint32_t at = claim(b, 1);
-    if (at < region) my_rec[b * bin_stride + at] = rec;
-    else hot_add(m, d, err, ws);
-  };
-  auto hll_settle = [&](const Pending<2> &q) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      if (((q.hv[j] >> ((q.hoff[j] & 3u) * 8)) & 0xFFu) < q.rho[j]) {
-        const uint32_t slot = atomicAdd(&hq_n[0], 1u);
-        if (slot < kBtHq) hq[slot] = make_uint2(q.hoff[j], q.rho[j]);
-        else hll_raise(kp->hll + q.hoff[j], q.rho[j]);
-      }
-    }
-  };
-
-  const uint32_t hp = P.p, lbs = P.lb_shift;
-  auto step = [&](SpanTile<2> &T, uint32_t toff, uint32_t pf) {
-    uint64_t m[2], d[2];
-    uint32_t ws[2], hoff[2], rho[2];
-    bool err[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const bool valid = lane_off + toff + (uint32_t)j < len;
-      const uint64_t key = copy_u64(T.key[j]);  // 0 past the range
-      n_zero += wave_count(valid && key == 0);
-      d[j] = T.e[j] > T.s[j] ? T.e[j] - T.s[j] : 0;
-      const uint32_t meta = copy_u32(T.meta[j]);
-      const uint32_t svc = meta & 0xFFFFu;
-      const bool svc_ok = svc < P.n_services;
-      ws[j] = window_slot_lean(P, T.e[j]);
-      const bool win_ok = ws[j] != 0xFFFFFFFFu;
-      n_badsvc += wave_count(valid && !svc_ok);
-      n_oor += wave_count(valid && svc_ok && !win_ok);
-      const bool sk = valid && svc_ok && win_ok;
-      err[j] = sk && ((meta >> 19) & 3u) == 2u;
-      // the span hash on 32-bit halves, rho without 64-bit shifts, the
-      // register row by a 24-bit multiply-add (as the lean C2 kernel)
-      const H64 x = xxh64_16_h(T.a[j], T.b[j]);
-      const uint32_t yh = __builtin_amdgcn_alignbit(x.hi, x.lo, 32 - hp), yl = (x.lo << hp) | (1u << (hp - 1));
-      const uint32_t r = (uint32_t)__clzll((long long)(((uint64_t)yh << 32) | yl)) + 1;
-      uint32_t row;
-      asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(row) : "v"(ws[j]), "s"(P.n_services), "v"(svc));
-      const uint32_t ho = sk ? (row << hp) + (x.hi >> (32 - hp)) : 0u;
-      bool up = sk && !(MODE & 2);
-      if (lb_on) {
-        const bool f = r <= llb[ho >> lbs];
-        n_filt += (up && f) ? 1u : 0u;
-        up = up && !f;
-      }
-      rho[j] = up ? r : 0u;
-      hoff[j] = up ? ho : 0u;
-      m[j] = key * P.kmul;
-    }
-    uint32_t hv[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-      hv[j] = (MODE & 2) ? 0xFFFFFFFFu : *reinterpret_cast<const uint32_t *>(P.hll + (hoff[j] & ~3u));
-    __builtin_amdgcn_sched_barrier(0);
-    load_tile_at<2, 2>(P, lo + pf, tremain(pf), lane_off, T);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      if (MODE & 1) n_drop += (uint32_t)((m[j] ^ d[j]) == 0x123456789ABCULL);  // keep the values live
-      else if (m[j] != 0) place(m[j], d[j], err[j], ws[j]);
-    }
-    hll_settle(pend2);
-    pend2 = pend;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      pend.hoff[j] = hoff[j];
-      pend.rho[j] = rho[j];
-      pend.hv[j] = hv[j];
-    }
-  };
-  // the waves write out the full stages of their 128 bins (4 lanes a stage)
-  uint16_t *wl = flist + wave * 128;
-  auto flush = [&]() {
-    const uint32_t fw = fillw[threadIdx.x];  // bins 2t, 2t + 1
-    const bool f0 = (fw & 0xFFFFu) >= kBtStage, f1 = (fw >> 16) >= kBtStage;
-    if (f0 || f1) fillw[threadIdx.x] = (f0 ? 0u : (fw & 0xFFFFu)) | (f1 ? 0u : (fw & 0xFFFF0000u));
-    const uint64_t m0 = __ballot(f0), m1 = __ballot(f1);
-    const uint32_t n0 = (uint32_t)__popcll(m0), nf = n0 + (uint32_t)__popcll(m1);
-    if (f0) wl[lane_rank(m0)] = (uint16_t)(2 * threadIdx.x);
-    if (f1) wl[n0 + lane_rank(m1)] = (uint16_t)(2 * threadIdx.x + 1);
-    compiler_fence();  // one wave's LDS operations complete in order
-    for (uint32_t i0 = 0; i0 < nf; i0 += 16) {  // wave-uniform
-      const uint32_t i = i0 + (lane >> 2), q = lane & 3u;
-      const bool act = i < nf;
-      const uint32_t b = act ? wl[i] : 0u;
-      const ulonglong2 r = stage[b * kBtStage + q];
-      uint32_t at = act && q == 0 ? claim(b, kBtStage) : 0u;
-      at = (uint32_t)__shfl((int)at, (int)(lane & ~3u), 64);
-      if (act) {
-        if (MODE & 16) my_rec[(uint64_t)threadIdx.x * 64 + ((i0 + at) & 63)] = r;  // ablation: no scatter
-        else if (MODE & 32) (void)0;                                          // ablation: no store
-        else if (at + q < region) my_rec[b * bin_stride + at + q] = r;
-        else hot_rec(b, r);
-      }
-    }
-  };
-
-  // Stage flushes: after every round, or -- once the first two rounds have
-  // put 32 or more keys in the overflow table (a skewed mix, whose hot keys
-  // bypass the stages) -- after every second round, which halves the
-  // barriers (for uniform keys the fuller stages would spill more records).
-  bool sparse = false;  // workgroup-uniform: read from LDS after a barrier
-  for (uint32_t r = 0; r < rounds; r += 2) {
-    step(buf[0], tstart(r), tstart(r + 2));
-    if (!sparse) {
-      __syncthreads();
-      if (!(MODE & 1)) flush();
-      __syncthreads();
-    }
-    if (r + 1 < rounds) step(buf[1], tstart(r + 1), tstart(r + 3));
-    __syncthreads();
-    if (!(MODE & 1)) flush();
-    if (r == 0 && wave == 0) {
-      uint32_t used = 0;
-      for (uint32_t h = lane; h < kBt2Hot; h += 64) used += wave_count(hkey[h] != 0);
-      if (lane == 0) hq_n[2] = used >= 32 ? 1u : 0u;
-    }
-    __syncthreads();
-    if (r == 0) sparse = (MODE & 64) ? true : hq_n[2] != 0;
+  static __device__ __forceinline__ uint32_t home_hash(Id m) { return (uint32_t)(m >> 21); }
+  static __device__ __forceinline__ Rec rec(Id m, uint64_t d, uint32_t bk, bool err, uint32_t ws) {
+    return make_ulonglong2((m & kBinRest) | (err ? (1ULL << 63) | ((uint64_t)ws << kBinShift) : 0ULL),
+                           d | ((uint64_t)bk << kRecDurBits));
   }
-  hll_settle(pend2);
-  hll_settle(pend);
-  // the wave's bound sub-block, loaded now (hll_lb_pre): it lands during the
-  // stage flush and the overflow table's key lookups below
-  uint4 lbv[4];
-  hll_lb_pre<kBtBlock>(P, lbv);
-  bt_stamp(P, sbase, 2);
-  // partial stages, then this workgroup's region fills
-  for (uint32_t b = threadIdx.x; b < kPartBins; b += kBtBlock) {
-    const uint32_t c = (fillw[b >> 1] >> ((b & 1u) * 16)) & 0xFFFFu;  // < kBtStage after the last flush
-    const uint32_t at = c ? claim(b, c) : 0u;
-    for (uint32_t q = 0; q < c; ++q) {
-      if (at + q < region) my_rec[b * bin_stride + at + q] = stage[b * kBtStage + q];
-      else hot_rec(b, stage[b * kBtStage + q]);
-    }
+  static __device__ __forceinline__ Id rec_id(uint32_t b, const Rec &r) {
+    return ((uint64_t)b << kBinShift) | (r.x & kBinRest);
   }
-  __syncthreads();
-  // the queued HLL raises' register words, read now (the queue is final after
-  // the barrier above) and CAS-raised at the end: the reads overlap the
-  // overflow table's lookups instead of adding a round trip
-  const uint32_t nq = min(hq_n[0], kBtHq);
-  constexpr uint32_t kQ = (kBtHq + kBtBlock - 1) / kBtBlock;
-  uint32_t qv[kQ];
-#pragma unroll
-  for (uint32_t i = 0; i < kQ; ++i) {
-    const uint32_t t = threadIdx.x + i * kBtBlock;
-    qv[i] = t < nq ? __hip_atomic_load(reinterpret_cast<const uint32_t *>(P.hll + (hq[t].x & ~3u)), __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT)
-                   : 0u;
+  static __device__ __forceinline__ uint64_t rec_d(const Rec &r) { return r.y & kRecDurMask; }
+  static __device__ __forceinline__ bool rec_err(const Rec &r) { return (r.x >> 63) != 0; }
+  static __device__ __forceinline__ uint32_t rec_ws(const Rec &r) { return (uint32_t)(r.x >> kBinShift) & 1023u; }
+  static __device__ __forceinline__ bool same_id(const Rec &a, const Rec &b) { return ((a.x ^ b.x) & kBinRest) == 0; }
+  // the cold paths take the id; cold_direct returns 1 when the span was dropped
+  static __device__ __forceinline__ Id cold_key(const IngestParams &, Id m) { return m; }
+  static __device__ __forceinline__ uint32_t cold_direct(KParams kp, Id m, uint64_t d, uint32_t bk, bool err,
+                                                         uint32_t ws) {
+    return bt_cold_direct(kp, m, d, bk, err, ws);
   }
-  for (uint32_t b = threadIdx.x; b < kPartBins; b += kBtBlock)
-    P.bt_cnt[(uint64_t)b * P.bt_grid + blockIdx.x] = min((rcnw[b >> 1] >> ((b & 1u) * 16)) & 0xFFFFu, region);
-  __syncthreads();
-  // the overflow table: each entry's key slot (find-or-insert, one lane per
-  // entry) into the LDS of the flush lists (the stages are all out) ...
-  uint32_t *hslot = reinterpret_cast<uint32_t *>(flist);  // [kBt2Hot]
-  for (uint32_t h = threadIdx.x; h < kBt2Hot; h += kBtBlock) {
-    const unsigned long long m = hkey[h];
-    uint32_t s = kNotFound;
-    if (m != 0) {
-      s = bt_find_insert(P.gkeys, m, P.log2sb);
-      if (s == kNotFound)
-        for (uint32_t b = 0; b < P.nbk; ++b) n_drop += (hcnt[h * kPartWords + (b >> 1)] >> ((b & 1u) * 16)) & 0xFFFFu;
-    }
-    hslot[h] = s;
+  static __device__ __forceinline__ void cold_err(KParams kp, Id m, uint32_t ws) { bt_cold_err(kp, m, ws); }
+  static __device__ __forceinline__ uint32_t lookup(const IngestParams &P, Id m) {
+    return bt_find_insert(P.gkeys, m, P.log2sb);
   }
-  __syncthreads();
-  // ... then its row added to the spill array (atomics: the entries of one key
-  // come from every workgroup), two entries per wave instruction and one cell
-  // per lane: an entry's nbk counts and ns sum are contiguous in base64, so it
-  // leaves as three 64-B atomic requests, where one lane's nbk + 1 serial
-  // atomics made a Zipf mix's epilogue (hundreds of hot keys in every
-  // workgroup's table) the scatter's longest phase
-  {
-    const uint32_t half = lane >> 5, cell = lane & 31u, nc = P.nbk + 1;
-    static_assert(kBt2Hot % 2 == 0 && kPartMaxBk + 1 <= 32, "overflow flush geometry");
-    for (uint32_t h0 = wave * 2; h0 < kBt2Hot; h0 += kWaves * 2) {
-      const uint32_t h = h0 + half;
-      const uint32_t s = hslot[h];
-      if (s == kNotFound || cell >= nc) continue;
-      const unsigned long long v = cell == P.nbk ? hsum[h]
-                                                 : (hcnt[h * kPartWords + (cell >> 1)] >> ((cell & 1u) * 16)) & 0xFFFFu;
-      if (v) atomicAdd(P.base64 + (uint64_t)s * nc + cell, v);
-    }
+  // one ERROR span of an overflow-table entry whose bin is full
+  static __device__ __forceinline__ void err_no_row(KParams kp, const IngestParams &P, Id m, uint32_t ws) {
+    bt_cms_add(kp, ws, m * P.kinv);
   }
-  if (threadIdx.x < kBt2HotErr) {
-    const uint2 e = herr[threadIdx.x];
-    if (e.x) {
-      const uint32_t ws = (e.x - 1) >> 8, h = (e.x - 1) & 0xFFu;
-      const uint32_t s = hslot[h];
-      if (s != kNotFound) atomicAdd(P.errcnt + ((uint64_t)ws << P.log2cap) + s, (unsigned long long)e.y);
-      else
-        for (uint32_t i = 0; i < e.y; ++i) bt_cms_add(kp, ws, hkey[h] * P.kinv);
-    }
-  }
-#pragma unroll
-  for (uint32_t i = 0; i < kQ; ++i) {
-    const uint32_t t = threadIdx.x + i * kBtBlock;
-    if (t >= nq) continue;
-    const uint2 q = hq[t];
-    SA_GLOBAL uint32_t *word = gbl(reinterpret_cast<uint32_t *>(P.hll + (q.x & ~3u)));
-    const uint32_t sh = (q.x & 3u) * 8;
-    uint32_t old = qv[i];
-    while (((old >> sh) & 0xFFu) < q.y) {  // a failed CAS refreshes `old`
-      const uint32_t nw = (old & ~(0xFFu << sh)) | (q.y << sh);
-      if (__hip_atomic_compare_exchange_strong(word, &old, nw, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                               __HIP_MEMORY_SCOPE_AGENT))
-        break;
-    }
-  }
-  n_drop = wave_sum(n_drop);
-  n_filt = wave_sum(n_filt);
-  if (lane == 0) {
-    // a slot per workgroup (same-address atomics from every wave would
-    // serialise the tail of the launch)
-    if (n_filt) atomicAdd(&P.hll_filt[blockIdx.x & (kFiltSlots - 1)], (unsigned long long)n_filt);
-    if (n_zero) atomicAdd(&P.stats[kStatZeroKey], (unsigned long long)n_zero);
-    if (n_badsvc) atomicAdd(&P.stats[kStatInvalidService], (unsigned long long)n_badsvc);
-    if (n_oor) atomicAdd(&P.stats[kStatWindowOOR], (unsigned long long)n_oor);
-    if (n_drop) atomicAdd(&P.stats[kStatDropped], (unsigned long long)n_drop);
-  }
-  hll_lb_finish<kBtBlock>(P, lbv);
-  bt_stamp(P, sbase, 3);
-}
+};
 
 // Aggregate geometry (bt_aggregate3_kernel; the laboratory build's earlier
 // form bt_aggregate2_kernel shares it).  One 512-thread workgroup per bin;
@@ -866,7 +497,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 1024 ? 8 : 6) void bt_aggregate3_ke
 #else
 // Product build: one scatter and one aggregate (bins of up to 1,024 slots, or
 // the wide form for 2,048).
-static const void *bt_scatter2_fn(uint32_t) { return (const void *)&bt_scatter2_kernel<0>; }
+static const void *bt_scatter2_fn(uint32_t) { return (const void *)&bt_scatter2_kernel<BtHashed, 0>; }
 constexpr uint32_t kDiagBtAggWide = 1u << 30;
 static const void *bt_agg_fn(uint32_t diag) {
   return (diag & kDiagBtAggWide) ? (const void *)&bt_aggregate3_kernel<0, 4> : (const void *)&bt_aggregate3_kernel<0, 2>;

@@ -9,11 +9,13 @@
 // from the first series on).  Nothing is looked up or inserted anywhere.
 //
 // Two kernels per launch, the shape of spanagg_binned.hip's:
-//   dn_scatter_kernel (one 1,024-thread workgroup per CU, ~160 KiB LDS)
-//     bt_scatter2_kernel's skeleton -- register tile ring, per-span stats,
-//     HLL with the lower-bound filter, round-synchronous LDS stages per bin,
-//     the LDS overflow table for hot indices, the same bt_cnt region fills --
-//     with 8-B records (dn_rec) in 8-record stages that leave as aligned 64-B
+//   bt_scatter2_kernel<BtDense> (one 1,024-thread workgroup per CU, ~160 KiB
+//   LDS; the binned path's scatter template, sa_bt_scatter.h, with BtDense
+//   below as its Path)
+//     register tile ring, per-span stats, HLL with the lower-bound filter,
+//     round-synchronous LDS stages per bin, the LDS overflow table for hot
+//     indices and the bt_cnt region fills are the template's; BtDense gives it
+//     8-B records (dn_rec) in 8-record stages that leave as aligned 64-B
 //     chunks, no multiply, and cold paths (region used up, duration beyond
 //     the record's bits) that add straight into base64[row] and
 //     errcnt[ws][row] with atomics.
@@ -29,17 +31,10 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "sa_device.h"
+#include "sa_bt_scatter.h"
 
 namespace sa {
 namespace {
-
-__device__ __forceinline__ void compiler_fence() { asm volatile("" ::: "memory"); }
-
-typedef SA_CONST const IngestParams *KParams;
-__device__ __forceinline__ KParams kernel_params() {
-  return (KParams)__builtin_amdgcn_kernarg_segment_ptr();
-}
 
 // The 8-B record of one span in the region of (its bin, scatter workgroup):
 //   bits  0-36  duration in ns (a longer span, 137 s, takes the cold path)
@@ -70,360 +65,49 @@ __device__ __noinline__ void dn_cold_err(KParams Q, uint32_t row, uint32_t ws) {
   atomicAdd(Q->errcnt + ((uint64_t)ws << Q->log2cap) + row, 1ULL);
 }
 
-__device__ __forceinline__ uint32_t lane_rank(uint64_t mask) {
-  return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
-
-// Round-synchronous scatter (see bt_scatter2_kernel for the scheme).  Every
-// span with a valid index claims a slot of its bin's 8-record LDS stage; after
-// a barrier each wave writes the full stages of its 128 bins out, eight lanes
-// per stage, so a stage leaves as one aligned 64-B piece.  Indices already in
-// the overflow table are added there; a span whose stage is full in its round
-// is stored on its own (or moves to the overflow table when its index already
-// holds two of the stage's slots); a span whose region is used up goes to the
-// overflow table, past that to the row's spill cells by atomics.
-// u16 counters: a workgroup takes at most kBtMaxWgSpans (65,520) spans per
-// launch, which bounds its region claims per bin and every overflow-table
-// count.
-__global__ __launch_bounds__(kBtBlock) void dn_scatter_kernel(IngestParams P) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr uint32_t kWaves = kBtBlock / 64;
-  unsigned long long *stage = reinterpret_cast<unsigned long long *>(smem);          // [bins][8]
-  uint32_t *fillw = reinterpret_cast<uint32_t *>(stage + kPartBins * kDnStage);      // [bins / 2] u16 pairs
-  uint32_t *rcnw = fillw + kPartBins / 2;                                            // [bins / 2] region fills
-  uint16_t *flist = reinterpret_cast<uint16_t *>(rcnw + kPartBins / 2);              // [waves][128]
-  unsigned long long *hkey = reinterpret_cast<unsigned long long *>(flist + kWaves * 128);  // the entry's index
-  unsigned long long *hsum = hkey + kBt2Hot;
-  uint32_t *hcnt = reinterpret_cast<uint32_t *>(hsum + kBt2Hot);  // [kBt2Hot][kPartWords] u16 pairs
-  uint2 *hq = reinterpret_cast<uint2 *>(hcnt + kBt2Hot * kPartWords);
-  uint32_t *hq_n = reinterpret_cast<uint32_t *>(hq + kBtHq);
-  BinEntry *lbins = reinterpret_cast<BinEntry *>(hq_n + 4);
-  uint2 *herr = reinterpret_cast<uint2 *>(lbins + kBins);  // [kBt2HotErr] {(ws << 8 | entry) + 1, count}
-  uint8_t *llb = reinterpret_cast<uint8_t *>(herr + kBt2HotErr);
-  const KParams kp = kernel_params();
-
-  uint64_t lo, hi;
-  wg_range_p(P, lo, hi);
-  const uint32_t len = (uint32_t)(hi - lo);
-  constexpr uint32_t kRound = kBtBlock * 2;
-  const uint32_t lane = threadIdx.x & 63u, lane_off = lane * 2;
-  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const uint32_t rounds = (len + kRound - 1) / kRound;
-  auto tstart = [&](uint32_t r) -> uint32_t { return r * kRound + wave * 128; };
-  auto tremain = [&](uint32_t t) -> uint32_t { return len > t ? len - t : 0u; };
-
-  // prologue: bin table and bounds, the first two rounds' tiles, LDS setup
-  uint4 bv = make_uint4(0, 0, 0, 0);
-  if (threadIdx.x < kBins * 2) bv = reinterpret_cast<const uint4 *>(P.bintab)[threadIdx.x];
-  const uint32_t lb_on = P.lb_n != 0;
-  uint32_t lbw = 0;
-  if (lb_on && threadIdx.x * 4 < P.lb_n) lbw = *reinterpret_cast<const uint32_t *>(P.hll_lb + threadIdx.x * 4);
-  SpanTile<2> buf[2];
-  Pending<2> pend, pend2;  // HLL reads of the last two rounds (compared two rounds later)
-  load_tile_at<2, 2>(P, lo + tstart(0), tremain(tstart(0)), lane_off, buf[0]);
-  load_tile_at<2, 2>(P, lo + tstart(1), tremain(tstart(1)), lane_off, buf[1]);
-  {
-    uint32_t z;  // a VGPR zero keeps these vector loads
-    asm volatile("v_mov_b32 %0, 0" : "=v"(z));
-#pragma unroll
-    for (int j = 0; j < 2; ++j) pend.hv[j] = pend2.hv[j] = *reinterpret_cast<const uint32_t *>(P.hll + z);
+// The scatter's Path (sa_bt_scatter.h) for series given by dense index.  The
+// id is the index itself (0 has no record; one at or past the table's
+// capacity is counted as dropped and has none either -- its HLL register is
+// still raised, as a key-0 span's); a record is the 8 B of dn_rec, in
+// 8-record stages.  A span past the overflow table adds straight into its
+// row's spill cells, and the epilogue needs no lookup: an entry's row is
+// dn_row of its index.
+struct BtDense {
+  typedef uint32_t Id;
+  typedef unsigned long long Rec;
+  static constexpr uint32_t kStage = kDnStage;
+  static constexpr uint64_t kDurMask = kDnDurMask;
+  static constexpr uint32_t kBinLsb = 0;
+  static constexpr bool kStamps = false, kLookup = false, kClampDrain = true;
+  static_assert(kPartBinBits == 11, "the record's slot field and rec_id take 11-bit in-bin slots");
+  static __device__ __forceinline__ Id id(const IngestParams &, uint64_t key, uint32_t &n_drop, uint64_t cap) {
+    const bool big = key >= cap;
+    n_drop += big ? 1u : 0u;
+    return big ? 0u : (uint32_t)key;
   }
-  for (uint32_t b = threadIdx.x; b < kPartBins / 2; b += kBtBlock) fillw[b] = rcnw[b] = 0;
-  for (uint32_t h = threadIdx.x; h < kBt2Hot; h += kBtBlock) hkey[h] = hsum[h] = 0;
-  for (uint32_t h = threadIdx.x; h < kBt2Hot * kPartWords; h += kBtBlock) hcnt[h] = 0;
-  if (threadIdx.x < kBt2HotErr) herr[threadIdx.x] = make_uint2(0, 0);
-  if (threadIdx.x < kBins * 2) reinterpret_cast<uint4 *>(lbins)[threadIdx.x] = bv;
-  if (lb_on && threadIdx.x * 4 < P.lb_n) reinterpret_cast<uint32_t *>(llb)[threadIdx.x] = lbw;
-  if (threadIdx.x == 0) hq_n[0] = 0;
-  __syncthreads();
-
-  uint32_t n_zero = 0, n_badsvc = 0, n_oor = 0;  // wave-uniform (SGPR)
-  uint32_t n_drop = 0;                           // per lane: indices at or past the table's capacity
-  uint32_t n_filt = 0;                           // per lane: HLL updates the lower-bound filter skipped
-#pragma unroll
-  for (int j = 0; j < 2; ++j) pend.hoff[j] = pend.rho[j] = pend2.hoff[j] = pend2.rho[j] = 0;
-  const uint32_t region = P.bt_region, log2sb = P.log2sb;
-  unsigned long long *my_rec = reinterpret_cast<unsigned long long *>(P.bt_rec) + (uint64_t)blockIdx.x * region;
-  const uint64_t bin_stride = (uint64_t)P.bt_grid * region;  // + bin * grid * region
-  const uint64_t cap = 1ULL << P.log2cap;
-
-  // overflow-table home: an even entry, probed as a pair first
-  auto hot_home = [&](uint32_t idx) -> uint32_t {
-    return (uint32_t)(((uint64_t)(idx * 0x9E3779B1u) * (kBt2Hot / 2)) >> 32) * 2;
-  };
-  auto hot_acc = [&](uint32_t h, uint32_t idx, uint64_t d, bool err, uint32_t ws) {
-    const uint32_t bk = bucket_lds<1>(d, lbins, P);
-    atomicAdd(&hcnt[h * kPartWords + (bk >> 1)], 1u << ((bk & 1u) * 16));
-    atomicAdd(&hsum[h], (unsigned long long)d);
-    if (err) {  // ERROR count per (window slot, entry); a full table adds to errcnt directly
-      const uint32_t ek = ((ws << 8) | h) + 1;
-      uint32_t e = (ek * 0x9E3779B1u) >> 25;  // kBt2HotErr = 128
-      for (int pr = 0; pr < 4; ++pr, e = (e + 1) & (kBt2HotErr - 1)) {
-        uint32_t k = herr[e].x;
-        if (k == 0) k = atomicCAS(&herr[e].x, 0u, ek);
-        if (k == 0 || k == ek) {
-          atomicAdd(&herr[e].y, 1u);
-          return;
-        }
-      }
-      dn_cold_err(kp, dn_row(idx, log2sb), ws);
-    }
-  };
-  // the overflow table: false when the index is not in it and its 8 probes
-  // are taken
-  auto hot_try = [&](uint32_t idx, uint64_t d, bool err, uint32_t ws) -> bool {
-    uint32_t h = hot_home(idx);
-    for (int pr = 0; pr < 8; ++pr) {
-      unsigned long long k = hkey[h];
-      if (k == 0) k = atomicCAS(&hkey[h], 0ULL, (unsigned long long)idx);
-      if (k == 0 || k == idx) {
-        hot_acc(h, idx, d, err, ws);
-        return true;
-      }
-      h = h + 1 == kBt2Hot ? 0u : h + 1;
-    }
-    return false;
-  };
-  // a span its region cannot take: the overflow table, else its row's spill cells
-  auto hot_add = [&](uint32_t idx, uint64_t d, bool err, uint32_t ws) {
-    if (hot_try(idx, d, err, ws)) return;
-    dn_cold_direct(kp, dn_row(idx, log2sb), d, bucket_lds<1>(d, lbins, P), err, ws);
-  };
-  auto hot_rec = [&](uint32_t b, unsigned long long r) {
-    const uint32_t idx = ((uint32_t)(r >> kDnSlotShift) & (kPartBins - 1)) << kPartBinBits | b;
-    hot_add(idx, r & kDnDurMask, (r >> 63) != 0, (uint32_t)(r >> kDnWsShift) & 1023u);
-  };
-  // claims n record positions of bin b's region (u16 pairs); positions at or
-  // past the region's end take the overflow table instead
-  auto claim = [&](uint32_t b, uint32_t n) -> uint32_t {
-    const uint32_t sh = (b & 1u) * 16;
-    return (atomicAdd(&rcnw[b >> 1], n << sh) >> sh) & 0xFFFFu;
-  };
-  static_assert(kPartBinBits == 11, "the record's slot field and hot_rec take 11-bit in-bin slots");
-  auto place = [&](uint32_t idx, uint64_t d, bool err, uint32_t ws) {
-    const uint32_t h0 = hot_home(idx);
-    const ulonglong2 hk = *reinterpret_cast<const ulonglong2 *>(hkey + h0);
-    if (hk.x == idx || hk.y == idx) {
-      hot_acc(h0 + (hk.x == idx ? 0u : 1u), idx, d, err, ws);
-      return;
-    }
-    const uint32_t bk = bucket_lds<1>(d, lbins, P);
-    if (__builtin_expect(d > kDnDurMask, 0)) {  // beyond the record's duration bits
-      dn_cold_direct(kp, dn_row(idx, log2sb), d, bk, err, ws);
-      return;
-    }
-    const uint32_t b = idx & (kPartBins - 1), sh = (b & 1u) * 16;
-    const uint32_t c = (atomicAdd(&fillw[b >> 1], 1u << sh) >> sh) & 0xFFFFu;
-    const unsigned long long rec = dn_rec(idx >> kPartBinBits, d, bk, err, ws);
-    if (c < kDnStage) {
-      stage[b * kDnStage + c] = rec;
-      return;
-    }
-    // the stage is full this round: an index that holds two or more of its
-    // slots is frequent and moves to the overflow table; any other record is
-    // stored on its own.  (The slots may hold an earlier round's records:
-    // records of this bin either way.)
-    uint32_t same = 0;
-#pragma unroll
-    for (uint32_t q = 0; q < kDnStage; ++q)
-      same += (((stage[b * kDnStage + q] ^ rec) >> kDnSlotShift) & (kPartBins - 1)) == 0 ? 1u : 0u;
-    if (same >= 2 && hot_try(idx, d, err, ws)) return;
-    const uint32_t at = claim(b, 1);
-    if (at < region) my_rec[b * bin_stride + at] = rec;
-    else hot_add(idx, d, err, ws);
-  };
-  auto hll_settle = [&](const Pending<2> &q) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      if (((q.hv[j] >> ((q.hoff[j] & 3u) * 8)) & 0xFFu) < q.rho[j]) {
-        const uint32_t slot = atomicAdd(&hq_n[0], 1u);
-        if (slot < kBtHq) hq[slot] = make_uint2(q.hoff[j], q.rho[j]);
-        else hll_raise(kp->hll + q.hoff[j], q.rho[j]);
-      }
-    }
-  };
-
-  const uint32_t hp = P.p, lbs = P.lb_shift;
-  auto step = [&](SpanTile<2> &T, uint32_t toff, uint32_t pf) {
-    uint64_t d[2];
-    uint32_t idx[2], ws[2], hoff[2], rho[2];
-    bool err[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const bool valid = lane_off + toff + (uint32_t)j < len;
-      const uint64_t key = copy_u64(T.key[j]);  // 0 past the range
-      n_zero += wave_count(valid && key == 0);
-      // an index at or past the table's capacity: counted dropped, no record
-      // (its HLL register is still raised below, as a key-0 span's)
-      const bool big = key >= cap;
-      n_drop += big ? 1u : 0u;
-      idx[j] = big ? 0u : (uint32_t)key;
-      d[j] = T.e[j] > T.s[j] ? T.e[j] - T.s[j] : 0;
-      const uint32_t meta = copy_u32(T.meta[j]);
-      const uint32_t svc = meta & 0xFFFFu;
-      const bool svc_ok = svc < P.n_services;
-      ws[j] = window_slot_lean(P, T.e[j]);
-      const bool win_ok = ws[j] != 0xFFFFFFFFu;
-      n_badsvc += wave_count(valid && !svc_ok);
-      n_oor += wave_count(valid && svc_ok && !win_ok);
-      const bool sk = valid && svc_ok && win_ok;
-      err[j] = sk && ((meta >> 19) & 3u) == 2u;
-      const H64 x = xxh64_16_h(T.a[j], T.b[j]);
-      const uint32_t yh = __builtin_amdgcn_alignbit(x.hi, x.lo, 32 - hp), yl = (x.lo << hp) | (1u << (hp - 1));
-      const uint32_t r = (uint32_t)__clzll((long long)(((uint64_t)yh << 32) | yl)) + 1;
-      uint32_t row;
-      asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(row) : "v"(ws[j]), "s"(P.n_services), "v"(svc));
-      const uint32_t ho = sk ? (row << hp) + (x.hi >> (32 - hp)) : 0u;
-      bool up = sk;
-      if (lb_on) {
-        const bool f = r <= llb[ho >> lbs];
-        n_filt += (up && f) ? 1u : 0u;
-        up = up && !f;
-      }
-      rho[j] = up ? r : 0u;
-      hoff[j] = up ? ho : 0u;
-    }
-    uint32_t hv[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) hv[j] = *reinterpret_cast<const uint32_t *>(P.hll + (hoff[j] & ~3u));
-    __builtin_amdgcn_sched_barrier(0);
-    load_tile_at<2, 2>(P, lo + pf, tremain(pf), lane_off, T);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-      if (idx[j] != 0) place(idx[j], d[j], err[j], ws[j]);
-    hll_settle(pend2);
-    pend2 = pend;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      pend.hoff[j] = hoff[j];
-      pend.rho[j] = rho[j];
-      pend.hv[j] = hv[j];
-    }
-  };
-  // the waves write out the full stages of their 128 bins (8 lanes a stage)
-  uint16_t *wl = flist + wave * 128;
-  auto flush = [&]() {
-    const uint32_t fw = fillw[threadIdx.x];  // bins 2t, 2t + 1
-    const bool f0 = (fw & 0xFFFFu) >= kDnStage, f1 = (fw >> 16) >= kDnStage;
-    if (f0 || f1) fillw[threadIdx.x] = (f0 ? 0u : (fw & 0xFFFFu)) | (f1 ? 0u : (fw & 0xFFFF0000u));
-    const uint64_t m0 = __ballot(f0), m1 = __ballot(f1);
-    const uint32_t n0 = (uint32_t)__popcll(m0), nf = n0 + (uint32_t)__popcll(m1);
-    if (f0) wl[lane_rank(m0)] = (uint16_t)(2 * threadIdx.x);
-    if (f1) wl[n0 + lane_rank(m1)] = (uint16_t)(2 * threadIdx.x + 1);
-    compiler_fence();  // one wave's LDS operations complete in order
-    for (uint32_t i0 = 0; i0 < nf; i0 += 64 / kDnStage) {  // wave-uniform
-      const uint32_t i = i0 + lane / kDnStage, q = lane & (kDnStage - 1);
-      const bool act = i < nf;
-      const uint32_t b = act ? wl[i] : 0u;
-      const unsigned long long r = stage[b * kDnStage + q];
-      uint32_t at = act && q == 0 ? claim(b, kDnStage) : 0u;
-      at = (uint32_t)__shfl((int)at, (int)(lane & ~(kDnStage - 1)), 64);
-      if (act) {
-        if (at + q < region) my_rec[b * bin_stride + at + q] = r;
-        else hot_rec(b, r);
-      }
-    }
-  };
-
-  // Stage flushes: after every round, or -- once the first two rounds have
-  // put 32 or more indices in the overflow table (a skewed mix, whose hot
-  // indices bypass the stages) -- after every second round.
-  bool sparse = false;  // workgroup-uniform: read from LDS after a barrier
-  for (uint32_t r = 0; r < rounds; r += 2) {
-    step(buf[0], tstart(r), tstart(r + 2));
-    if (!sparse) {
-      __syncthreads();
-      flush();
-      __syncthreads();
-    }
-    if (r + 1 < rounds) step(buf[1], tstart(r + 1), tstart(r + 3));
-    __syncthreads();
-    flush();
-    if (r == 0 && wave == 0) {
-      uint32_t used = 0;
-      for (uint32_t h = lane; h < kBt2Hot; h += 64) used += wave_count(hkey[h] != 0);
-      if (lane == 0) hq_n[2] = used >= 32 ? 1u : 0u;
-    }
-    __syncthreads();
-    if (r == 0) sparse = hq_n[2] != 0;
+  static __device__ __forceinline__ uint32_t home_hash(Id idx) { return idx * 0x9E3779B1u; }
+  static __device__ __forceinline__ uint32_t row(const IngestParams &P, Id idx) { return dn_row(idx, P.log2sb); }
+  static __device__ __forceinline__ Rec rec(Id idx, uint64_t d, uint32_t bk, bool err, uint32_t ws) {
+    return dn_rec(idx >> kPartBinBits, d, bk, err, ws);
   }
-  hll_settle(pend2);
-  hll_settle(pend);
-  uint4 lbv[4];
-  hll_lb_pre<kBtBlock>(P, lbv);
-  // partial stages, then this workgroup's region fills
-  for (uint32_t b = threadIdx.x; b < kPartBins; b += kBtBlock) {
-    const uint32_t c = min((fillw[b >> 1] >> ((b & 1u) * 16)) & 0xFFFFu, kDnStage);  // < kDnStage after a flush
-    const uint32_t at = c ? claim(b, c) : 0u;
-    for (uint32_t q = 0; q < c; ++q) {
-      if (at + q < region) my_rec[b * bin_stride + at + q] = stage[b * kDnStage + q];
-      else hot_rec(b, stage[b * kDnStage + q]);
-    }
+  static __device__ __forceinline__ Id rec_id(uint32_t b, Rec r) {
+    return ((uint32_t)(r >> kDnSlotShift) & (kPartBins - 1)) << kPartBinBits | b;
   }
-  __syncthreads();
-  // the queued HLL raises' register words, read now and CAS-raised at the end
-  const uint32_t nq = min(hq_n[0], kBtHq);
-  constexpr uint32_t kQ = (kBtHq + kBtBlock - 1) / kBtBlock;
-  uint32_t qv[kQ];
-#pragma unroll
-  for (uint32_t i = 0; i < kQ; ++i) {
-    const uint32_t t = threadIdx.x + i * kBtBlock;
-    qv[i] = t < nq ? __hip_atomic_load(reinterpret_cast<const uint32_t *>(P.hll + (hq[t].x & ~3u)), __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT)
-                   : 0u;
+  static __device__ __forceinline__ uint64_t rec_d(Rec r) { return r & kDnDurMask; }
+  static __device__ __forceinline__ bool rec_err(Rec r) { return (r >> 63) != 0; }
+  static __device__ __forceinline__ uint32_t rec_ws(Rec r) { return (uint32_t)(r >> kDnWsShift) & 1023u; }
+  static __device__ __forceinline__ bool same_id(Rec a, Rec b) {
+    return (((a ^ b) >> kDnSlotShift) & (kPartBins - 1)) == 0;
   }
-  for (uint32_t b = threadIdx.x; b < kPartBins; b += kBtBlock)
-    P.bt_cnt[(uint64_t)b * P.bt_grid + blockIdx.x] = min((rcnw[b >> 1] >> ((b & 1u) * 16)) & 0xFFFFu, region);
-  // the overflow table: each entry's counts and ns sum added to its row's
-  // spill cells (atomics: the entries of one index come from every
-  // workgroup), two entries per wave instruction and one cell per lane
-  {
-    const uint32_t half = lane >> 5, cell = lane & 31u, nc = P.nbk + 1;
-    static_assert(kBt2Hot % 2 == 0 && kPartMaxBk + 1 <= 32, "overflow flush geometry");
-    for (uint32_t h0 = wave * 2; h0 < kBt2Hot; h0 += kWaves * 2) {
-      const uint32_t h = h0 + half;
-      const uint32_t idx = (uint32_t)hkey[h];
-      if (idx == 0 || cell >= nc) continue;
-      const unsigned long long v = cell == P.nbk ? hsum[h]
-                                                 : (hcnt[h * kPartWords + (cell >> 1)] >> ((cell & 1u) * 16)) & 0xFFFFu;
-      if (v) atomicAdd(P.base64 + (uint64_t)dn_row(idx, log2sb) * nc + cell, v);
-    }
+  // the cold paths take the row
+  static __device__ __forceinline__ uint32_t cold_key(const IngestParams &P, Id idx) { return row(P, idx); }
+  static __device__ __forceinline__ uint32_t cold_direct(KParams kp, uint32_t row, uint64_t d, uint32_t bk, bool err,
+                                                         uint32_t ws) {
+    dn_cold_direct(kp, row, d, bk, err, ws);
+    return 0u;  // never dropped
   }
-  if (threadIdx.x < kBt2HotErr) {
-    const uint2 e = herr[threadIdx.x];
-    if (e.x) {
-      const uint32_t ws = (e.x - 1) >> 8, h = (e.x - 1) & 0xFFu;
-      const uint32_t idx = (uint32_t)hkey[h];
-      atomicAdd(P.errcnt + ((uint64_t)ws << P.log2cap) + dn_row(idx, log2sb), (unsigned long long)e.y);
-    }
-  }
-#pragma unroll
-  for (uint32_t i = 0; i < kQ; ++i) {
-    const uint32_t t = threadIdx.x + i * kBtBlock;
-    if (t >= nq) continue;
-    const uint2 q = hq[t];
-    SA_GLOBAL uint32_t *word = gbl(reinterpret_cast<uint32_t *>(P.hll + (q.x & ~3u)));
-    const uint32_t sh = (q.x & 3u) * 8;
-    uint32_t old = qv[i];
-    while (((old >> sh) & 0xFFu) < q.y) {  // a failed CAS refreshes `old`
-      const uint32_t nw = (old & ~(0xFFu << sh)) | (q.y << sh);
-      if (__hip_atomic_compare_exchange_strong(word, &old, nw, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                               __HIP_MEMORY_SCOPE_AGENT))
-        break;
-    }
-  }
-  n_drop = wave_sum(n_drop);
-  n_filt = wave_sum(n_filt);
-  if (lane == 0) {
-    if (n_filt) atomicAdd(&P.hll_filt[blockIdx.x & (kFiltSlots - 1)], (unsigned long long)n_filt);
-    if (n_zero) atomicAdd(&P.stats[kStatZeroKey], (unsigned long long)n_zero);
-    if (n_badsvc) atomicAdd(&P.stats[kStatInvalidService], (unsigned long long)n_badsvc);
-    if (n_oor) atomicAdd(&P.stats[kStatWindowOOR], (unsigned long long)n_oor);
-    if (n_drop) atomicAdd(&P.stats[kStatDropped], (unsigned long long)n_drop);
-  }
-  hll_lb_finish<kBtBlock>(P, lbv);
-}
+  static __device__ __forceinline__ void cold_err(KParams kp, uint32_t row, uint32_t ws) { dn_cold_err(kp, row, ws); }
+};
 
 // Aggregate.  One 512-thread workgroup per bin; its LDS holds, per in-bin
 // slot, the u64 ns sum and 17 packed u16 bucket counts, then the ERROR list
@@ -581,7 +265,7 @@ __global__ void dn_bind_kernel(unsigned long long *gkeys, const uint64_t *index,
 size_t dn_agg_lds_bytes(uint32_t log2sb, uint32_t grid) { return dn_off_reg(1u << log2sb) + (size_t)grid * 4 + 16; }
 
 hipError_t prepare_ingest_dn(size_t agg_lds) {
-  if (hipError_t e = hipFuncSetAttribute((const void *)&dn_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+  if (hipError_t e = hipFuncSetAttribute((const void *)&bt_scatter2_kernel<BtDense, 0>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                          (int)kBt2ScatterLds);
       e != hipSuccess)
     return e;
@@ -591,7 +275,7 @@ hipError_t prepare_ingest_dn(size_t agg_lds) {
 
 hipError_t launch_dn_scatter(const IngestParams &P, hipStream_t s) {
   void *args[] = {const_cast<IngestParams *>(&P)};
-  return hipLaunchKernel((const void *)&dn_scatter_kernel, dim3(P.bt_grid), dim3(kBtBlock), args, kBt2ScatterLds, s);
+  return hipLaunchKernel((const void *)&bt_scatter2_kernel<BtDense, 0>, dim3(P.bt_grid), dim3(kBtBlock), args, kBt2ScatterLds, s);
 }
 
 hipError_t launch_dn_aggregate(const IngestParams &P, hipStream_t s) {

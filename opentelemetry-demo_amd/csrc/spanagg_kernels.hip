@@ -108,14 +108,7 @@ __device__ __forceinline__ void epi_raise_and_bound(const PT &P, const uint2 *hq
     if (tid + i * B >= nq) continue;
     const uint2 q = hq[tid + i * B];
     SA_GLOBAL uint32_t *word = gbl(reinterpret_cast<uint32_t *>(P.hll + (q.x & ~3u)));
-    const uint32_t sh = (q.x & 3u) * 8;
-    uint32_t old = hqv[tid + i * B];
-    while (((old >> sh) & 0xFFu) < q.y) {  // a failed CAS refreshes `old`
-      const uint32_t nw = (old & ~(0xFFu << sh)) | (q.y << sh);
-      if (__hip_atomic_compare_exchange_strong(word, &old, nw, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                               __HIP_MEMORY_SCOPE_AGENT))
-        break;
-    }
+    hll_raise_from(word, hqv[tid + i * B], (q.x & 3u) * 8, q.y);
   }
   hll_lb_finish<B>(P, lv);
 }

@@ -1,6 +1,8 @@
 """GPU parity of dense-index engines (SA_OPT_DENSE_IDS, spanagg_dense.hip:
-dn_scatter_kernel + dn_aggregate_kernel, sa_bind_ids) against the CPU oracle
-fed the real series hashes.
+bt_scatter2_kernel<BtDense> + dn_aggregate_kernel, sa_bind_ids) against the
+CPU oracle fed the real series hashes.  The scatter's launch-size and
+record-limit edges run on a default (hashed) engine of the same table too: one
+kernel template serves both.
 
 Bar: parity_util.assert_red_equal (bucket counts, calls and ns sums bit-exact,
 sums within 1e-9 relative); HLL registers and count-min cells np.array_equal
@@ -31,11 +33,18 @@ def _oracle(*batches):
     return o
 
 
-def _dense(kcap=300_000, n_windows=16):
-    e = Engine(Config(n_services=1, n_windows=n_windows, key_capacity=kcap, options=OPT_DENSE_IDS))
+def _engine(options, kcap=300_000, n_windows=16):
+    e = Engine(Config(n_services=1, n_windows=n_windows, key_capacity=kcap, options=options))
     st = e.stats()
     assert st["small_table"] == 0 and st["n_keys"] == 0
     return e
+
+
+def _dense(kcap=300_000, n_windows=16):
+    return _engine(OPT_DENSE_IDS, kcap, n_windows)
+
+
+BOTH = pytest.mark.parametrize("options", [0, OPT_DENSE_IDS], ids=["hashed", "dense"])
 
 
 def _with_keys(batch, keys):
@@ -129,14 +138,11 @@ def test_one_hot_series_twice_before_flush():
         assert int(res.calls.max()) > 2 * 0.69 * n
 
 
-def test_duration_edges():
-    """Durations 0, end < start, each default threshold and +-1 ns, and the
-    record's limits (2^37 - 1 in the record, 2^37 and longer by the cold
-    path: 2^42, 2^59, 2^63 ns), ERROR spans among them, over 50 series.  A
-    series' ns sum is a u64 everywhere (engine, oracle, result): the 2^63-ns
-    spans go to three series, one each, so no sum wraps."""
+@functools.lru_cache(maxsize=None)
+def _edge_batch():
     thr, _ = bucket_thresholds(Config().bounds)
-    edges = [0] + [int(t) + k for t in thr for k in (-1, 0, 1)] + [2**37 - 1, 2**37, 2**42, 2**59]
+    edges = ([0] + [int(t) + k for t in thr for k in (-1, 0, 1)] +
+             [2**37 - 1, 2**37, 2**42, 2**59 - 1, 2**59])
     n = 4000
     base, w0, _ = _workload(0.0)
     base = base.slice(0, n)
@@ -159,7 +165,20 @@ def test_duration_edges():
     o = _oracle(batch)
     ref = o.series()
     assert np.allclose(ref["sum_ns"].astype(np.float64) / 1e6, ref["sum_go"], rtol=1e-9)  # (no u64 sum wrapped)
-    with _dense() as e:
+    return batch, w0, o, long
+
+
+@BOTH
+def test_duration_edges(options):
+    """Durations 0, end < start, each default threshold and +-1 ns, and the
+    records' limits: 2^37 - 1 stays in a dense record, 2^37 and longer take
+    its cold path; 2^59 - 1 stays in a hashed record, 2^59 takes its cold
+    path; also 2^42 and 2^63 ns.  ERROR spans among them, over 50 series.  A
+    series' ns sum is a u64 everywhere (engine, oracle, result): the 2^63-ns
+    spans go to three series, one each, so no sum wraps."""
+    batch, w0, o, long = _edge_batch()
+    n = len(batch)
+    with _engine(options) as e:
         e.window_advance(w0)
         e.ingest(batch)
         res = e.flush()
@@ -176,16 +195,19 @@ def test_duration_edges():
             assert np.array_equal(sk.hll, hll) and np.array_equal(sk.cms, cms), wid
 
 
+@BOTH
 @pytest.mark.parametrize("n", [1, 127, 4097, 8193])
-def test_ragged_launch_sizes(n):
+def test_ragged_launch_sizes(n, options):
     """One and two scatter workgroups, partial tiles and partial stages."""
     base, w0, _ = _workload(0.0)
     batch = base.slice(1000, 1000 + n)
-    with _dense() as e:
+    with _engine(options) as e:
         e.window_advance(w0)
-        ids, ni, nh = e.ids.encode(batch.key_hash)
-        e.bind_ids(ni, nh)
-        e.ingest_device(*_dev((ids,) + batch.columns()[1:]), n=n)
+        keys = batch.key_hash
+        if options & OPT_DENSE_IDS:
+            keys, ni, nh = e.ids.encode(batch.key_hash)
+            e.bind_ids(ni, nh)
+        e.ingest_device(*_dev((keys,) + batch.columns()[1:]), n=n)
         _check(e, _oracle(batch), n)
 
 
