@@ -247,7 +247,13 @@ int sa_ingest_device(sa_engine *e, const sa_span_batch *batch, void *stream);
  * the stream reaches the end of the k).  Small-table engines launch the k
  * ingests as one HIP graph, so consecutive launches carry no per-launch
  * dispatch gap; other engines (binned, exponential, laboratory options) and
- * batches that would need a split take the one-by-one path.  Replaces a loop
+ * batches that would need a split take the one-by-one path.  Unlike
+ * sa_ingest_device, the graph path can block the host: the engine keeps two
+ * instantiated graphs and, before it re-points one at new batches, waits
+ * (hipEventSynchronize) until that graph's previous launch -- the one of two
+ * graph calls earlier -- has finished on the device.  Do not call it while
+ * holding a lock that `stream`'s pending work needs, nor when `stream` waits
+ * on host work queued after this call.  Replaces a loop
  * of ConsumeTraces calls over the batches a receiver queued (the connector's
  * aggregateMetrics per request, connector.go [UPSTREAM]). */
 int sa_ingest_device_many(sa_engine *e, const sa_span_batch *batches, uint32_t k, void *stream);

@@ -6,9 +6,10 @@
 #include <cmath>
 #include <cstdint>
 
+#include "sa_path.h"  // constants the path decision shares: BinEntry, kBins, kLdsExtraBytes, ...
+
 namespace sa {
 
-constexpr int kMaxBounds = 62;          // SA_MAX_BOUNDS
 constexpr uint32_t kNotFound = 0xFFFFFFFFu;
 constexpr uint64_t kPhi = 0x9E3779B97F4A7C15ULL;  // Fibonacci hashing multiplier
 
@@ -23,15 +24,6 @@ enum : int {
 // HLL updates skipped by the lower-bound filter (sa_stats.hll_filtered): one
 // u64 slot per workgroup index (mod kFiltSlots), summed when stats are read
 constexpr uint32_t kFiltSlots = 1024;
-
-// Bucket lookup table: bin k = floor(log2 d) (k = 64 for d = 0).  For d in
-// bin k, bucket = base + [d > ta] + [d > tb] (ta/tb = UINT64_MAX when absent);
-// valid when no bin holds more than two thresholds.
-struct BinEntry {
-  unsigned long long ta, tb;
-  uint32_t base, pad[3];
-};
-constexpr int kBins = 65;
 
 struct XHdr;
 struct ExpoHdr;
@@ -250,22 +242,15 @@ __host__ __device__ inline uint32_t xc_slab_stride(uint32_t ne, uint32_t max_siz
 __host__ __device__ ExpoHdr expo_hdr_empty();
 constexpr uint32_t kExpoMaxSize = 4096;
 
-// HLL bound sub-blocks: 2^kLbMinShift registers or more, at most kLbMaxSub of
-// them per engine (the kernels keep the bounds in LDS)
 constexpr uint64_t kHostChunkSpans = 1ull << 20;  // sa_ingest pinned slot (44 MiB)
 constexpr uint64_t kHostPageableMin = 1ull << 18;  // chunks from here on: the runtime's pageable staging
-constexpr uint32_t kLbMinShift = 10;
-constexpr uint32_t kLbMaxSub = 2048;
 
 
 // Partitioned HBM-table path (high cardinality): part_scatter_kernel bins
 // every span's record by the top 11 bits of its key, part_aggregate_kernel
 // aggregates one bin per workgroup in an LDS table and adds it to the HBM
 // counters once per key.
-#ifndef SA_PART_BIN_BITS
-#define SA_PART_BIN_BITS 11
-#endif
-constexpr uint32_t kPartBinBits = SA_PART_BIN_BITS;
+// (kPartBinBits, kPartMaxBk: sa_path.h)
 constexpr uint32_t kPartBins = 1u << kPartBinBits;
 // LDS table slots per bin: ~2x the mean keys per bin at 1 M keys
 constexpr uint32_t kPartSlotBits = 21 - kPartBinBits;
@@ -275,7 +260,6 @@ constexpr uint32_t kPartSlots = 1u << kPartSlotBits;
 #define SA_PART_STAGE (SA_PART_BIN_BITS >= 11 ? 2 : 8)  // 2: LDS left for a 512-entry overflow table
 #endif
 constexpr uint32_t kPartStage = SA_PART_STAGE;
-constexpr uint32_t kPartMaxBk = 17;       // LDS counter row: nbk <= 17 (default buckets)
 constexpr uint32_t kPartBlock = 1024;     // scatter
 constexpr uint32_t kPartAggBlock = kPartSlots >= 2048 ? 1024 : 512;  // aggregate workgroup
 constexpr uint64_t kPartMaxSpans = 1ULL << 24;  // spans per partitioned launch
@@ -470,13 +454,7 @@ constexpr uint32_t kDbgPerWg = 136;  // diagnostic stamps per workgroup: 8 + 16 
 // the last slots of the wave rows
 constexpr uint32_t kXcStamp = 4, kXcStampSlab = kDbgPerWg - 1, kXcStampZeroed = kDbgPerWg - 9,
                    kXcStampSelected = kDbgPerWg - 17, kXcStampTail = kDbgPerWg - 25;
-constexpr uint32_t kHllQueue = 2048;  // deferred HLL raises per workgroup (8 B each)
-constexpr uint32_t kErrTab = 1024;    // LDS (window, slot) -> ERROR count table per workgroup (4 B each)
-// ingest_lds_kernel LDS beyond the table: HLL queue + its count + bin table
-// (+ the ERROR table and HLL bounds of the v2 kernels; their TAG forms add
-// cap u32 key tags, see kLdsTagBytes)
-// (+ 64 B: the POOL kernels' map of stolen pool blocks)
-constexpr size_t kLdsExtraBytes = kHllQueue * 8 + 32 + kBins * sizeof(BinEntry) + kErrTab * 4 + kLbMaxSub + 64;
+// (kHllQueue, kErrTab, kLdsExtraBytes: sa_path.h)
 constexpr size_t kLdsTagBytesPerSlot = 4;
 constexpr int kLdsTagVariant = 21;  // the only small-table variant with LDS key tags
 

@@ -78,6 +78,13 @@ struct red_holder {
   ~red_holder() {
     if (pin) pool->give(pin, pin_bytes);
   }
+  // the vector columns sized for n series of nbk buckets, and r pointing at them
+  __attribute__((visibility("hidden"))) void shape(uint64_t n, uint32_t nbk) {
+    keys.resize(n), counts.resize(n * nbk), calls.resize(n), sum_ns.resize(n), sum.resize(n);
+    r.n_series = n, r.n_buckets = nbk;
+    r.key_hash = keys.data(), r.bucket_counts = counts.data(), r.calls = calls.data();
+    r.sum_ns = sum_ns.data(), r.sum = sum.data();
+  }
 };
 
 struct exp_holder {
@@ -86,10 +93,24 @@ struct exp_holder {
   std::vector<double> sum, min, max;
   std::vector<int32_t> scale, offset;
   std::vector<uint32_t> nb;
+  // the columns sized for n series of at most max_size buckets (zeroed), and r pointing at them
+  __attribute__((visibility("hidden"))) void shape(uint64_t n, uint32_t max_size, uint32_t unit) {
+    keys.resize(n), count.resize(n), zero.resize(n), sum_ns.resize(n), sum.resize(n), min.resize(n), max.resize(n);
+    scale.resize(n), offset.resize(n), nb.resize(n), buckets.assign(n * max_size, 0);
+    r.n_series = n, r.max_size = max_size, r.unit = unit;
+    r.key_hash = keys.data(), r.count = count.data(), r.zero_count = zero.data(), r.sum_ns = sum_ns.data();
+    r.sum = sum.data(), r.min = min.data(), r.max = max.data(), r.scale = scale.data(), r.offset = offset.data();
+    r.n_buckets = nb.data(), r.bucket_counts = buckets.data();
+  }
 };
 
 struct sketch_holder {
   sa_sketch_result r;
   std::vector<uint8_t> hll;
   std::vector<uint32_t> cms;
+  // r: window window_id of an engine with config c, pointing at the (sized) vectors
+  __attribute__((visibility("hidden"))) void wire(uint64_t window_id, const sa_config &c) {
+    r.window_id = window_id, r.n_services = c.n_services, r.hll_p = c.hll_p, r.hll = hll.data();
+    r.cms_d = c.cms_d, r.cms_w = c.cms_w, r.cms = cms.data();
+  }
 };

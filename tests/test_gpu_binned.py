@@ -78,7 +78,7 @@ def test_binned_matches_partitioned_path(zipf):
 
 @pytest.mark.parametrize("zipf", [0.0, 1.2])
 def test_binned_pipeline_new_keys_every_launch(zipf):
-    """The launch pipeline (spanagg_engine.cpp sa_engine::bt_rec): launch k's
+    """The launch pipeline (sa_engine.h sa_engine::Binned): launch k's
     aggregate runs on the engine's stream beside launch k + 1's scatter.  Every
     launch brings a key set no launch had (the series ids XORed with a
     per-launch constant), so launch k's aggregate inserts its keys into the
