@@ -42,6 +42,43 @@ int sa_key_union_probe(sa_engine *e, const uint64_t *in, uint64_t n, uint64_t *o
  * otherwise). */
 int sa_debug_stamps(sa_engine *e, uint64_t *out, uint64_t cap, uint64_t *n_out);
 
+/* Which ingest kernel an engine runs (sa_debug_geometry_info.kernel).  Small
+ * tables: the kernel specialised for the default geometry (2,048 slots, 17
+ * buckets, HLL p = 14), the generic kernel with 512- or 1,024-thread
+ * workgroups, or the linear-threshold kernel for bounds no bin table holds.
+ * Small exponential tables: the kernel specialised for 2,048 slots and p = 14,
+ * or the generic one.  HBM tables (exponential, binned, dense, partitioned,
+ * atomic): the instance for 16 non-negative bounds or the generic one (the
+ * binned and dense scatters have a single instance; the value then only names
+ * the bounds).  SA_KERNEL_LAB: a laboratory variant (libspanagg_ab.so). */
+enum {
+  SA_KERNEL_SMALL_DEFAULT = 0,
+  SA_KERNEL_SMALL_512 = 1,
+  SA_KERNEL_SMALL_1024 = 2,
+  SA_KERNEL_SMALL_LINEAR = 3,
+  SA_KERNEL_EXPO_SPECIALISED = 4,
+  SA_KERNEL_EXPO_GENERIC = 5,
+  SA_KERNEL_BOUNDS16 = 6,
+  SA_KERNEL_BOUNDS_GENERIC = 7,
+  SA_KERNEL_LAB = 8
+};
+
+typedef struct sa_debug_geometry_info {
+  uint32_t path;        /* 0 Small, 1 ExpoSmall, 2 ExpoHbm, 3 Binned, 4 Dense, 5 Partitioned, 6 Atomic */
+  uint32_t kernel;      /* SA_KERNEL_* */
+  uint32_t block;       /* threads per ingest workgroup */
+  uint32_t grid_max;    /* G: the most workgroups one ingest launch uses */
+  uint32_t log2cap;     /* log2 of the key table's slots */
+  uint32_t lb_shift;    /* HLL lower-bound filter: sub-blocks of 2^lb_shift registers ... */
+  uint32_t lb_n;        /* ... lb_n of them; 0: the filter is off */
+  uint32_t error_table; /* 1: per-workgroup (window, slot) ERROR tables (small tables) */
+  uint64_t lds_bytes;   /* the ingest kernel's dynamic LDS (small tables) */
+} sa_debug_geometry_info;
+
+/* Diagnostic: the geometry decisions sa_create took for this engine, so a
+ * test can assert which device code it is about to run.  Host state only. */
+int sa_debug_geometry(sa_engine *e,sa_debug_geometry_info *out);
+
 #ifdef __cplusplus
 }
 #endif

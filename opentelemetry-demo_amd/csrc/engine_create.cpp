@@ -200,12 +200,17 @@ int sa_create(const sa_config *cfg, sa_engine **out) {
       e->variant = kDefaultVariant;
   }
   if (small) {
-    // a table other than the specialised default geometry whose LDS state
-    // fits a CU twice: 512-thread workgroups, two per CU, so one workgroup's
-    // prologue and write-back overlap the other's loop
-    if (e->variant == kDefaultVariant && h.has_bins && 2 * e->lds_bytes <= (size_t)160 * 1024 &&
-        !(e->log2cap == 11 && nw == 9 && cfg->hll_p == 14))
-      e->variant = sa::kLdsHalfBlockVariant;
+    // the product's kernel for the geometry (sa_path.h small_kernel); the
+    // laboratory build's other variants report SA_KERNEL_LAB
+    e->kernel_kind = SA_KERNEL_LAB;
+    if (e->variant == kDefaultVariant) {
+      const sa::SmallKernel k = sa::small_kernel(h.has_bins, e->lds_bytes, e->log2cap, h.nbk, cfg->hll_p);
+      if (k == sa::SmallKernel::Generic512) e->variant = sa::kLdsHalfBlockVariant;
+      e->kernel_kind = k == sa::SmallKernel::Default      ? SA_KERNEL_SMALL_DEFAULT
+                       : k == sa::SmallKernel::Generic512 ? SA_KERNEL_SMALL_512
+                       : k == sa::SmallKernel::Generic1024 ? SA_KERNEL_SMALL_1024
+                                                           : SA_KERNEL_SMALL_LINEAR;
+    }
     e->spl = (uint32_t)sa::kLdsSpl[e->variant];
     e->block = sa::ingest_small_block(h.has_bins, e->variant, e->log2cap, h.nbk, cfg->hll_p);
     if ((rc = lds_attr(sa::prepare_ingest_small(e->lds_bytes)))) return bail(rc);
@@ -217,6 +222,8 @@ int sa_create(const sa_config *cfg, sa_engine **out) {
       per_cu = std::max<uint32_t>(1, std::min<uint32_t>(2048 / e->block, (uint32_t)((160 * 1024) / e->lds_bytes)));
     e->G = e->cus * per_cu;
   } else if (expo_small) {
+    e->kernel_kind = sa::expo_kernel(e->log2cap, cfg->hll_p) == sa::ExpoKernel::Specialised ? SA_KERNEL_EXPO_SPECIALISED
+                                                                                            : SA_KERNEL_EXPO_GENERIC;
     e->block = 1024;
     e->spl = 2;
     if ((rc = lds_attr(sa::prepare_ingest_expo_small(e->lds_bytes)))) return bail(rc);
@@ -233,6 +240,8 @@ int sa_create(const sa_config *cfg, sa_engine **out) {
         (rc = lds_attr(sa::prepare_expo_slab(sa::expo_slab_lds_bytes(e->cap, cfg->exp_max_size, e->expo.xc_ne)))))
       return bail(rc);
   } else {
+    // (the binned and dense scatters have one instance: the value names the bounds they run with)
+    e->kernel_kind = sa::bounds16(h.nneg, h.npos) ? SA_KERNEL_BOUNDS16 : SA_KERNEL_BOUNDS_GENERIC;
     e->block = sa::kHbmBlock;
     e->spl = (uint32_t)sa::kVariants[e->variant].spl;
     e->G = e->cus * 8;
@@ -256,12 +265,10 @@ int sa_create(const sa_config *cfg, sa_engine **out) {
   {
     // bound sub-blocks: as small as kLbMinShift allows within kLbMaxSub of them
     // (SA_OPT_NO_HLL_FILTER turns the filter off)
-    const uint64_t regs = W * S << cfg->hll_p;
-    uint32_t sh = sa::kLbMinShift;
-    while (sh < cfg->hll_p && (regs >> sh) > sa::kLbMaxSub) ++sh;
-    if ((regs >> sh) <= sa::kLbMaxSub && sh <= cfg->hll_p && !(cfg->options & SA_OPT_NO_HLL_FILTER)) {
-      e->lb_shift = sh;
-      e->lb_n = (uint32_t)(regs >> sh);
+    const sa::LbGeom lb = sa::hll_filter_geometry(*cfg);
+    if (lb.n) {
+      e->lb_shift = lb.shift;
+      e->lb_n = lb.n;
       if ((rc = dalloc(e, e->hll_lb, ((size_t)e->lb_n + 15) & ~(size_t)15, true))) return bail(rc);
     }
   }
@@ -299,7 +306,7 @@ int sa_create(const sa_config *cfg, sa_engine **out) {
                       hipMemset(x.xc_ent, 0xFF, (size_t)e->cap * 8) != hipSuccess))
         return bail(fail(e, SA_EDEVICE, "hipMemset failed"));
       // (window, slot) keys of the LDS ERROR table are 16-bit
-      if ((uint64_t)cfg->n_windows * e->cap < 65535 &&
+      if (sa::error_table(cfg->n_windows, e->cap) &&
           (rc = dalloc(e, e->small.errslab, gs * cfg->n_windows * e->cap, true)))
         return bail(rc);
     }
@@ -351,7 +358,7 @@ int sa_create(const sa_config *cfg, sa_engine **out) {
     if ((rc = dalloc(e, s.slab_cnt, gs * e->cap * srow, true)) || (rc = dalloc(e, s.slab_sum, gs * e->cap, true)))
       return bail(rc);
     // (window, slot) keys of the v2 kernels' LDS ERROR table are 16-bit
-    if (e->small_v2() && (uint64_t)cfg->n_windows * e->cap < 65535 &&
+    if (e->small_v2() && sa::error_table(cfg->n_windows, e->cap) &&
         (rc = dalloc(e, s.errslab, gs * cfg->n_windows * e->cap, true)))
       return bail(rc);
     // the tail pool: only the specialised default geometry has a POOL kernel
@@ -381,5 +388,22 @@ void sa_destroy(sa_engine *e) {
 }
 
 const char *sa_last_error(const sa_engine *e) { return e ? e->err.c_str() : "null engine"; }
+
+int sa_debug_geometry(sa_engine *e, sa_debug_geometry_info *out) {
+  if (!e || !out) return SA_EINVAL;
+  std::memset(out, 0, sizeof *out);
+  out->path = (uint32_t)e->path;
+  out->kernel = (uint32_t)e->kernel_kind;
+  // (the binned, dense and partitioned scatters have blocks and grids of their own)
+  const bool part = e->path == Path::Partitioned;
+  out->block = sa::binned_like(e->path) ? sa::kBtBlock : part ? sa::kPartBlock : e->block;
+  out->grid_max = sa::binned_like(e->path) ? e->binned.grid : part ? sa::kPartMaxGrid : e->G;
+  out->log2cap = e->log2cap;
+  out->lb_shift = e->lb_shift;
+  out->lb_n = e->lb_n;
+  out->error_table = e->small.errslab != nullptr;
+  out->lds_bytes = sa::lds_table(e->path) ? e->lds_bytes : 0;
+  return SA_OK;
+}
 
 }  // extern "C"

@@ -36,6 +36,15 @@ __device__ __forceinline__ void bt_stamp(const IngestParams &P, uint64_t base, u
   if (P.dbg && threadIdx.x == 0) P.dbg[base + k] = __builtin_amdgcn_s_memrealtime();
 }
 
+// Count-min cells of one ERROR span whose key column is 0 (d atomics; cold).
+__device__ __noinline__ void bt_err_no_series(KParams Q, uint32_t ws) {
+  SA_GLOBAL unsigned long long *row0 = gbl(Q->cms) + (uint64_t)ws * Q->cms_d * Q->cms_w;
+  for (uint32_t r = 0; r < Q->cms_d; ++r) {
+    const uint64_t col = splitmix64(Q->seeds[r]) >> Q->cms_shift;  // (key 0 ^ seed)
+    __hip_atomic_fetch_add(row0 + (uint64_t)r * Q->cms_w + col, 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
 // Round-synchronous scatter.  The workgroup takes its span range in rounds of
 // 2,048 spans (one 128-span tile per wave, two rounds of tiles in flight);
 // every span claims a slot of its bin's kStage-record LDS stage with one LDS
@@ -245,6 +254,9 @@ __global__ __launch_bounds__(kBtBlock) void bt_scatter2_kernel(IngestParams P) {
       n_oor += wave_count(valid && svc_ok && !win_ok);
       const bool sk = valid && svc_ok && win_ok;
       err[j] = sk && ((meta >> 19) & 3u) == 2u;
+      // an ERROR span of no series (key 0) has no record: its count-min cells
+      // here, as on every other path (key 0's cells)
+      if (err[j] && key == 0) bt_err_no_series(kp, ws[j]);
       id[j] = Path::id(P, key, n_drop, cap);  // (here: earlier or later in this body moves the hashed instance's code)
       // the span hash on 32-bit halves, rho without 64-bit shifts, the
       // register row by a 24-bit multiply-add (as the lean C2 kernel)

@@ -86,6 +86,7 @@ struct sa_engine {
   uint32_t log2cap = 0;
   uint64_t cap = 0;
   int variant = 0;
+  int kernel_kind = 0;  // SA_KERNEL_* (spanagg_diag.h): what sa_debug_geometry reports
   uint32_t spl = 4;
   uint32_t G = 0, block = 0, cus = 0;
   size_t lds_bytes = 0;

@@ -261,6 +261,7 @@ constexpr uint32_t kPartSlots = 1u << kPartSlotBits;
 #endif
 constexpr uint32_t kPartStage = SA_PART_STAGE;
 constexpr uint32_t kPartBlock = 1024;     // scatter
+constexpr uint32_t kPartMaxGrid = 256;    // scatter workgroups per launch, at most
 constexpr uint32_t kPartAggBlock = kPartSlots >= 2048 ? 1024 : 512;  // aggregate workgroup
 constexpr uint64_t kPartMaxSpans = 1ULL << 24;  // spans per partitioned launch
 // records per bin: 1.25x the mean plus slack (a fuller bin spills to the direct path)

@@ -175,5 +175,56 @@ inline PathChoice decide_path(const sa_config &c, const Hist &h, uint64_t cap) {
   return {binned ? Path::Binned : Path::Partitioned, lds};
 }
 
+// The geometry the specialised small-table kernels are compiled for: 2,048
+// slots, 17 or 18 buckets (9 u16-pair counter words per slot), HLL p = 14.
+constexpr bool default_geometry(uint32_t log2cap, uint32_t nbk, uint32_t hll_p) {
+  return log2cap == 11 && (nbk + 1) / 2 == 9 && hll_p == 14;
+}
+
+// Which small-table kernel a Small engine runs (spanagg_kernels.hip small_fn):
+// the linear-threshold kernel for bounds no bin table holds; otherwise the v2
+// kernel -- specialised for the default geometry, generic with 512-thread
+// workgroups where the LDS state fits a CU's 160 KiB twice (two workgroups per
+// CU: one's prologue and write-back overlap the other's loop, DESIGN section
+// 4), generic with 1,024 threads for the rest.
+enum class SmallKernel { Default, Generic512, Generic1024, Linear };
+inline SmallKernel small_kernel(bool has_bins, size_t lds_bytes, uint32_t log2cap, uint32_t nbk, uint32_t hll_p) {
+  if (!has_bins) return SmallKernel::Linear;
+  if (default_geometry(log2cap, nbk, hll_p)) return SmallKernel::Default;
+  return 2 * lds_bytes <= (size_t)160 * 1024 ? SmallKernel::Generic512 : SmallKernel::Generic1024;
+}
+
+// The small exponential table's kernel: specialised for 2,048 slots and HLL
+// p = 14 (the buckets live in HBM, so their number does not matter).
+enum class ExpoKernel { Specialised, Generic };
+constexpr ExpoKernel expo_kernel(uint32_t log2cap, uint32_t hll_p) {
+  return log2cap == 11 && hll_p == 14 ? ExpoKernel::Specialised : ExpoKernel::Generic;
+}
+
+// The HBM-table kernels (per-span atomics, the partitioned scatter) have an
+// instance unrolled for 16 non-negative bounds and a generic one.
+constexpr bool bounds16(uint32_t nneg, uint32_t npos) { return nneg == 0 && npos == 16; }
+
+// HLL lower-bound filter: one bound per sub-block of 2^shift registers, the
+// sub-blocks as small as kLbMinShift allows within kLbMaxSub of them and never
+// larger than one service's 2^hll_p registers.  n = 0: no filter (hll_p below
+// kLbMinShift, too many registers, or SA_OPT_NO_HLL_FILTER).
+struct LbGeom {
+  uint32_t shift, n;
+};
+inline LbGeom hll_filter_geometry(const sa_config &c) {
+  const uint64_t regs = (uint64_t)c.n_windows * c.n_services << c.hll_p;
+  uint32_t sh = kLbMinShift;
+  while (sh < c.hll_p && (regs >> sh) > kLbMaxSub) ++sh;
+  if ((regs >> sh) <= kLbMaxSub && sh <= c.hll_p && !(c.options & SA_OPT_NO_HLL_FILTER))
+    return {sh, (uint32_t)(regs >> sh)};
+  return {0, 0};
+}
+
+// The v2 and exponential small-table kernels' per-workgroup LDS ERROR table
+// (errslab) keys a (window, slot) pair in 16 bits; engines with more pairs
+// count ERROR spans per span instead.
+constexpr bool error_table(uint32_t n_windows, uint64_t cap) { return (uint64_t)n_windows * cap < 65535; }
+
 }  // namespace sa
 #pragma GCC visibility pop

@@ -352,7 +352,7 @@ __global__ __launch_bounds__(kLdsBlock) void ingest_lds_kernel(IngestParams P) {
 #pragma unroll
     for (int j = 0; j < S; ++j) {
       const uint32_t rho = (info[j] >> 6) & 127u;
-      if ((hv[j] & 0xFFu) < rho) {
+      if (((hv[j] >> ((hoff[j] & 3u) * 8)) & 0xFFu) < rho) {  // (hv: the aligned word the register lies in)
         const uint32_t q = atomicAdd(hq_n, 1u);
         if (q < kHllQueue) hq[q] = make_uint2(hoff[j], rho);
         else hll_raise(P.hll + hoff[j], rho);
@@ -700,7 +700,7 @@ __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
     hq_n[0] = 0;
     // DYN: next unclaimed chunk of this workgroup's range, x 64 (see the claims)
     hq_n[1] = ((kTileClaims ? 2u * NBUF : 2u) * kWaves) << 6;
-    hq_n[2] = 0;  // EPI: HLL updates the lower-bound filter skipped (summed over the waves)
+    hq_n[2] = 0;  // HLL updates the lower-bound filter skipped (summed over the waves)
   }
   if (threadIdx.x < 4) lstat[threadIdx.x] = 0;
   if (POOL && threadIdx.x < kPoolMaxSteal) pmap[threadIdx.x] = 0;
@@ -740,7 +740,7 @@ __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
   unsigned long long hot_sum = 0;
   // wave-uniform event counts (scalar registers)
   uint32_t n_zero = 0, n_badsvc = 0, n_oor = 0, n_drop = 0;
-  uint32_t n_filt = 0;  // per lane: HLL updates the lower-bound filter skipped (EPI builds)
+  uint32_t n_filt = 0;  // per lane: HLL updates the lower-bound filter skipped
 #pragma unroll
   for (int j = 0; j < S; ++j) pend.hoff[j] = pend.rho[j] = 0;
 
@@ -826,7 +826,7 @@ __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
         const uint32_t ho = sk ? (row << hp) + idx : 0u;
         // a rho at or below the register sub-block's lower bound cannot raise it
         const bool up = sk && !(r <= llb[ho >> lbs_v]);
-        if constexpr (EPI) n_filt += (sk && !up) ? 1u : 0u;
+        n_filt += (sk && !up) ? 1u : 0u;
         rho[j] = up ? r : 0u;
         hoff[j] = up ? ho : 0u;
       }
@@ -1119,10 +1119,9 @@ __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
                  ((unsigned long long)(uint32_t)__shfl_xor((int)(uint32_t)(hot_sum >> 32), o, 64) << 32);
     if ((threadIdx.x & 63u) == 0 && hot_sum) atomicAdd(&lsum[hot_slot], hot_sum);
   }
-  if constexpr (EPI) {  // one LDS add per wave; one global add per workgroup after the epilogue
-    n_filt = wave_sum(n_filt);
-    if ((threadIdx.x & 63) == 0 && n_filt) atomicAdd(&hq_n[2], n_filt);
-  }
+  // one LDS add per wave; one global add per workgroup after the epilogue
+  n_filt = wave_sum(n_filt);
+  if ((threadIdx.x & 63) == 0 && n_filt) atomicAdd(&hq_n[2], n_filt);
   // (parameters used only after the loop are read through the laundered
   // kernarg pointer, so they do not hold SGPRs across it)
   unsigned long long *const dbg = cold_params().dbg;
@@ -1183,11 +1182,12 @@ __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
       constexpr uint32_t kIdx[4] = {kStatZeroKey, kStatInvalidService, kStatWindowOOR, kStatDropped};
       atomicAdd(&cold_params().stats[kIdx[threadIdx.x]], (unsigned long long)lstat[threadIdx.x]);
     }
-    // (a slot per workgroup: thousands of same-address atomics at the end of
-    // every launch would serialise its tail)
-    if (threadIdx.x == 0 && hq_n[2])
-      atomicAdd(&cold_params().hll_filt[blockIdx.x & (kFiltSlots - 1)], (unsigned long long)hq_n[2]);
   }
+  // (hq_n[2] is final: the epilogue follows a workgroup barrier.  A slot per
+  // workgroup: thousands of same-address atomics at the end of every launch
+  // would serialise its tail)
+  if (threadIdx.x == 0 && hq_n[2])
+    atomicAdd(&cold_params().hll_filt[blockIdx.x & (kFiltSlots - 1)], (unsigned long long)hq_n[2]);
   if ((threadIdx.x & 63) == 0) {
     unsigned long long *const stats = cold_params().stats;
     if (n_zero) atomicAdd(&stats[kStatZeroKey], (unsigned long long)n_zero);
@@ -1913,7 +1913,7 @@ hipError_t prepare_ingest_small(size_t lds_bytes) {
 // valid for their compile-time geometry (2,048 slots, 17 buckets, HLL p 14)
 static int small_variant(int variant, uint32_t log2cap, uint32_t nbk, uint32_t p) {
   if ((variant == 12 || variant == 13 || (variant >= 14 && variant != 25 && variant != 26)) &&
-      !(log2cap == 11 && (nbk + 1) / 2 == 9 && p == 14))
+      !default_geometry(log2cap, nbk, p))
     variant = variant == 12 ? 8 : variant == 13 ? 11 : 15;
   return variant;
 }
@@ -1982,33 +1982,34 @@ hipError_t prepare_ingest_expo_small(size_t lds_bytes) {
 // tell.  After prepare_ingest_expo_small.
 uint32_t ingest_expo_blocks_per_cu(uint32_t log2cap, uint32_t p, size_t lds_bytes) {
   int n = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, expo_small_fn(log2cap == 11 && p == 14), (int)kLdsBlock,
-                                                   lds_bytes) != hipSuccess)
+  const void *fn = expo_small_fn(expo_kernel(log2cap, p) == ExpoKernel::Specialised);
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, (int)kLdsBlock, lds_bytes) != hipSuccess)
     return 0;
   return n > 0 ? (uint32_t)n : 0u;
 }
 
 hipError_t launch_ingest_expo_small(const IngestParams &P, uint32_t grid, size_t lds_bytes, hipStream_t s) {
   void *args[] = {const_cast<IngestParams *>(&P)};
-  return hipLaunchKernel(expo_small_fn(P.log2cap == 11 && P.p == 14), dim3(grid), dim3(kLdsBlock), args, lds_bytes, s);
+  const void *fn = expo_small_fn(expo_kernel(P.log2cap, P.p) == ExpoKernel::Specialised);
+  return hipLaunchKernel(fn, dim3(grid), dim3(kLdsBlock), args, lds_bytes, s);
 }
 
 hipError_t launch_ingest_part(const IngestParams &P, hipStream_t s) {
 #ifdef SPANAGG_AB
   static const uint32_t max_grid = [] {
     const char *v = std::getenv("SPANAGG_PART_GRID");  // laboratory knob
-    return v ? (uint32_t)std::max(1, std::atoi(v)) : 256u;
+    return v ? (uint32_t)std::max(1, std::atoi(v)) : kPartMaxGrid;
   }();
   static const bool stage = [] {
     const char *v = std::getenv("SPANAGG_PART_STAGE");  // laboratory knob
     return !(v && std::atoi(v) == 0);
   }();
 #else
-  constexpr uint32_t max_grid = 256u;
+  constexpr uint32_t max_grid = kPartMaxGrid;
   constexpr bool stage = true;
 #endif
   const uint32_t grid = (uint32_t)std::min<uint64_t>(max_grid, (P.n + kPartBlock - 1) / kPartBlock);
-  const bool b16 = P.nneg == 0 && P.npos == 16;
+  const bool b16 = bounds16(P.nneg, P.npos);
 #ifdef SPANAGG_AB
   const void *fn = stage ? (b16 ? (const void *)&part_scatter_kernel<16, true> : (const void *)&part_scatter_kernel<-1, true>)
                          : (b16 ? (const void *)&part_scatter_kernel<16, false> : (const void *)&part_scatter_kernel<-1, false>);
@@ -2039,7 +2040,7 @@ hipError_t prepare_ingest_part() {
 }
 
 hipError_t launch_ingest_hbm(const IngestParams &P, uint32_t grid, hipStream_t s, int variant) {
-  if (P.nneg == 0 && P.npos == 16) launch_hbm_nb<16>(P, grid, s, variant);
+  if (bounds16(P.nneg, P.npos)) launch_hbm_nb<16>(P, grid, s, variant);
   else launch_hbm_nb<-1>(P, grid, s, variant);
   return hipGetLastError();
 }

@@ -86,6 +86,20 @@ class sa_stats(C.Structure):
     ]
 
 
+class sa_debug_geometry_info(C.Structure):
+    """include/spanagg_diag.h: the geometry decisions sa_create took."""
+    _fields_ = [
+        ("path", C.c_uint32), ("kernel", C.c_uint32), ("block", C.c_uint32), ("grid_max", C.c_uint32),
+        ("log2cap", C.c_uint32), ("lb_shift", C.c_uint32), ("lb_n", C.c_uint32), ("error_table", C.c_uint32),
+        ("lds_bytes", C.c_uint64),
+    ]
+
+
+PATH_NAMES = ("Small", "ExpoSmall", "ExpoHbm", "Binned", "Dense", "Partitioned", "Atomic")  # sa::Path
+# SA_KERNEL_* (include/spanagg_diag.h)
+KERNEL_NAMES = ("small_default", "small_512", "small_1024", "small_linear", "expo_specialised", "expo_generic",
+                "bounds16", "bounds_generic", "lab")
+
 # (name, restype, argtypes) for every entry point declared in include/spanagg.h
 SIGNATURES = [
     ("sa_config_default", None, [C.POINTER(sa_config)]),
@@ -134,6 +148,7 @@ SIGNATURES = [
     ("sa_group_window_advance", C.c_int, [C.c_void_p, C.c_uint64]),
     ("sa_group_get_stats", C.c_int, [C.c_void_p, C.POINTER(sa_stats)]),
     ("sa_debug_stamps", C.c_int, [C.c_void_p, u64p, C.c_uint64, u64p]),
+    ("sa_debug_geometry", C.c_int, [C.c_void_p, C.POINTER(sa_debug_geometry_info)]),
     ("sa_bucket_thresholds", C.c_int, [f64p, C.c_uint32, C.c_uint32, u64p, u32p]),
     ("sa_hll_estimate", C.c_double, [u8p, C.c_uint32]),
 ]

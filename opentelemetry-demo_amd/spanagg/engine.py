@@ -409,6 +409,17 @@ class Engine:
         self._check(self.lib.sa_get_stats(self._h, C.byref(s)), "sa_get_stats")
         return {name: int(getattr(s, name)) for name, _ in _lib.sa_stats._fields_ if name != "pad"}
 
+    def debug_geometry(self) -> dict:
+        """sa_debug_geometry: which ingest kernel this engine runs -- path and
+        kernel by name (_lib.PATH_NAMES, _lib.KERNEL_NAMES), block, grid_max,
+        log2cap, lb_shift, lb_n (0: no HLL filter), error_table, lds_bytes."""
+        g = _lib.sa_debug_geometry_info()
+        self._check(self.lib.sa_debug_geometry(self._h, C.byref(g)), "sa_debug_geometry")
+        d = {name: int(getattr(g, name)) for name, _ in g._fields_}
+        d["path"], d["kernel"] = _lib.PATH_NAMES[g.path], _lib.KERNEL_NAMES[g.kernel]
+        d["error_table"] = bool(g.error_table)
+        return d
+
     # -- multi-GPU merge hooks (device pointers) ----------------------------
     def export_keys(self, d_keys, cap: int, stream: Optional[int] = None) -> int:
         n = C.c_uint64(0)

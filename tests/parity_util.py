@@ -1,6 +1,8 @@
 """Shared comparison helpers: product (GPU) results vs the CPU oracle."""
 import numpy as np
 
+import pyoracle
+
 SUM_RTOL = 1e-9  # north_star: duration sums within 1e-9 relative
 
 
@@ -37,3 +39,15 @@ def sketch_sparse(hll, cms):
     nz = np.argwhere(cms)
     c = sorted([int(a), int(b), int(cms[a, b])] for a, b in nz)
     return h, c
+
+
+def _check(res, batch, max_size, unit_s=False):
+    ora = pyoracle.expo_aggregate(batch, max_size, unit_s)
+    assert [int(k) for k in res.key_hash] == sorted(ora)
+    for i, k in enumerate(res.key_hash):
+        o = ora[int(k)]
+        assert (int(res.count[i]), int(res.zero_count[i])) == (o["count"], o["zero_count"]), k
+        assert (int(res.scale[i]), int(res.offset[i])) == (o["scale"], o["offset"]), k
+        assert [int(x) for x in res.buckets[i]] == [int(x) for x in o["counts"]], k
+        assert res.min[i] == o["min"] and res.max[i] == o["max"], k
+        assert abs(res.sum[i] - o["sum"]) <= 1e-9 * max(abs(o["sum"]), 1e-300), k

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import pyoracle
+from parity_util import _check
 from spanagg._lib import OPT_EXPO_CACHED, OPT_EXPO_HBM
 from spanagg import Config, Engine, SpanBatch, pack_meta
 from spanagg import _lib
@@ -19,18 +20,6 @@ from spanagg.synth import generate_c2
 
 pytestmark = pytest.mark.gpu
 KAT = os.path.join(os.path.dirname(__file__), "golden", "expo_kat.json")
-
-
-def _check(res, batch, max_size, unit_s=False):
-    ora = pyoracle.expo_aggregate(batch, max_size, unit_s)
-    assert [int(k) for k in res.key_hash] == sorted(ora)
-    for i, k in enumerate(res.key_hash):
-        o = ora[int(k)]
-        assert (int(res.count[i]), int(res.zero_count[i])) == (o["count"], o["zero_count"]), k
-        assert (int(res.scale[i]), int(res.offset[i])) == (o["scale"], o["offset"]), k
-        assert [int(x) for x in res.buckets[i]] == [int(x) for x in o["counts"]], k
-        assert res.min[i] == o["min"] and res.max[i] == o["max"], k
-        assert abs(res.sum[i] - o["sum"]) <= 1e-9 * max(abs(o["sum"]), 1e-300), k
 
 
 def _engine(wl, **kw):

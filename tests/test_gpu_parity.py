@@ -7,6 +7,7 @@ sums float64 ms in Go's arrival order).
 import numpy as np
 import pytest
 
+import geometry_util
 import pyoracle
 from parity_util import assert_red_equal, assert_red_golden, sketch_sparse
 from spanagg._lib import OPT_ATOMIC_TABLE, OPT_PARTITIONED
@@ -265,10 +266,16 @@ def test_flush_is_delta_and_resets():
         assert_red_equal(r2, o2.series())
 
 
-def test_epoch_flush_u16_counters():
+@pytest.mark.parametrize("row", ["default", "half17", "wide10", "linear"])
+def test_epoch_flush_u16_counters(row):
     """> 65,535 spans of one (key, bucket) per workgroup: exercises the LDS
-    u16 epoch flush into the workgroup slabs."""
+    u16 epoch flush into the workgroup slabs -- in each of the four small-table
+    kernels: the default geometry's, the generic 512- and 1,024-thread ones
+    (geometry_util rows half17 and wide10) and the linear-threshold one (40 M
+    spans over at most 512 workgroups)."""
     import torch
+    cfg = Config(n_windows=8) if row == "default" else geometry_util.config_of(row)
+    kernel = "small_default" if row == "default" else geometry_util.ROWS[row]["kernel"]
     n = 40_000_000
     dev = "cuda"
     key = torch.full((n,), 12345, dtype=torch.int64, device=dev)
@@ -277,13 +284,18 @@ def test_epoch_flush_u16_counters():
     w0 = torch.arange(n, dtype=torch.int64, device=dev)
     w1 = torch.zeros(n, dtype=torch.int64, device=dev)
     meta = torch.zeros(n, dtype=torch.int32, device=dev)
-    with Engine(Config(n_windows=8)) as e:
-        e.window_advance(10**18 // 10**10)
+    # 1,000,000 ns lies in a finite bucket of every row's bounds
+    bucket = pyoracle.search_float64s(cfg.bounds, pyoracle.duration(10**18, 10**18 + 1_000_000, cfg.unit == "s"))
+    assert bucket < len(cfg.bounds)
+    with Engine(cfg) as e:
+        g = e.debug_geometry()
+        assert (g["path"], g["kernel"]) == ("Small", kernel) and g["grid_max"] <= 512, g
+        e.window_advance(10**18 // cfg.window_ns)
         e.ingest_device(key, start, end, w0, w1, meta, stream=torch.cuda.current_stream().cuda_stream)
         torch.cuda.synchronize()
         res = e.flush()
         assert res.key_hash.tolist() == [12345]
-        assert int(res.bucket_counts[0, 0]) == n
+        assert int(res.bucket_counts[0, bucket]) == n
         assert int(res.bucket_counts[0].sum()) == n
         assert int(res.sum_ns[0]) == n * 1_000_000
 
