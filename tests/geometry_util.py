@@ -2,7 +2,9 @@
 config, and the comparison with the CPU oracle.
 
 ROWS is shared by tests/test_path_decision.py (the decisions on the CPU) and
-tests/test_gpu_geometry.py (the kernels on the GPU).  Each row's expectation is
+tests/test_gpu_geometry.py (the kernels on the GPU); RING_ROWS, the small rings
+of the moving-ring walk (tests/ring_util.py), by tests/test_path_decision.py,
+tests/test_ring_walk.py and tests/test_gpu_ring.py.  Each row's expectation is
 written from the rules, not read from the code:
 
   cap   = next power of two >= 1.25 x key_capacity (>= 16; SA_OPT_DENSE_IDS: >= 2^19)
@@ -44,6 +46,27 @@ The arithmetic of every row:
   expo_spec   2,048 slots, p 14: specialised
   expo_generic  500 -> 512: 512*41 + X = 45,696.  16*20*2^12 >> 10 = 1,280
   expo_p      2,048 slots, p 10: generic.  16*64*2^10 >> 10 = 1,024
+
+RING_ROWS (n_windows stated in every row; rings small enough to raise every
+register of):
+
+  ring_default   1,250 -> 2,048 slots; nbk 17, p 14: default; 32,768 + 73,728 + X = 131,200.
+                 regs 2*1*2^14 = 32,768 >> 10 = 32 -> (10, 32).  2*2,048 = 4,096: ERROR table
+  ring_512       1,000 -> 1,024; 16,384 + 36,864 + X = 77,952 <= 81,920: 512.  4*2*2^11 = 16,384 >> 10 = 16
+  ring_1024_noerr  1,875 -> 2,048; nbk 10: 32,768 + 40,960 + X = 98,432: 1024.  32*1*2^10 >> 10 = 32 (shift 10 = p).
+                 32*2,048 = 65,536 >= 65,535: no ERROR table
+  ring1          ROWS["ring1"]: one window, every advance clears the whole ring
+  ring_linear    1,250 -> 2,048; nbk 7: 32,768 + 32,768 + X = 90,240; 1.1e6 .. 1.4e6 ns in one bin: linear.
+                 4*2*2^11 >> 10 = 16.  4*2,048 = 8,192: ERROR table (allocated; the linear kernel counts per span)
+  ring_expo_spec   2,048 slots, p 14: specialised; 2,048*41 + X.  2*1*2^14 >> 10 = 32
+  ring_expo_generic  500 -> 512: 512*41 + X = 45,696; p 11: generic.  4*2*2^11 >> 10 = 16
+  ring_expo_hbm  ring_expo_spec with SA_OPT_EXPO_HBM: ExpoHbm, its sketches through the HBM kernel.  The default 16
+                 bounds, none negative: the HBM kernels' rule gives the 16-bound instance (bounds16).  Not an
+                 LDS table: no ERROR table, no dynamic LDS.  Its 2,048-slot table takes the small rows' 700 keys
+  ring_part      125,000 -> 2^17; nbk 10 <= 17, below 2^19: Partitioned; one negative bound: generic.  (10, 16)
+  ring_atomic    2^17; nbk 31 > 17: Atomic; 30 bounds: generic.  (10, 16)
+  ring_binned    375,000 -> 2^19; nbk 5, a bin table, 4 windows <= 1,024: Binned.  (10, 16)
+  ring_dense     ring_binned with SA_OPT_DENSE_IDS
 """
 import functools
 
@@ -53,7 +76,7 @@ import pyoracle
 from parity_util import _check as check_expo
 from parity_util import assert_red_equal
 from spanagg import Config, SpanBatch, bucket_thresholds, pack_meta
-from spanagg._lib import OPT_DENSE_IDS
+from spanagg._lib import OPT_DENSE_IDS, OPT_EXPO_HBM
 
 DEFAULT = (2, 4, 6, 8, 10, 50, 100, 200, 400, 800, 1000, 1400, 2000, 5000, 10000, 15000)
 NINE = (-1.5, -0.0, 0.1, 0.3, 1.0000001, 3.3, 7.77, 1e3, 2.5e6)
@@ -112,8 +135,61 @@ ROWS = {
 }
 
 
+def _ring(cfg, *expect, fill=24, n_keys=None):
+    """A RING_ROWS row: n_windows stated; `fill` = the fill batch's spans per
+    register of the ring (ring_util.walk)."""
+    assert "n_windows" in cfg
+    r = dict(_row(cfg, *expect), fill=fill)
+    if n_keys is not None:
+        r["n_keys"] = n_keys
+    return r
+
+
+_RING_EXPO = dict(key_capacity=1000, exp_max_size=160, hll_p=14, n_services=1, n_windows=2)
+_RING_BINNED = dict(key_capacity=300_000, bounds=(1, 10, 100, 1000), hll_p=11, n_services=2, n_windows=4)
+
+RING_ROWS = {
+    "ring_default": _ring(dict(key_capacity=1000, hll_p=14, n_services=1, n_windows=2),
+                          "Small", "small_default", 11, (10, 32), True, 131_200),
+    "ring_512": _ring(dict(key_capacity=800, hll_p=11, n_services=2, n_windows=4),
+                      "Small", "small_512", 10, (10, 16), True, 77_952),
+    "ring_1024_noerr": _ring(dict(key_capacity=1500, bounds=NINE, unit="s", hll_p=10, n_services=1, n_windows=32),
+                             "Small", "small_1024", 11, (10, 32), False, 98_432),
+    "ring1": dict(ROWS["ring1"], fill=24),
+    "ring_linear": _ring(dict(key_capacity=1000, bounds=CROWDED6, hll_p=11, n_services=2, n_windows=4),
+                         "Small", "small_linear", 11, (10, 16), True, 90_240),
+    "ring_expo_spec": _ring(_RING_EXPO, "ExpoSmall", "expo_specialised", 11, (10, 32), True, 2048 * 41 + 24_704),
+    "ring_expo_generic": _ring(dict(key_capacity=400, exp_max_size=20, hll_p=11, n_services=2, n_windows=4),
+                               "ExpoSmall", "expo_generic", 9, (10, 16), True, 45_696),
+    "ring_expo_hbm": _ring(dict(_RING_EXPO, options=OPT_EXPO_HBM), "ExpoHbm", "bounds16", 11, (10, 32), n_keys=700),
+    "ring_part": _ring(dict(key_capacity=100_000, bounds=NINE, unit="s", hll_p=11, n_services=2, n_windows=4),
+                       "Partitioned", "bounds_generic", 17, (10, 16)),
+    "ring_atomic": _ring(dict(key_capacity=100_000, bounds=THIRTY, hll_p=11, n_services=2, n_windows=4),
+                         "Atomic", "bounds_generic", 17, (10, 16)),
+    "ring_binned": _ring(_RING_BINNED, "Binned", "bounds_generic", 19, (10, 16)),
+    "ring_dense": _ring(dict(_RING_BINNED, options=OPT_DENSE_IDS), "Dense", "bounds_generic", 19, (10, 16)),
+}
+
+
 def config_of(row) -> Config:
-    return Config(**ROWS[row]["cfg"])
+    return Config(**(RING_ROWS.get(row) or ROWS[row])["cfg"])
+
+
+def assert_geometry(e, row):
+    """Engine.debug_geometry() against the row's expectation (ROWS or RING_ROWS)."""
+    r, g = RING_ROWS.get(row) or ROWS[row], e.debug_geometry()
+    assert (g["path"], g["kernel"], g["log2cap"]) == (r["path"], r["kernel"], r["log2cap"]), g
+    assert (g["lb_shift"], g["lb_n"]) == r["lb"], g
+    assert g["error_table"] == r["error_table"], g
+    if r["lds"]:
+        assert g["lds_bytes"] == r["lds"], g
+    # 256-thread workgroups on the atomic path (an ExpoHbm engine's sketches run its kernel), 1,024
+    # everywhere else but the half-block kernel
+    hbm = r["path"] in ("Atomic", "ExpoHbm")
+    assert g["block"] == (512 if r["kernel"] == "small_512" else 256 if hbm else 1024), g
+    # small tables: one resident round of workgroups, at most two per CU
+    assert 0 < g["grid_max"] and (g["grid_max"] <= 512 or r["path"] not in ("Small", "ExpoSmall")), g
+    return g
 
 
 def ring_start(cfg) -> int:

@@ -24,7 +24,7 @@ import zlib
 import numpy as np
 import pytest
 
-from geometry_util import OFF, ROWS, THIN, check_against_oracle, config_of, make_batch, ring_start
+from geometry_util import OFF, ROWS, THIN, assert_geometry, check_against_oracle, config_of, make_batch, ring_start
 from spanagg import Engine
 
 pytestmark = pytest.mark.gpu
@@ -33,20 +33,6 @@ pytestmark = pytest.mark.gpu
 def _rng(row):
     # dense5 takes binned5's batches: both must equal the same oracle, hence each other
     return np.random.default_rng(zlib.crc32({"dense5": "binned5"}.get(row, row).encode()))
-
-
-def assert_geometry(e, row):
-    r, g = ROWS[row], e.debug_geometry()
-    assert (g["path"], g["kernel"], g["log2cap"]) == (r["path"], r["kernel"], r["log2cap"]), g
-    assert (g["lb_shift"], g["lb_n"]) == r["lb"], g
-    assert g["error_table"] == r["error_table"], g
-    if r["lds"]:
-        assert g["lds_bytes"] == r["lds"], g
-    # 256-thread workgroups on the atomic path, 1,024 everywhere else but the half-block kernel
-    assert g["block"] == (512 if r["kernel"] == "small_512" else 256 if r["path"] == "Atomic" else 1024), g
-    # small tables: one resident round of workgroups, at most two per CU
-    assert 0 < g["grid_max"] and (g["grid_max"] <= 512 or r["path"] not in ("Small", "ExpoSmall")), g
-    return g
 
 
 def _engine(row):

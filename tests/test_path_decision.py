@@ -27,7 +27,9 @@ small-table kernel (small_kernel), the small exponential table's kernel
 the HLL filter's sub-blocks (hll_filter_geometry) and the small tables' ERROR
 table rule (error_table).  tests/geometry_util.py states those rules and works
 every row of its matrix out by hand; the rows are checked here on the CPU and
-run on the GPU by tests/test_gpu_geometry.py.
+run on the GPU by tests/test_gpu_geometry.py.  The rows of the moving-ring
+matrix (RING_ROWS, run by tests/test_gpu_ring.py) go through the same program
+and the same assertions.
 
 The same program also runs built with -fsanitize=address,undefined (plain
 host code; nothing is preloaded).
@@ -38,7 +40,7 @@ import subprocess
 
 import pytest
 
-from geometry_util import ROWS
+from geometry_util import RING_ROWS, ROWS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "opentelemetry-demo_amd", "csrc")
@@ -159,7 +161,16 @@ def test_path_table(tmp_path, flags):
     assert [g[3] for g in got[:3]] == ["small_default", "expo_specialised", "bounds16"]
     assert got[7][3] == "small_linear"  # CROWDED on a small table
     assert got[8][3] == "bounds16" and got[17][3] == "bounds_generic"
-    for (name, r), g in zip(ROWS.items(), got[len(CASES):]):
+    _assert_rows(ROWS, got[len(CASES):])
+    ring = subprocess.run([str(exe)], input="".join(_line(**r["cfg"]) for r in RING_ROWS.values()),
+                          capture_output=True, text=True, check=True).stdout.split("\n")
+    ring = [tuple(ln.split()) for ln in ring if ln]
+    assert len(ring) == len(RING_ROWS)
+    _assert_rows(RING_ROWS, ring)
+
+
+def _assert_rows(rows, got):
+    for (name, r), g in zip(rows.items(), got):
         assert (g[0], int(g[1]), g[3]) == (r["path"], r["log2cap"], r["kernel"]), (name, g)
         assert (int(g[4]), int(g[5])) == r["lb"], (name, g)
         assert bool(int(g[6])) == r["error_table"], (name, g)
