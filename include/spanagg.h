@@ -17,6 +17,7 @@
  *   exportMetrics -> buildMetrics + resetState      sa_flush (+ host-side encoding)
  *   Shutdown                                        sa_destroy
  *   (new) per-service HLL + error count-min         sa_window_read / sa_window_advance
+ *   (new) the same over a span of windows           sa_window_range (merged on the device)
  *
  * Boundary rules (mirroring the connector's contracts):
  *  - Ownership: batches are borrowed for the duration of the call (page-locked
@@ -295,6 +296,44 @@ int sa_window_read(sa_engine *e, uint64_t window_id, sa_sketch_result **out);
 int sa_window_advance(sa_engine *e, uint64_t new_base);
 void sa_sketch_result_free(sa_sketch_result *r);
 
+/* ---- range queries over the window ring ----
+ * The sketches of the resident windows first..last (inclusive) merged on the
+ * device: HLL registers max-merged, count-min cells summed, point queries for
+ * a list of series.  Only the answers cross the bus: without flags a call
+ * returns n_services x SA_HLL_HIST_BINS histogram words, the estimates and
+ * n_keys counts, whatever the ring holds (one sa_window_read per window copies
+ * n_services x 2^hll_p bytes each). */
+#define SA_HLL_HIST_BINS 64          /* register values 0 .. 65 - p <= 61 */
+#define SA_RANGE_REGISTERS 1u        /* also return the merged registers */
+#define SA_RANGE_CELLS     2u        /* also return the summed cells */
+
+typedef struct {
+    uint64_t first_window, last_window;      /* inclusive */
+    uint32_t n_services, hll_p;
+    const uint32_t *hll_hist;  /* [n_services][SA_HLL_HIST_BINS]: registers of the max-merged
+                                  array holding value v; every row sums to 2^hll_p */
+    const double *distinct;    /* [n_services] sa_hll_estimate_hist(row, hll_p) */
+    const uint8_t *hll;        /* [n_services][2^hll_p] merged registers; NULL without SA_RANGE_REGISTERS */
+    uint32_t cms_d, cms_w;
+    const uint64_t *cms;       /* [cms_d][cms_w] cells summed over the windows, unsaturated;
+                                  NULL without SA_RANGE_CELLS */
+    uint64_t n_keys;
+    const uint64_t *errors;    /* [n_keys] min over rows of the summed cell of keys[i]: the merged
+                                  sketch's estimate, an upper bound on the key's ERROR spans */
+} sa_range_result;
+
+/* Ordering and waiting as sa_window_read: joins every launch in flight, runs
+ * on the engine stream, waits, clears nothing (two calls give equal results).
+ * SA_ERANGE when first > last or a window of the range is not resident;
+ * SA_EINVAL for a null `out`, n_keys != 0 with null `keys`, unknown flag bits.
+ * `keys`: a host array of series hashes borrowed for the call -- hashes also
+ * on an SA_OPT_DENSE_IDS engine (the count-min is addressed by the bound
+ * hash); key 0 is allowed.  Works on every ingest path.  Free the result with
+ * sa_range_result_free. */
+int sa_window_range(sa_engine *e, uint64_t first, uint64_t last, const uint64_t *keys,
+                    uint64_t n_keys, uint32_t flags, sa_range_result **out);
+void sa_range_result_free(sa_range_result *r);
+
 int sa_get_stats(sa_engine *e, sa_stats *out);
 
 /* ---- multi-GPU merge hooks (device pointers on this engine's device) ----
@@ -375,6 +414,12 @@ int sa_group_flush_exp(sa_group *g, sa_exp_result **out);
 /* Merged sketches of one resident window. Free with sa_sketch_result_free. */
 int sa_group_window_read(sa_group *g, uint64_t window_id, sa_sketch_result **out);
 int sa_group_window_advance(sa_group *g, uint64_t new_base);
+/* sa_window_range of a group: every member merges its own windows on its
+ * device, the group's transport merges the members' registers (max) and
+ * cells (sum), and member 0's device takes the histogram and the point
+ * queries.  Results equal those of one engine fed every span. */
+int sa_group_window_range(sa_group *g, uint64_t first, uint64_t last, const uint64_t *keys,
+                          uint64_t n_keys, uint32_t flags, sa_range_result **out);
 /* Counters summed over members (n_keys and table_capacity too; window_base and
  * small_table from member 0). */
 int sa_group_get_stats(sa_group *g, sa_stats *out);
@@ -387,6 +432,13 @@ int sa_bucket_thresholds(const double *bounds, uint32_t n_bounds, uint32_t unit,
                          uint64_t *thr, uint32_t *n_neg);
 /* HLL estimate of one register array (standard estimator + linear counting). */
 double sa_hll_estimate(const uint8_t *regs, uint32_t p);
+/* The same estimate from a register array's value histogram (hist[v] =
+ * registers holding v, SA_HLL_HIST_BINS words summing to 2^p): sum hist[v] *
+ * 2^-v is taken exactly, as sum hist[v] << (63 - v) in a 128-bit integer
+ * converted to double once, so the result does not depend on any summation
+ * order; then sa_hll_estimate's alpha and linear-counting branch (zeros =
+ * hist[0]).  -1.0 for p outside 4..18.  Defines sa_range_result.distinct. */
+double sa_hll_estimate_hist(const uint32_t *hist, uint32_t p);
 
 #ifdef __cplusplus
 }

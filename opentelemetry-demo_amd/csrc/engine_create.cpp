@@ -127,6 +127,21 @@ double sa_hll_estimate(const uint8_t *regs, uint32_t p) {
   return est;
 }
 
+double sa_hll_estimate_hist(const uint32_t *hist, uint32_t p) {
+  if (!hist || p < 4 || p > 18) return -1.0;
+  const uint32_t m = 1u << p;
+  // sum hist[v] * 2^-v, exactly: 2^63 times it is an integer below 2^(32 + 63)
+  unsigned __int128 acc = 0;
+  for (uint32_t v = 0; v < SA_HLL_HIST_BINS; ++v) acc += (unsigned __int128)hist[v] << (63 - v);
+  const double sum = std::ldexp((double)acc, -63);
+  const uint32_t zeros = hist[0];
+  const double alpha = m == 16 ? 0.673 : m == 32 ? 0.697 : m == 64 ? 0.709
+                                                                  : 0.7213 / (1.0 + 1.079 / m);
+  double est = alpha * (double)m * (double)m / sum;
+  if (est <= 2.5 * m && zeros) est = (double)m * std::log((double)m / (double)zeros);
+  return est;
+}
+
 int sa_create(const sa_config *cfg, sa_engine **out) {
   if (!out) return SA_EINVAL;
   *out = nullptr;

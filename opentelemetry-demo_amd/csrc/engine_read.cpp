@@ -1,11 +1,12 @@
 // engine_read.cpp -- the read side of the engine: flush and compaction,
-// window sketches, stats, key reclamation, the merge hooks (export, gather),
+// window sketches and range queries over them, stats, key reclamation, the merge hooks (export, gather),
 // sa_bind_ids, the probes and the engine group's asynchronous hooks (sa_grp).
 // Every call here joins the launches in flight onto the engine stream first.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
+#include <memory>
 #include <numeric>
 #include <string>
 #include <vector>
@@ -165,6 +166,89 @@ bool resident(const sa_engine *e, uint64_t w) {
   return w >= e->win_base && w - e->win_base < e->cfg.n_windows;
 }
 
+// ---- range queries (sa_window_range; kernels in spanagg_range.hip) ----
+constexpr uint32_t kRangeFlags = SA_RANGE_REGISTERS | SA_RANGE_CELLS;
+
+int range_args(sa_engine *e, uint64_t first, uint64_t last, const uint64_t *keys, uint64_t n_keys, uint32_t flags) {
+  if (n_keys && !keys) return fail(e, SA_EINVAL, "window range: n_keys != 0 with null keys");
+  if (flags & ~kRangeFlags) return fail(e, SA_EINVAL, "window range: unknown flag bits");
+  if (first > last || !resident(e, first) || !resident(e, last))
+    return fail(e, SA_ERANGE, "window range: first > last or a window of it is not resident");
+  return SA_OK;
+}
+
+// the engine's own device buffers: the histogram, room for n_keys keys and
+// their answers, and the merged registers / summed cells where asked for
+int range_buffers(sa_engine *e, uint64_t n_keys, bool regs, bool cells) {
+  sa_engine::Range &R = e->range;
+  const uint32_t S = e->cfg.n_services;
+  if (!R.hist)
+    if (int rc = dalloc(e, R.hist, (size_t)S * SA_HLL_HIST_BINS, false, "window range: histogram hipMalloc failed"))
+      return rc;
+  if (regs && !R.regs)
+    if (int rc = dalloc(e, R.regs, e->hll_slot_bytes, false, "window range: register buffer hipMalloc failed")) return rc;
+  if (cells && !R.cells)
+    if (int rc = dalloc(e, R.cells, e->cms_slot_elems, false, "window range: cell buffer hipMalloc failed")) return rc;
+  if (n_keys > R.key_cap) {  // (hipFree waits for the device)
+    dfree(e, R.keys);
+    R.key_cap = 0;
+    const uint64_t want = std::max<uint64_t>(n_keys, 1u << 10);
+    if (int rc = dalloc(e, R.keys, want * 2, false, "window range: key buffer hipMalloc failed")) return rc;
+    R.key_cap = want;
+  }
+  return SA_OK;
+}
+
+// On `s`: every window of first..last folded (its per-slot ERROR counts go to
+// its cells before any cell is summed), then the registers max-merged into
+// hist (zeroed here) and regs, and the cells summed into cells -- each where
+// the pointer is not null.
+int range_merge_on(sa_engine *e, uint64_t first, uint64_t last, uint32_t *hist, uint8_t *regs,
+                   unsigned long long *cells, hipStream_t s) {
+  const uint32_t W = e->cfg.n_windows, n = (uint32_t)(last - first + 1);
+  // fold_window for each, with the windows' count folds as one launch (the
+  // ERROR slabs of the small rings that have them go window by window first)
+  for (uint32_t k = 0; k < n; ++k)
+    if (int rc = fold_errslab(e, (first + k) & (W - 1), s)) return rc;
+  SA_HIP(e, sa::launch_range_fold(e->gkeys, e->errcnt, e->cap, e->cms, e->cms_slot_elems, e->cfg.cms_d, e->cfg.cms_w,
+                                  64 - sa::log2u(e->cfg.cms_w), e->d_seeds, e->binned.kinv, e->dense() ? 1u : 0u, W,
+                                  first, n, s));
+  if (hist) SA_HIP(e, hipMemsetAsync(hist, 0, (size_t)e->cfg.n_services * SA_HLL_HIST_BINS * 4, s));
+  if (hist || regs) SA_HIP(e, sa::launch_range_merge(e->hll, W, e->cfg.n_services, e->cfg.hll_p, first, n, hist, regs, s));
+  if (cells) SA_HIP(e, sa::launch_range_cells(e->cms, e->cms_slot_elems, W, first, n, cells, s));
+  return SA_OK;
+}
+
+// From the device arrays to the result, on `s` (waited for): the point
+// queries on d_cells, the copies of what the flags ask for, the estimates.
+int range_result(sa_engine *e, uint64_t first, uint64_t last, const uint32_t *d_hist, const uint8_t *d_regs,
+                 const unsigned long long *d_cells, const uint64_t *keys, uint64_t n_keys, uint32_t flags,
+                 hipStream_t s, sa_range_result **out) {
+  std::unique_ptr<range_holder> h(new range_holder());
+  h->shape(first, last, e->cfg, n_keys, flags);
+  hipError_t st = hipSuccess;
+  if (n_keys) {
+    uint64_t *dk = e->range.keys, *de = dk + e->range.key_cap;
+    st = hipMemcpyAsync(dk, keys, n_keys * 8, hipMemcpyHostToDevice, s);
+    if (st == hipSuccess)
+      st = sa::launch_range_query(d_cells, e->cfg.cms_d, e->cfg.cms_w, 64 - sa::log2u(e->cfg.cms_w), e->d_seeds, dk,
+                                  n_keys, reinterpret_cast<unsigned long long *>(de), s);
+    if (st == hipSuccess) st = hipMemcpyAsync(h->errors.data(), de, n_keys * 8, hipMemcpyDeviceToHost, s);
+  }
+  if (st == hipSuccess) st = hipMemcpyAsync(h->hist.data(), d_hist, h->hist.size() * 4, hipMemcpyDeviceToHost, s);
+  if (st == hipSuccess && (flags & SA_RANGE_REGISTERS))
+    st = hipMemcpyAsync(h->hll.data(), d_regs, h->hll.size(), hipMemcpyDeviceToHost, s);
+  if (st == hipSuccess && (flags & SA_RANGE_CELLS))
+    st = hipMemcpyAsync(h->cms.data(), d_cells, h->cms.size() * 8, hipMemcpyDeviceToHost, s);
+  const hipError_t waited = hipStreamSynchronize(s);  // (also after a failure: a copy into h may be in flight)
+  if (st != hipSuccess || waited != hipSuccess)
+    return fail(e, SA_EDEVICE, std::string("window range: ") + hipGetErrorString(st != hipSuccess ? st : waited));
+  for (uint32_t sv = 0; sv < e->cfg.n_services; ++sv)
+    h->distinct[sv] = sa_hll_estimate_hist(h->hist.data() + (size_t)sv * SA_HLL_HIST_BINS, e->cfg.hll_p);
+  *out = &h.release()->r;
+  return SA_OK;
+}
+
 }  // namespace
 
 namespace sa_grp {
@@ -204,6 +288,29 @@ int sync_stream(sa_engine *e) {
   if (int rc = set_dev(e)) return rc;
   SA_HIP(e, hipStreamSynchronize(e->stream));
   return SA_OK;
+}
+
+int window_range_export_async(sa_engine *e, uint64_t first, uint64_t last, uint8_t *d_hll, uint64_t *d_cms,
+                              hipStream_t s) {
+  if (!e || !d_hll || !d_cms) return SA_EINVAL;
+  if (int rc = range_args(e, first, last, nullptr, 0, 0)) return rc;
+  if (int rc = begin_read(e)) return rc;
+  if (int rc = hop_to(e, s)) return rc;
+  if (int rc = range_merge_on(e, first, last, nullptr, d_hll, reinterpret_cast<unsigned long long *>(d_cms), s))
+    return rc;
+  return hop_back(e, s);  // (the folds wrote this engine's cells and ERROR counts)
+}
+
+int window_range_finish(sa_engine *e, uint64_t first, uint64_t last, const uint8_t *d_hll, const uint64_t *d_cms,
+                        const uint64_t *keys, uint64_t n_keys, uint32_t flags, hipStream_t s, sa_range_result **out) {
+  if (!e || !out || !d_hll || !d_cms) return SA_EINVAL;
+  if (int rc = set_dev(e)) return rc;
+  if (int rc = range_buffers(e, n_keys, false, false)) return rc;  // (the merged arrays are the group's)
+  uint32_t *hist = e->range.hist;
+  SA_HIP(e, hipMemsetAsync(hist, 0, (size_t)e->cfg.n_services * SA_HLL_HIST_BINS * 4, s));
+  SA_HIP(e, sa::launch_hll_hist(d_hll, e->cfg.n_services, e->cfg.hll_p, hist, s));
+  return range_result(e, first, last, hist, d_hll, reinterpret_cast<const unsigned long long *>(d_cms), keys, n_keys,
+                      flags, s, out);
 }
 }  // namespace sa_grp
 
@@ -414,6 +521,23 @@ int sa_window_read(sa_engine *e, uint64_t window_id, sa_sketch_result **out) {
 }
 
 void sa_sketch_result_free(sa_sketch_result *r) { delete reinterpret_cast<sketch_holder *>(r); }
+
+int sa_window_range(sa_engine *e, uint64_t first, uint64_t last, const uint64_t *keys, uint64_t n_keys, uint32_t flags,
+                    sa_range_result **out) {
+  if (!e || !out) return SA_EINVAL;
+  *out = nullptr;
+  if (int rc = range_args(e, first, last, keys, n_keys, flags)) return rc;
+  if (int rc = begin_read(e)) return rc;
+  const bool regs = flags & SA_RANGE_REGISTERS, cells = n_keys || (flags & SA_RANGE_CELLS);
+  if (int rc = range_buffers(e, n_keys, regs, cells)) return rc;
+  const sa_engine::Range &R = e->range;
+  // (without SA_RANGE_REGISTERS the merge writes the histogram and nothing else)
+  if (int rc = range_merge_on(e, first, last, R.hist, regs ? R.regs : nullptr, cells ? R.cells : nullptr, e->stream))
+    return rc;
+  return range_result(e, first, last, R.hist, R.regs, R.cells, keys, n_keys, flags, e->stream, out);
+}
+
+void sa_range_result_free(sa_range_result *r) { delete reinterpret_cast<range_holder *>(r); }
 
 int sa_window_advance(sa_engine *e, uint64_t new_base) {
   if (!e) return SA_EINVAL;

@@ -373,6 +373,31 @@ __device__ __forceinline__ void cms_add(const IngestParams &P, uint32_t ws, uint
   }
 }
 
+// One window slot's exact per-slot ERROR counts added into its count-min
+// cells, then cleared (so reads are idempotent); the workgroups of blockIdx.x
+// stride the slots.  fold_errcnt_kernel for one window, range_fold_kernel for
+// the windows of a range.
+__device__ __forceinline__ void fold_errcnt_slots(const unsigned long long *gkeys, unsigned long long *errcnt,
+                                                  uint64_t cap, unsigned long long *cms, uint32_t d, uint32_t w,
+                                                  uint32_t shift, const uint64_t *seeds, uint64_t kinv,
+                                                  uint32_t dense) {
+  for (uint64_t s = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; s < cap;
+       s += (uint64_t)gridDim.x * blockDim.x) {
+    const unsigned long long c = errcnt[s];
+    if (!c) continue;
+    const uint64_t key = gkeys[s] * kinv;
+    if (dense && key == 0) {  // dense-index engines: ERROR spans on an unbound index touch no cell
+      errcnt[s] = 0;
+      continue;
+    }
+    for (uint32_t r = 0; r < d; ++r) {
+      const uint64_t col = splitmix64(key ^ seeds[r]) >> shift;
+      atomicAdd(cms + (uint64_t)r * w + col, c);
+    }
+    errcnt[s] = 0;
+  }
+}
+
 // Sketch phase B: raise HLL registers that grew; count ERROR spans.  A span
 // whose series has a key-table slot adds 1 to the exact per-(window, slot)
 // error counter (one atomic); the count-min cells are derived from those

@@ -193,6 +193,16 @@ struct sa_engine {
     uint64_t bind_cap = 0;
   } binned;
   size_t hll_slot_bytes = 0, cms_slot_elems = 0;
+  // sa_window_range (allocated by its first call): the histogram
+  // [n_services][SA_HLL_HIST_BINS], the merged registers (SA_RANGE_REGISTERS
+  // only), the summed cells, and the keys with their answers [2][key_cap]
+  struct Range {
+    uint32_t *hist = nullptr;
+    uint8_t *regs = nullptr;
+    unsigned long long *cells = nullptr;
+    uint64_t *keys = nullptr;
+    uint64_t key_cap = 0;
+  } range;
   // sa_ingest: two pinned host slots and their HBM copies; a slot is refilled
   // once its event (H2D copy + aggregation of the previous use) has passed
   struct HostStage {

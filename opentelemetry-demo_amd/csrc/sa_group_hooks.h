@@ -29,4 +29,16 @@ bool over_reclaim_threshold(const sa_engine *e, uint64_t n_keys);
 int sync_stream(sa_engine *e);
 // key-table slots (sa_stats.table_capacity without a device read)
 uint64_t table_capacity(const sa_engine *e);
+// sa_window_range's device part for one member, without the wait: every
+// window of first..last folded, then d_hll [n_services][2^p] = their registers
+// max-merged and d_cms [d][w] = their cells summed (u64), on `s`.  SA_ERANGE
+// as sa_window_range.
+int window_range_export_async(sa_engine *e, uint64_t first, uint64_t last, uint8_t *d_hll, uint64_t *d_cms,
+                              hipStream_t s);
+// the rest of a group's range query, on member 0 (`e`, whose device holds the
+// merged d_hll and d_cms) and on `s`: the histogram of d_hll, the point
+// queries on d_cms, the copies and the wait.  keys, flags and *out as
+// sa_window_range.
+int window_range_finish(sa_engine *e, uint64_t first, uint64_t last, const uint8_t *d_hll, const uint64_t *d_cms,
+                        const uint64_t *keys, uint64_t n_keys, uint32_t flags, hipStream_t s, sa_range_result **out);
 }  // namespace sa_grp

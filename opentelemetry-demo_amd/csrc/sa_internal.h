@@ -509,6 +509,28 @@ hipError_t launch_reduce_errslab(uint32_t *errslab, uint32_t G, uint64_t per_wg,
                                  uint32_t log2cap, unsigned long long *errcnt_ws, hipStream_t s);
 hipError_t launch_count_keys(const unsigned long long *gkeys, uint64_t cap,
                              unsigned long long *out, hipStream_t s);
+// range queries over the window ring (spanagg_range.hip): windows first ..
+// first + n_win - 1 of a ring of n_windows slots (slot = window & (n_windows - 1)).
+// hist [n_services][SA_HLL_HIST_BINS] (zeroed by the caller; nullptr: none): the
+// max-merged registers holding each value; out [n_services][2^p] (nullptr:
+// none): the merged registers themselves
+hipError_t launch_range_merge(const uint8_t *hll, uint32_t n_windows, uint32_t n_services, uint32_t p, uint64_t first,
+                              uint32_t n_win, uint32_t *hist, uint8_t *out, hipStream_t s);
+// launch_fold_errcnt for the n_win windows from `first` in one launch
+// (errcnt [n_windows][cap], cms [n_windows][slot_elems])
+hipError_t launch_range_fold(const unsigned long long *gkeys, unsigned long long *errcnt, uint64_t cap,
+                             unsigned long long *cms, uint64_t slot_elems, uint32_t d, uint32_t w, uint32_t shift,
+                             const uint64_t *seeds, uint64_t kinv, uint32_t dense, uint32_t n_windows, uint64_t first,
+                             uint32_t n_win, hipStream_t s);
+// the same histogram of an already merged array [n_services][2^p]
+hipError_t launch_hll_hist(const uint8_t *merged, uint32_t n_services, uint32_t p, uint32_t *hist, hipStream_t s);
+// out [slot_elems] = the windows' count-min cells summed (zeroes out first)
+hipError_t launch_range_cells(const unsigned long long *cms, uint64_t slot_elems, uint32_t n_windows, uint64_t first,
+                              uint32_t n_win, unsigned long long *out, hipStream_t s);
+// out[i] = min over the d rows of cells[r][splitmix64(keys[i] ^ seeds[r]) >> shift]
+hipError_t launch_range_query(const unsigned long long *cells, uint32_t d, uint32_t w, uint32_t shift,
+                              const uint64_t *seeds, const uint64_t *keys, uint64_t n, unsigned long long *out,
+                              hipStream_t s);
 // sorted union of series ids on the device (spanagg_union.hip): out = the
 // distinct non-zero ids of in[0..n) ascending, *d_total (device u32) their
 // count; scratch >= key_union_scratch_bytes(n); big_scratch / big_bytes: a

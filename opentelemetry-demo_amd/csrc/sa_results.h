@@ -104,6 +104,26 @@ struct exp_holder {
   }
 };
 
+struct range_holder {
+  sa_range_result r;
+  std::vector<uint32_t> hist;
+  std::vector<double> distinct;
+  std::vector<uint8_t> hll;
+  std::vector<uint64_t> cms, errors;
+  // the columns sized for config c, n_keys keys and the flags' optional parts, and r pointing at them
+  __attribute__((visibility("hidden"))) void shape(uint64_t first, uint64_t last, const sa_config &c, uint64_t n_keys,
+                                                   uint32_t flags) {
+    hist.resize((size_t)c.n_services * SA_HLL_HIST_BINS), distinct.resize(c.n_services), errors.resize(n_keys);
+    if (flags & SA_RANGE_REGISTERS) hll.resize((size_t)c.n_services << c.hll_p);
+    if (flags & SA_RANGE_CELLS) cms.resize((size_t)c.cms_d * c.cms_w);
+    r.first_window = first, r.last_window = last, r.n_services = c.n_services, r.hll_p = c.hll_p;
+    r.hll_hist = hist.data(), r.distinct = distinct.data();
+    r.hll = (flags & SA_RANGE_REGISTERS) ? hll.data() : nullptr;
+    r.cms_d = c.cms_d, r.cms_w = c.cms_w, r.cms = (flags & SA_RANGE_CELLS) ? cms.data() : nullptr;
+    r.n_keys = n_keys, r.errors = errors.data();
+  }
+};
+
 struct sketch_holder {
   sa_sketch_result r;
   std::vector<uint8_t> hll;

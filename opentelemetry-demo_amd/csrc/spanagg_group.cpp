@@ -1082,6 +1082,51 @@ int sa_group_window_read(sa_group *g, uint64_t window_id, sa_sketch_result **out
   return SA_OK;
 }
 
+// Each member merges its own windows first..last on its device (registers
+// max-merged, cells summed), the transport merges the members' arrays as for
+// one window, and member 0's device takes the histogram and the point queries.
+int sa_group_window_range(sa_group *g, uint64_t first, uint64_t last, const uint64_t *keys, uint64_t n_keys,
+                          uint32_t flags, sa_range_result **out) {
+  if (!g || !out) return SA_EINVAL;
+  *out = nullptr;
+  if (n_keys && !keys) return gfail(g, SA_EINVAL, "window range: n_keys != 0 with null keys");
+  if (flags & ~(SA_RANGE_REGISTERS | SA_RANGE_CELLS)) return gfail(g, SA_EINVAL, "window range: unknown flag bits");
+  const uint32_t n = (uint32_t)g->eng.size();
+  for (uint32_t i = 0; i < n; ++i) {
+    if (int rc = ensure(g, g->dev[i], g->hll[i], g->hll_bytes)) return rc;
+    if (int rc = ensure(g, g->dev[i], g->cms[i], g->cms_elems * 8)) return rc;
+    if (int rc = sa_grp::window_range_export_async(g->eng[i], first, last, static_cast<uint8_t *>(g->hll[i].p),
+                                                   static_cast<uint64_t *>(g->cms[i].p), g->st[i]))
+      return member_error(g, i, rc, "window range");
+  }
+  if (g->rccl) {
+    SG_NCCL(g, ncclGroupStart());
+    for (uint32_t i = 0; i < n; ++i) {
+      SG_NCCL(g, ncclAllReduce(g->hll[i].p, g->hll[i].p, g->hll_bytes, ncclUint8, ncclMax, g->comm[i], g->st[i]));
+      SG_NCCL(g, ncclAllReduce(g->cms[i].p, g->cms[i].p, g->cms_elems, ncclUint64, ncclSum, g->comm[i], g->st[i]));
+    }
+    SG_NCCL(g, ncclGroupEnd());
+  } else {
+    if (int rc = copy_reduce(g, g->hll, g->hll_bytes, true)) return rc;
+    if (int rc = copy_reduce(g, g->cms, g->cms_elems, false)) return rc;
+  }
+  const int rc = sa_grp::window_range_finish(g->eng[0], first, last, static_cast<const uint8_t *>(g->hll[0].p),
+                                             static_cast<const uint64_t *>(g->cms[0].p), keys, n_keys, flags, g->st[0],
+                                             out);
+  hipError_t st = hipSuccess;
+  for (uint32_t i = 1; i < n && st == hipSuccess; ++i) {  // (an all-reduce ends on every member's stream)
+    st = hipSetDevice(g->dev[i]);
+    if (st == hipSuccess) st = hipStreamSynchronize(g->st[i]);
+  }
+  if (rc) return member_error(g, 0, rc, "window range");
+  if (st != hipSuccess) {
+    sa_range_result_free(*out);
+    *out = nullptr;
+    return gfail(g, SA_EDEVICE, std::string("window range: ") + hipGetErrorString(st));
+  }
+  return SA_OK;
+}
+
 int sa_group_window_advance(sa_group *g, uint64_t new_base) {
   if (!g) return SA_EINVAL;
   for (uint32_t i = 0; i < g->eng.size(); ++i)

@@ -1826,21 +1826,7 @@ __global__ void count_keys_kernel(const unsigned long long *gkeys, uint64_t cap,
 __global__ void fold_errcnt_kernel(const unsigned long long *gkeys, unsigned long long *errcnt,
                                    uint64_t cap, unsigned long long *cms, uint32_t d, uint32_t w,
                                    uint32_t shift, const uint64_t *seeds, uint64_t kinv, uint32_t dense) {
-  for (uint64_t s = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; s < cap;
-       s += (uint64_t)gridDim.x * blockDim.x) {
-    const unsigned long long c = errcnt[s];
-    if (!c) continue;
-    const uint64_t key = gkeys[s] * kinv;
-    if (dense && key == 0) {  // dense-index engines: ERROR spans on an unbound index touch no cell
-      errcnt[s] = 0;
-      continue;
-    }
-    for (uint32_t r = 0; r < d; ++r) {
-      const uint64_t col = splitmix64(key ^ seeds[r]) >> shift;
-      atomicAdd(cms + (uint64_t)r * w + col, c);
-    }
-    errcnt[s] = 0;
-  }
+  fold_errcnt_slots(gkeys, errcnt, cap, cms, d, w, shift, seeds, kinv, dense);
 }
 
 uint32_t grid_for(uint64_t work, uint32_t block, uint32_t cap_blocks) {

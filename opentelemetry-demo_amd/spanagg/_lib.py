@@ -77,6 +77,18 @@ class sa_sketch_result(C.Structure):
     ]
 
 
+SA_HLL_HIST_BINS = 64
+SA_RANGE_REGISTERS, SA_RANGE_CELLS = 1, 2
+
+
+class sa_range_result(C.Structure):
+    _fields_ = [
+        ("first_window", C.c_uint64), ("last_window", C.c_uint64), ("n_services", C.c_uint32), ("hll_p", C.c_uint32),
+        ("hll_hist", u32p), ("distinct", f64p), ("hll", u8p), ("cms_d", C.c_uint32), ("cms_w", C.c_uint32),
+        ("cms", u64p), ("n_keys", C.c_uint64), ("errors", u64p),
+    ]
+
+
 class sa_stats(C.Structure):
     _fields_ = [
         ("spans", C.c_uint64), ("zero_key", C.c_uint64), ("invalid_service", C.c_uint64),
@@ -127,6 +139,12 @@ SIGNATURES = [
     ("sa_window_read", C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.POINTER(sa_sketch_result))]),
     ("sa_window_advance", C.c_int, [C.c_void_p, C.c_uint64]),
     ("sa_sketch_result_free", None, [C.POINTER(sa_sketch_result)]),
+    ("sa_window_range", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, u64p, C.c_uint64, C.c_uint32,
+                                  C.POINTER(C.POINTER(sa_range_result))]),
+    ("sa_group_window_range", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, u64p, C.c_uint64, C.c_uint32,
+                                        C.POINTER(C.POINTER(sa_range_result))]),
+    ("sa_range_result_free", None, [C.POINTER(sa_range_result)]),
+    ("sa_hll_estimate_hist", C.c_double, [u32p, C.c_uint32]),
     ("sa_get_stats", C.c_int, [C.c_void_p, C.POINTER(sa_stats)]),
     ("sa_bind_ids", C.c_int, [C.c_void_p, u64p, u64p, C.c_uint64]),
     ("sa_export_keys", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, u64p, C.c_void_p]),

@@ -137,10 +137,40 @@ class SketchResult:
         return hll_estimate(self.hll[service_id], self.p)
 
 
+@dataclass
+class RangeResult:
+    """sa_range_result: the sketches of windows first..last merged on the device."""
+    first: int
+    last: int
+    hist: np.ndarray              # [n_services, 64] u32: merged registers holding each value
+    distinct: np.ndarray          # [n_services] f64: hll_estimate_hist(hist[s], p)
+    hll: Optional[np.ndarray]     # [n_services, 2^p] u8 merged registers (registers=True), else None
+    cms: Optional[np.ndarray]     # [d, w] u64 summed cells, unsaturated (cells=True), else None
+    errors: np.ndarray            # [n_keys] u64: the merged count-min's estimate for keys[i]
+    keys: np.ndarray              # [n_keys] u64, as given
+    p: int = 14
+
+    def top_errors(self, k: int = 10):
+        """Top-k (key, estimate) of the queried keys, ordered as sketch.heavy_hitters."""
+        est = [(int(key), int(e)) for key, e in zip(self.keys, self.errors) if e > 0]
+        est.sort(key=lambda e: (-e[1], e[0]))
+        return est[:k]
+
+
 def hll_estimate(regs: np.ndarray, p: int) -> float:
     lib = _lib.load()
     r = np.ascontiguousarray(regs, dtype=np.uint8)
     return float(lib.sa_hll_estimate(r.ctypes.data_as(_lib.u8p), p))
+
+
+def hll_estimate_hist(hist: np.ndarray, p: int) -> float:
+    """sa_hll_estimate_hist: the estimate from a register array's value
+    histogram (64 counts), exact in the sum and so independent of its order."""
+    lib = _lib.load()
+    h = np.ascontiguousarray(hist, dtype=np.uint32)
+    if h.shape != (_lib.SA_HLL_HIST_BINS,):
+        raise ValueError("hll_estimate_hist: the histogram has 64 bins")
+    return float(lib.sa_hll_estimate_hist(h.ctypes.data_as(_lib.u32p), p))
 
 
 def bucket_thresholds(bounds, unit: str = "ms"):
@@ -201,6 +231,28 @@ def _sketch_result(lib, out) -> SketchResult:
         return SketchResult(int(r.window_id), hll, cms, int(r.hll_p))
     finally:
         lib.sa_sketch_result_free(out)
+
+
+def _window_range(obj, fn, what, first, last, keys, registers, cells) -> RangeResult:
+    """sa_window_range / sa_group_window_range -> RangeResult (copies), freeing the library's result."""
+    k = np.ascontiguousarray(() if keys is None else keys, dtype=np.uint64).reshape(-1)
+    flags = (_lib.SA_RANGE_REGISTERS if registers else 0) | (_lib.SA_RANGE_CELLS if cells else 0)
+    out = C.POINTER(_lib.sa_range_result)()
+    obj._check(fn(obj._h, int(first), int(last), k.ctypes.data_as(_lib.u64p) if len(k) else None, len(k), flags,
+                  C.byref(out)), what)
+    try:
+        r = out.contents
+        S, p = int(r.n_services), int(r.hll_p)
+        return RangeResult(
+            int(r.first_window), int(r.last_window),
+            np.ctypeslib.as_array(r.hll_hist, shape=(S, _lib.SA_HLL_HIST_BINS)).copy(),
+            np.ctypeslib.as_array(r.distinct, shape=(S,)).copy(),
+            np.ctypeslib.as_array(r.hll, shape=(S, 1 << p)).copy() if r.hll else None,
+            np.ctypeslib.as_array(r.cms, shape=(r.cms_d, r.cms_w)).copy() if r.cms else None,
+            np.ctypeslib.as_array(r.errors, shape=(len(k),)).copy() if len(k) else np.zeros(0, np.uint64),
+            k, p)
+    finally:
+        obj.lib.sa_range_result_free(out)
 
 
 def _ptr(x) -> int:
@@ -353,6 +405,15 @@ class Engine:
         out = C.POINTER(_lib.sa_sketch_result)()
         self._check(self.lib.sa_window_read(self._h, window_id, C.byref(out)), "sa_window_read")
         return _sketch_result(self.lib, out)
+
+    def window_range(self, first: int, last: int, keys=None, registers: bool = False,
+                     cells: bool = False) -> RangeResult:
+        """sa_window_range: the resident windows first..last (inclusive)
+        merged on the device -- per service the merged registers' histogram
+        and estimate, and the summed count-min's estimate for each of `keys`
+        (series hashes, also on a dense-index engine).  registers / cells:
+        also the merged registers / the summed cells themselves."""
+        return _window_range(self, self.lib.sa_window_range, "sa_window_range", first, last, keys, registers, cells)
 
     def flush_exp(self, allow_drops: bool = False) -> ExpoResult:
         out = C.POINTER(_lib.sa_exp_result)()
@@ -517,6 +578,12 @@ class Group:
         out = C.POINTER(_lib.sa_sketch_result)()
         self._check(self.lib.sa_group_window_read(self._h, window_id, C.byref(out)), "sa_group_window_read")
         return _sketch_result(self.lib, out)
+
+    def window_range(self, first: int, last: int, keys=None, registers: bool = False,
+                     cells: bool = False) -> RangeResult:
+        """sa_group_window_range: Engine.window_range over the members' merge."""
+        return _window_range(self, self.lib.sa_group_window_range, "sa_group_window_range", first, last, keys,
+                             registers, cells)
 
     def window_advance(self, new_base: int):
         self._check(self.lib.sa_group_window_advance(self._h, int(new_base)), "sa_group_window_advance")
