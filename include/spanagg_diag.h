@@ -73,10 +73,26 @@ typedef struct sa_debug_geometry_info {
   uint32_t lb_n;        /* ... lb_n of them; 0: the filter is off */
   uint32_t error_table; /* 1: per-workgroup (window, slot) ERROR tables (small tables) */
   uint64_t lds_bytes;   /* the ingest kernel's dynamic LDS (small tables) */
+  /* the exponential histograms' counting pass (all 0 without exp_max_size) */
+  uint32_t expo_count;     /* SA_EXPO_COUNT_*: which kernels count the buckets */
+  uint32_t expo_entries;   /* slab counting: a counting workgroup's LDS entries; cached-probe: its cache's; else 0 */
+  uint32_t expo_bin_slots; /* slab counting: key slots per fold bin of the tail records (16, 8 past max_size 2,048) */
+  uint32_t expo_bins;      /* slab counting: fold bins (slots / expo_bin_slots, rounded up) */
 } sa_debug_geometry_info;
 
+/* How an exponential engine counts buckets (sa_debug_geometry_info.expo_count).
+ * Small tables: slab counting (a series among the expo_entries most frequent
+ * of the last launch counts in LDS, the others leave as tail records that one
+ * workgroup per fold bin adds up), or with SA_OPT_EXPO_CACHED -- and when the
+ * LDS has no room for one entry -- the cached-probe kernel.  HBM tables
+ * (SA_OPT_EXPO_HBM, or more slots than LDS holds): the three HBM passes. */
+enum { SA_EXPO_COUNT_NONE = 0, SA_EXPO_COUNT_SLAB = 1, SA_EXPO_COUNT_CACHED = 2, SA_EXPO_COUNT_HBM = 3 };
+
 /* Diagnostic: the geometry decisions sa_create took for this engine, so a
- * test can assert which device code it is about to run.  Host state only. */
+ * test can assert which device code it is about to run: the ingest kernel and
+ * its launch geometry, the HLL filter, the ERROR table, and for exponential
+ * histograms the counting kernel (expo_count), its LDS entries (expo_entries)
+ * and the tail fold's layout (expo_bin_slots, expo_bins).  Host state only. */
 int sa_debug_geometry(sa_engine *e,sa_debug_geometry_info *out);
 
 #ifdef __cplusplus

@@ -418,6 +418,18 @@ int sa_debug_geometry(sa_engine *e, sa_debug_geometry_info *out) {
   out->lb_n = e->lb_n;
   out->error_table = e->small.errslab != nullptr;
   out->lds_bytes = sa::lds_table(e->path) ? e->lds_bytes : 0;
+  if (e->path == Path::ExpoHbm) {
+    out->expo_count = SA_EXPO_COUNT_HBM;
+  } else if (e->path == Path::ExpoSmall && e->expo.xc_ne) {
+    const uint32_t M = e->cfg.exp_max_size;
+    out->expo_count = SA_EXPO_COUNT_SLAB;
+    out->expo_entries = e->expo.xc_ne;
+    out->expo_bin_slots = sa::xt_bin_slots(M);
+    out->expo_bins = sa::xt_bins(e->cap, M);
+  } else if (e->path == Path::ExpoSmall) {
+    out->expo_count = SA_EXPO_COUNT_CACHED;
+    out->expo_entries = sa::expo_cached_entries(e->cfg.exp_max_size);
+  }
   return SA_OK;
 }
 

@@ -545,6 +545,7 @@ hipError_t launch_expo_compact(const ExpoParams &E, unsigned long long *out_keys
                                uint32_t *out_buckets, unsigned long long *out_n, hipStream_t s);
 hipError_t launch_expo_init(ExpoHdr *hdr, int8_t *xscale, uint64_t cap, hipStream_t s);
 size_t expo_count_lds_bytes(uint64_t cap, uint32_t max_size);
+uint32_t expo_cached_entries(uint32_t max_size);  // the cached-probe kernel's cache entries (sa_debug_geometry)
 // LDS entries of the slab counting kernel for one workgroup's LDS budget, and its LDS bytes
 uint32_t expo_slab_entries(uint64_t cap, uint32_t max_size, size_t budget);
 size_t expo_slab_lds_bytes(uint64_t cap, uint32_t max_size, uint32_t ne);

@@ -1030,6 +1030,8 @@ size_t expo_count_lds_bytes(uint64_t cap, uint32_t max_size) {
   return (size_t)cap * 8 + (size_t)ne * 4 + ((size_t)ne * max_size + 1) / 2 * 4;
 }
 
+uint32_t expo_cached_entries(uint32_t max_size) { return xc_entries(max_size); }
+
 hipError_t prepare_expo_count(size_t lds_bytes) {
   return hipFuncSetAttribute((const void *)&expo_count_cached_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)lds_bytes);

@@ -104,9 +104,13 @@ class sa_debug_geometry_info(C.Structure):
         ("path", C.c_uint32), ("kernel", C.c_uint32), ("block", C.c_uint32), ("grid_max", C.c_uint32),
         ("log2cap", C.c_uint32), ("lb_shift", C.c_uint32), ("lb_n", C.c_uint32), ("error_table", C.c_uint32),
         ("lds_bytes", C.c_uint64),
+        ("expo_count", C.c_uint32), ("expo_entries", C.c_uint32), ("expo_bin_slots", C.c_uint32),
+        ("expo_bins", C.c_uint32),
     ]
 
 
+# SA_EXPO_COUNT_* (include/spanagg_diag.h): an exponential engine's counting pass
+EXPO_COUNT_NONE, EXPO_COUNT_SLAB, EXPO_COUNT_CACHED, EXPO_COUNT_HBM = 0, 1, 2, 3
 PATH_NAMES = ("Small", "ExpoSmall", "ExpoHbm", "Binned", "Dense", "Partitioned", "Atomic")  # sa::Path
 # SA_KERNEL_* (include/spanagg_diag.h)
 KERNEL_NAMES = ("small_default", "small_512", "small_1024", "small_linear", "expo_specialised", "expo_generic",

@@ -473,7 +473,10 @@ class Engine:
     def debug_geometry(self) -> dict:
         """sa_debug_geometry: which ingest kernel this engine runs -- path and
         kernel by name (_lib.PATH_NAMES, _lib.KERNEL_NAMES), block, grid_max,
-        log2cap, lb_shift, lb_n (0: no HLL filter), error_table, lds_bytes."""
+        log2cap, lb_shift, lb_n (0: no HLL filter), error_table, lds_bytes; and
+        the exponential histograms' counting pass -- expo_count (_lib.EXPO_COUNT_*:
+        0 none, 1 slab counting, 2 cached-probe, 3 the HBM passes), expo_entries,
+        expo_bin_slots, expo_bins."""
         g = _lib.sa_debug_geometry_info()
         self._check(self.lib.sa_debug_geometry(self._h, C.byref(g)), "sa_debug_geometry")
         d = {name: int(getattr(g, name)) for name, _ in g._fields_}
