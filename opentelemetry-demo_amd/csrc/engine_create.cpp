@@ -24,10 +24,6 @@ constexpr uint64_t kCmsSeed[8] = {0x9E3779B97F4A7C15ULL, 0xBF58476D1CE4E5B9ULL,
                                   0x94D049BB133111EBULL, 0xD6E8FEB86659FD93ULL,
                                   0xA0761D6478BD642FULL, 0xE7037ED1A0B428DBULL,
                                   0x8EBC6AF09C88C6E3ULL, 0x589965CC75374CC3ULL};
-// small path: ingest_v2_kernel variant 20 (19 LEAN: the span hash on 32-bit
-// halves and the wave-level (slot, bucket) dedup of the hot series' counter
-// adds); SPANAGG_VARIANT overrides in the laboratory build
-constexpr int kDefaultVariant = 20;
 constexpr uint32_t kDefaultSlabSets = 2;  // SPANAGG_SLAB_SETS overrides (laboratory build)
 
 // The engine's ordering events only order its own launches, copies and
@@ -152,7 +148,7 @@ int sa_create(const sa_config *cfg, sa_engine **out) {
     delete e;
     return rc;
   }
-  const LabKnobs knobs = lab_for_create();  // (laboratory build: this engine's SPANAGG_VARIANT, SLAB_SETS, ...)
+  const LabKnobs knobs = lab_for_create();  // (laboratory build: this engine's SPANAGG_SLAB_SETS, SPANAGG_KMUL, ...)
   e->cfg = *cfg;
   e->cfg.bounds = e->hist.bounds.data();
   const sa::Hist &h = e->hist;
@@ -202,37 +198,26 @@ int sa_create(const sa_config *cfg, sa_engine **out) {
   e->path = choice.path;
   e->lds_bytes = choice.lds_bytes;
   const bool small = e->path == Path::Small, expo_small = e->path == Path::ExpoSmall;
-  const uint32_t nw = (h.nbk + 1) / 2;
-  e->variant = small ? kDefaultVariant : 0;
-  if (knobs.variant_set)
-    e->variant = std::max(0, std::min((small ? sa::kNumLdsVariants : sa::kNumVariants) - 1, knobs.variant));
-  // the laboratory TAG variant also keeps a u32 key tag per slot in LDS; a
-  // table whose tags do not fit stays on the default variant
-  if (small && e->variant == sa::kLdsTagVariant) {
-    if (e->lds_bytes + (size_t)e->cap * sa::kLdsTagBytesPerSlot <= sa::kLdsBudget)
-      e->lds_bytes += (size_t)e->cap * sa::kLdsTagBytesPerSlot;
-    else
-      e->variant = kDefaultVariant;
-  }
   if (small) {
-    // the product's kernel for the geometry (sa_path.h small_kernel); the
-    // laboratory build's other variants report SA_KERNEL_LAB
-    e->kernel_kind = SA_KERNEL_LAB;
-    if (e->variant == kDefaultVariant) {
-      const sa::SmallKernel k = sa::small_kernel(h.has_bins, e->lds_bytes, e->log2cap, h.nbk, cfg->hll_p);
-      if (k == sa::SmallKernel::Generic512) e->variant = sa::kLdsHalfBlockVariant;
-      e->kernel_kind = k == sa::SmallKernel::Default      ? SA_KERNEL_SMALL_DEFAULT
-                       : k == sa::SmallKernel::Generic512 ? SA_KERNEL_SMALL_512
-                       : k == sa::SmallKernel::Generic1024 ? SA_KERNEL_SMALL_1024
-                                                           : SA_KERNEL_SMALL_LINEAR;
-    }
-    e->spl = (uint32_t)sa::kLdsSpl[e->variant];
-    e->block = sa::ingest_small_block(h.has_bins, e->variant, e->log2cap, h.nbk, cfg->hll_p);
+    // the kernel for the geometry (sa_path.h small_kernel).  Laboratory build:
+    // an engine with SA_DIAG_* flags runs the ablation instance, which has
+    // Generic1024's geometry, and reports SA_KERNEL_LAB
+    sa::SmallKernel k = sa::small_kernel(h.has_bins, e->lds_bytes, e->log2cap, h.nbk, cfg->hll_p);
+    if (e->diag() && k == sa::SmallKernel::Linear)
+      return bail(fail(e, SA_EINVAL, "SA_DIAG_* flags: the linear-threshold kernel has no ablation instance"));
+    if (e->diag()) k = sa::SmallKernel::Generic1024;
+    e->small_kernel = k;
+    e->kernel_kind = e->diag()                          ? SA_KERNEL_LAB
+                     : k == sa::SmallKernel::Default    ? SA_KERNEL_SMALL_DEFAULT
+                     : k == sa::SmallKernel::Generic512 ? SA_KERNEL_SMALL_512
+                     : k == sa::SmallKernel::Generic1024 ? SA_KERNEL_SMALL_1024
+                                                         : SA_KERNEL_SMALL_LINEAR;
+    e->spl = sa::small_spans_per_lane(k);
+    e->block = sa::small_block(k);
     if ((rc = lds_attr(sa::prepare_ingest_small(e->lds_bytes)))) return bail(rc);
     // one resident round of workgroups (registers and LDS decide how many
     // share a CU; a second round would repeat every workgroup's prologue)
-    uint32_t per_cu = sa::ingest_small_blocks_per_cu(h.has_bins, e->variant, e->log2cap, h.nbk, cfg->hll_p,
-                                                     e->lds_bytes);
+    uint32_t per_cu = sa::ingest_small_blocks_per_cu(k, e->diag(), e->lds_bytes);
     if (per_cu == 0)
       per_cu = std::max<uint32_t>(1, std::min<uint32_t>(2048 / e->block, (uint32_t)((160 * 1024) / e->lds_bytes)));
     e->G = e->cus * per_cu;
@@ -258,7 +243,7 @@ int sa_create(const sa_config *cfg, sa_engine **out) {
     // (the binned and dense scatters have one instance: the value names the bounds they run with)
     e->kernel_kind = sa::bounds16(h.nneg, h.npos) ? SA_KERNEL_BOUNDS16 : SA_KERNEL_BOUNDS_GENERIC;
     e->block = sa::kHbmBlock;
-    e->spl = (uint32_t)sa::kVariants[e->variant].spl;
+    e->spl = sa::kHbmSpansPerLane;
     e->G = e->cus * 8;
     // (the binned path keeps the partitioned kernels' attribute too)
     if (e->path == Path::Partitioned || e->path == Path::Binned)
@@ -372,13 +357,11 @@ int sa_create(const sa_config *cfg, sa_engine **out) {
     const size_t gs = (size_t)e->G * e->order.nsets;  // slabs of all sets, set-major
     if ((rc = dalloc(e, s.slab_cnt, gs * e->cap * srow, true)) || (rc = dalloc(e, s.slab_sum, gs * e->cap, true)))
       return bail(rc);
-    // (window, slot) keys of the v2 kernels' LDS ERROR table are 16-bit
-    if (e->small_v2() && sa::error_table(cfg->n_windows, e->cap) &&
+    // (window, slot) keys of the v2 kernels' LDS ERROR table are 16-bit (the
+    // linear-threshold kernel counts ERROR spans per span: its slabs stay zero)
+    if (sa::error_table(cfg->n_windows, e->cap) &&
         (rc = dalloc(e, s.errslab, gs * cfg->n_windows * e->cap, true)))
       return bail(rc);
-    // the tail pool: only the specialised default geometry has a POOL kernel
-    s.pool = e->variant == sa::kLdsPoolVariant && e->d_bins && e->log2cap == 11 && nw == 9 && cfg->hll_p == 14;
-    if (s.pool && (rc = dalloc(e, s.pool_ring, sa::kPoolRing, true))) return bail(rc);
   }
   if (hipDeviceSynchronize() != hipSuccess) return bail(fail(e, SA_EDEVICE, "device sync failed"));
   *out = e;

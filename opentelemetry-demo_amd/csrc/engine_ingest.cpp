@@ -204,9 +204,7 @@ uint64_t max_spans_per_launch(const sa_engine *e) {
     case Path::Binned:
     case Path::Dense: return (uint64_t)e->binned.grid * sa::kBtMaxWgSpans;
     case Path::Partitioned: return sa::kPartMaxSpans;
-    case Path::Small:
-      if (e->small.pool) return (uint64_t)e->G * sa::kPoolMaxWgSpans;
-      return (uint64_t)e->G * (e->small_v2() ? sa::kMaxWgSpans : (1u << 27));
+    case Path::Small:  // (the linear-threshold kernel flushes every epoch; it keeps the v2 kernels' limit)
     case Path::ExpoSmall: return (uint64_t)e->G * sa::kMaxWgSpans;
     case Path::ExpoHbm:
     case Path::Atomic: break;
@@ -217,32 +215,19 @@ uint64_t max_spans_per_launch(const sa_engine *e) {
 // Workgroup ranges of one launch of n spans (n > 0).
 struct LaunchPlan {
   uint32_t grid = 0;
-  uint64_t wg_chunk = 0, pool_base = 0;
-  uint32_t pool_n = 0;
+  uint64_t wg_chunk = 0;
   uint64_t slab_load = 0;  // what the launch adds to a workgroup's slab counters (Small)
 };
 
-int plan_launch(sa_engine *e, uint64_t n, LaunchPlan &pl) {
+LaunchPlan plan_launch(const sa_engine *e, uint64_t n) {
+  LaunchPlan pl;
   const uint64_t tile = (uint64_t)e->block * e->spl;
   // each workgroup gets one contiguous range of >= one tile (kernel: wg_range)
   pl.grid = (uint32_t)std::min<uint64_t>((n + tile - 1) / tile, e->G);
   const uint64_t per = (n + pl.grid - 1) / pl.grid;
   pl.wg_chunk = (per + 3) / 4 * 4;
-  // tail pool (POOL kernel): each workgroup's static share is 7/8 of the
-  // average in whole 256-span chunks, the rest is the pool the workgroups
-  // that finish first take in blocks of kPoolSpans (a launch too small for two
-  // fixed chunks per wave has no pool)
-  if (e->small.pool) {
-    const uint64_t wc = std::min<uint64_t>(per * 7 / 8 / 256 * 256, sa::kPoolMaxStatic);
-    if (wc >= sa::kPoolMinStatic) {
-      pl.wg_chunk = wc;
-      pl.pool_base = pl.grid * wc;
-      pl.pool_n = (uint32_t)((n - pl.pool_base + sa::kPoolSpans - 1) / sa::kPoolSpans);
-      if (pl.pool_n > (uint64_t)pl.grid * sa::kPoolMaxSteal) return fail(e, SA_EINVAL, "tail pool above the steal limits");
-    }
-  }
-  if (e->path == Path::Small) pl.slab_load = pl.pool_n ? pl.wg_chunk + sa::kPoolMaxSteal * sa::kPoolSpans : pl.wg_chunk;
-  return SA_OK;
+  if (e->path == Path::Small) pl.slab_load = pl.wg_chunk;
+  return pl;
 }
 
 // Small path: folds every set into the counters before `load` more spans per
@@ -283,7 +268,7 @@ int mark_after(sa_engine *e, hipStream_t hs, uint32_t first_set, uint32_t n, boo
 }
 
 // The launch parameters of one ingest of batch b into slab set `set` (the
-// workgroup ranges, pool and tables; every path's kernels read from these).
+// workgroup ranges and tables; every path's kernels read from these).
 void fill_params(sa_engine *e, const sa_span_batch *b, uint32_t set, const LaunchPlan &pl, IngestParams &P) {
   const sa::Hist &h = e->hist;
   sa_engine::Small &sm = e->small;
@@ -296,13 +281,6 @@ void fill_params(sa_engine *e, const sa_span_batch *b, uint32_t set, const Launc
   P.meta = b->meta;
   P.n = b->n;
   P.wg_chunk = pl.wg_chunk;
-  P.pool_base = pl.pool_base;
-  P.pool_n = pl.pool_n;
-  if (sm.pool) {
-    P.pool_ctr = sm.pool_ring + sm.pool_seq % sa::kPoolRing;
-    P.pool_next = sm.pool_ring + (sm.pool_seq + e->order.nsets) % sa::kPoolRing;
-    ++sm.pool_seq;
-  }
   P.gkeys = e->gkeys;
   P.log2cap = e->log2cap;
   P.max_probe = sa::max_probe_of(e->log2cap);
@@ -351,12 +329,12 @@ int launched(sa_engine *e, hipError_t st) {
 }
 
 int launch_small(sa_engine *e, uint32_t grid, const IngestParams &P, hipStream_t s) {
-  return launched(e, sa::launch_ingest_small(P, grid, e->lds_bytes, s, e->variant));
+  return launched(e, sa::launch_ingest_small(P, grid, e->lds_bytes, s, e->small_kernel, e->diag()));
 }
 
 // per-span CAS insert and atomics into the HBM rows
 int launch_atomic(sa_engine *e, uint32_t grid, const IngestParams &P, hipStream_t s) {
-  return launched(e, sa::launch_ingest_hbm(P, grid, s, e->variant));
+  return launched(e, sa::launch_ingest_hbm(P, grid, s));
 }
 
 // Binned and dense: the scatter here, the aggregate on agg_stream (the
@@ -470,7 +448,7 @@ int launch_expo(sa_engine *e, const sa_span_batch *b, uint32_t set, uint32_t gri
     // sketches (and the zero-key / service / window counters) through the
     // HBM-table kernel with its RED part off
     P.diag |= SA_DIAG_NO_RED;
-    st = sa::launch_ingest_hbm(P, grid, s, e->variant);
+    st = sa::launch_ingest_hbm(P, grid, s);
   }
   // then the histogram kernels
   if (st == hipSuccess) st = sa::launch_expo_ingest(expo_params(e, b, set), hs);
@@ -489,8 +467,7 @@ int launch_expo(sa_engine *e, const sa_span_batch *b, uint32_t set, uint32_t gri
 // room in the slabs, the order before, the path's launcher, the mark after.
 int ingest_launch(sa_engine *e, const sa_span_batch *b, hipStream_t s) {
   if (b->n == 0) return SA_OK;
-  LaunchPlan pl;
-  if (int rc = plan_launch(e, b->n, pl)) return rc;
+  const LaunchPlan pl = plan_launch(e, b->n);
   if (pl.slab_load) {
     if (int rc = make_slab_room(e, pl.slab_load)) return rc;
     e->small.slab_load += pl.slab_load;
@@ -676,7 +653,7 @@ int sa_ingest_device(sa_engine *e, const sa_span_batch *b, void *stream) {
 }
 
 // k device batches in order on `stream`, as k sa_ingest_device calls would
-// ingest them.  Small-table engines (no tail pool, no diagnostics) launch the
+// ingest them.  Small-table engines (no diagnostics) launch the
 // k kernels as one HIP graph: no per-launch dispatch gap between them.  Any
 // other engine, a batch that would split, or a slab reduction due inside the
 // k launches takes the stream path, one launch after another.
@@ -687,12 +664,12 @@ int sa_ingest_device_many(sa_engine *e, const sa_span_batch *bs, uint32_t k, voi
     if (int rc = check_batch(e, &bs[i], true)) return rc;
   if (int rc = set_dev(e)) return rc;
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : e->stream;
-  bool graph = k > 1 && e->path == Path::Small && !e->small.pool && !e->dbg && e->cfg.flags == 0;
+  bool graph = k > 1 && e->path == Path::Small && !e->dbg && !e->diag();
   std::vector<LaunchPlan> pl(graph ? k : 0);
   uint64_t load = 0;
   for (uint32_t i = 0; graph && i < k; ++i) {
-    graph = bs[i].n != 0 && bs[i].n <= max_spans_per_launch(e) && plan_launch(e, bs[i].n, pl[i]) == SA_OK;
-    if (graph) load += pl[i].slab_load;
+    graph = bs[i].n != 0 && bs[i].n <= max_spans_per_launch(e);
+    if (graph) load += (pl[i] = plan_launch(e, bs[i].n)).slab_load;
   }
   if (graph) {
     if (int rc = make_slab_room(e, load)) return rc;
@@ -714,7 +691,7 @@ int sa_ingest_device_many(sa_engine *e, const sa_span_batch *bs, uint32_t k, voi
   for (uint32_t i = 0; i < k; ++i) {
     fill_params(e, &bs[i], (first + i) % nsets, pl[i], P[i]);
     args[i] = &P[i];
-    sa::ingest_small_node(P[i], pl[i].grid, e->lds_bytes, e->variant, &args[i], &np[i]);
+    sa::ingest_small_node(pl[i].grid, e->lds_bytes, e->small_kernel, &args[i], &np[i]);
   }
   const bool reuse = g.x && g.nodes.size() == k && g.fn == np[0].func && g.lds == e->lds_bytes &&
                      g.block.x == np[0].blockDim.x;

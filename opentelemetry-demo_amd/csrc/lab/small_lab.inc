@@ -1,67 +1,16 @@
 // lab/small_lab.inc -- laboratory build only (-DSPANAGG_AB, libspanagg_ab.so):
-// every small-table kernel variant (SPANAGG_VARIANT, sa_internal.h lists
-// them) and the diagnostic (SA_DIAG ablation) instances.  Included by
-// spanagg_kernels.hip; the product library never compiles it.
+// the small-table ablation instance.  Included by spanagg_kernels.hip; the
+// product library never compiles it.
 //
-// The v2 kernel's laboratory option sets: the product's V2Plain / V2Lean
-// switches plus DIAG (honour the SA_DIAG_* ablation bits), TAG (32-bit tag
-// lookup, lab/v2_tag_lookup.inc) and POOL (tail pool, lab/v2_pool_loop.inc).
-template <int S_, int NBUF_, int AUX_, bool DIAG_, int HAUX_, bool DYN_, int OPT_, bool EPI_, bool LEAN_, bool TAG_,
-          bool POOL_>
-struct LabV2 {
-  static constexpr int S = S_, NBUF = NBUF_, AUX = AUX_, HAUX = HAUX_, OPT = OPT_;
-  static constexpr bool DYN = DYN_, EPI = EPI_, LEAN = LEAN_, DIAG = DIAG_, TAG = TAG_, POOL = POOL_;
+// An engine created with SA_DIAG_* flags runs the generic 1,024-thread v2
+// kernel with V2Plain's switches plus DIAG (honour the ablation bits, stamp
+// the step's segments); sa_create gives such an engine SmallKernel::Generic1024
+// and refuses the flags on the linear-threshold kernel, which has no ablation
+// instance.
+struct V2Diag : V2Plain {
+  static constexpr bool DIAG = true;
 };
-// (the round-5 template order, so the variant table below reads as before)
-template <int S, int NBUF, int AUX, bool DIAG, int LC = 0, int NWC = 0, int PC = 0, int HAUX = -1, bool DYN = false,
-          int OPT = 0, bool EPI = false, bool LEAN = false, bool EXPO = false, bool TAG = false, bool POOL = false,
-          uint32_t BLK = kLdsBlock>
-const void *const lab_v2 = (const void *)&ingest_v2_kernel<LC, NWC, PC, EXPO, BLK,
-                                                            LabV2<S, NBUF, AUX, DIAG, HAUX, DYN, OPT, EPI, LEAN, TAG, POOL>>;
 
-static const void *small_fn(bool bt, int v, bool diag) {
-  if (bt && v >= 8) {  // v2 kernels (bin-table bucketing only)
-    if (diag)
-      return (v >= 14) ? lab_v2<2, 2, 2, true, 0, 0, 0, -1, true>
-                                  : lab_v2<2, 2, 2, true>;
-    switch (v) {
-      case 9: return lab_v2<2, 3, 0, false>;
-      case 10: return lab_v2<4, 1, 0, false>;
-      case 11: return lab_v2<2, 2, 0, false>;
-      case 12: return lab_v2<2, 2, 2, false, 11, 9, 14>;
-      case 13: return lab_v2<2, 2, 0, false, 11, 9, 14>;
-      case 14: return lab_v2<2, 2, 2, false, 11, 9, 14, -1, true>;
-      case 15: return (const void *)&ingest_v2_kernel<0, 0, 0, false, 1024, V2Plain>;  // (the product's)
-      case 16: return lab_v2<2, 2, 2, false, 11, 9, 14, -1, true, 1>;
-      case 17: return lab_v2<2, 2, 2, false, 11, 9, 14, -1, true, 3>;
-      case 18: return lab_v2<2, 2, 2, false, 11, 9, 14, -1, true, 2>;
-      case 19: return lab_v2<2, 2, 2, false, 11, 9, 14, -1, true, 1, true>;
-      case 20: return (const void *)&ingest_v2_kernel<11, 9, 14, false, 1024, V2Lean>;  // (the product's)
-      case 21: return lab_v2<2, 2, 2, false, 11, 9, 14, -1, true, 1, true, true, false, true>;
-      case 22:
-        return lab_v2<2, 2, 2, false, 11, 9, 14, -1, true, 1, true, true, false, false, true>;
-      case 23: return lab_v2<2, 2, 2, false, 11, 9, 14, -1, true, 3, true, true>;
-      case 24: return lab_v2<2, 2, 2, false, 11, 9, 14, -1, true, 2, true, true>;
-      case 25:  // 15 with 512-thread workgroups (two per CU where the LDS state fits 80 KB)
-        return lab_v2<2, 2, 2, false, 0, 0, 0, -1, true, 0, false, false, false, false, false,
-                                               512>;
-      case 26:  // 25 with the prologue barrier, LDS event counters and the lean hash (variant 20's options)
-        return lab_v2<2, 2, 2, false, 0, 0, 0, -1, true, 1, true, true, false, false, false,
-                                               512>;
-      default: return lab_v2<2, 2, 2, false>;
-    }
-  }
-  if (diag) return bt ? (const void *)&ingest_lds_kernel<1, 4, true, true>
-                      : (const void *)&ingest_lds_kernel<0, 4, true, true>;
-  if (!bt) return (const void *)&ingest_lds_kernel<0, 4, true, false>;
-  switch (v) {
-    case 1: return (const void *)&ingest_lds_kernel<1, 4, false, false>;
-    case 2: return (const void *)&ingest_lds_kernel<1, 2, true, false>;
-    case 3: return (const void *)&ingest_lds_kernel<1, 2, false, false>;
-    case 4: return (const void *)&ingest_lds_kernel<1, 4, true, false, 2>;
-    case 5: return (const void *)&ingest_lds_kernel<1, 4, false, false, 2>;
-    case 6: return (const void *)&ingest_lds_kernel<1, 2, true, false, 2>;
-    case 7: return (const void *)&ingest_lds_kernel<1, 2, false, false, 2>;
-    default: return (const void *)&ingest_lds_kernel<1, 4, true, false>;
-  }
+static const void *small_fn(SmallKernel k, bool diag) {
+  return diag ? (const void *)&ingest_v2_kernel<0, 0, 0, false, 1024, V2Diag> : product_small_fn(k);
 }

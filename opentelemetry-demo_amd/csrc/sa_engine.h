@@ -85,7 +85,7 @@ struct sa_engine {
   } order;
   uint32_t log2cap = 0;
   uint64_t cap = 0;
-  int variant = 0;
+  sa::SmallKernel small_kernel = sa::SmallKernel::Linear;  // Path::Small: the ingest kernel
   int kernel_kind = 0;  // SA_KERNEL_* (spanagg_diag.h): what sa_debug_geometry reports
   uint32_t spl = 4;
   uint32_t G = 0, block = 0, cus = 0;
@@ -107,11 +107,6 @@ struct sa_engine {
     // v2: [G][n_windows << log2cap] per-workgroup ERROR counts (the small
     // exponential tables' kernel keeps them too)
     uint32_t *errslab = nullptr;
-    // small-table kernel with the tail pool (sa::kLdsPoolVariant): per-launch
-    // pool counters [kPoolRing] (launch k zeroes launch k + nsets's)
-    bool pool = false;
-    uint32_t *pool_ring = nullptr;
-    uint32_t pool_seq = 0;
     // sa_ingest_device_many: two instantiated graphs of K launches, used in
     // turn; one is re-pointed at new batches only after its last launch (done)
     struct GraphIngest {
@@ -222,7 +217,7 @@ struct sa_engine {
   std::string err;
 
   bool dense() const { return path == sa::Path::Dense; }
-  bool small_v2() const { return variant >= 8; }  // ingest_v2_kernel: u16 LDS counters, ERROR slabs
+  bool diag() const { return cfg.flags != 0; }  // SA_DIAG_* flags (laboratory build; the product's sa_create refuses them)
 };
 
 inline int fail(sa_engine *e, int code, const std::string &msg) {

@@ -116,23 +116,7 @@ struct IngestParams {
   int32_t l2d_q24;  // log2(div) * 2^24 rounded (expo_index_fast)
   uint32_t xidx;
   XHdr *xslab;
-  // Small-table kernels with the tail pool (POOL): every workgroup owns the
-  // static range [b * wg_chunk, (b + 1) * wg_chunk); spans [pool_base, n)
-  // form pool_n blocks of kPoolSpans that workgroups take from *pool_ctr
-  // (x 64: one wave's claim) once their own range is claimed, so fast
-  // workgroups (and XCDs) finish the slow ones' share of the launch.
-  // pool_next: the counter of the launch nsets ahead (same slab set, so it
-  // starts after this one ends), zeroed here.
-  uint64_t pool_base;
-  uint32_t pool_n;
-  uint32_t *pool_ctr, *pool_next;
 };
-// the tail pool (IngestParams::pool_*): blocks of 8 claim chunks (2 x 128
-// spans each), at most kPoolMaxSteal of them per workgroup (its u16 LDS
-// counters bound the spans of one launch)
-constexpr uint32_t kPoolSpans = 2048;
-constexpr uint32_t kPoolMaxSteal = 8;
-constexpr uint32_t kPoolRing = 8;  // per-launch pool counters per engine
 // One workgroup's exponential-histogram header partial for one key slot
 // (EXPO kernel -> expo_reduce_rescale_kernel): counts, exact ns sum, the
 // largest ~d over positive durations (so the minimum starts from a zeroed
@@ -412,42 +396,11 @@ __host__ __device__ inline uint32_t seq_slot(const ProbeSeq &p, uint32_t i) {
 inline uint32_t max_probe_of(uint32_t log2cap) { return (1u << log2cap) + 4; }
 
 
-// HBM-table path variants (spans per lane, prefetch; 256-thread blocks).  The
-// small-table path has two: 0 = next-tile prefetch, 1 = none (1,024 threads,
-// 4 spans per lane); the block field below is unused by it.
-struct Variant {
-  int spl;
-  bool prefetch;
-  uint32_t block;
-};
-constexpr int kNumVariants = 4;
-constexpr Variant kVariants[kNumVariants] = {{4, false, 1024}, {2, true, 1024}, {4, true, 512},
-                                             {2, false, 1024}};
+// HBM-table kernel (ingest_hbm_kernel): 256 threads, 4 spans per lane per tile
 constexpr uint32_t kHbmBlock = 256;
-// small-table kernels: 0-3 ingest_lds_kernel {4,PF} {4,-} {2,PF} {2,-}, 4-7 the
-// same with nt loads; 8-13 ingest_v2_kernel: 8 generic (nt tile loads), 9 three
-// tiles in flight, 10 four spans per lane, 11 generic (default cache policy),
-// 12 / 13 = 8 / 11 specialised for cap 2048, 17 buckets, HLL p 14; 14 = 12 with
-// dynamic wave chunks; 15 = 14 generic; 16-18 = 14 with OPT 1 / 3 / 2; 19 = 16
-// with the batched end-of-launch write-back (v2_epilogue); 20 = 19 LEAN; 21 =
-// 20 with the TAG key lookup; 22 = 20 with the tail pool (POOL); 23 / 24 = 20
-// with tile claims (OPT 3 / 2: NBUF claims of one wave tile per round); 25 =
-// 15 with 512-thread workgroups; 26 = 25 with variant 20's options (OPT 1,
-// EPI, LEAN): kLdsHalfBlockVariant, the product's choice for a table with a
-// bin table whose LDS state fits a CU twice (two workgroups per CU).
-constexpr int kNumLdsVariants = 27;
-constexpr int kLdsSpl[kNumLdsVariants] = {4, 4, 2, 2, 4, 4, 2, 2, 2, 2, 4, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2};
-constexpr int kLdsHalfBlockVariant = 26;
-constexpr uint32_t lds_variant_block(int v) { return v == 25 || v == 26 ? 512u : 1024u; }
-constexpr int kLdsPoolVariant = 22;
+constexpr int kHbmSpansPerLane = 4;
 // v2 kernels keep u16 LDS counters for a whole launch: spans per workgroup per launch
 constexpr uint32_t kMaxWgSpans = 65532;
-// POOL launches: the static share per workgroup (whole 256-span chunks) leaves
-// room for kPoolMaxSteal stolen blocks under kMaxWgSpans; a launch averages at
-// most kPoolMaxWgSpans per workgroup, so the steal limits cover the pool
-constexpr uint32_t kPoolMaxStatic = (kMaxWgSpans - kPoolMaxSteal * kPoolSpans) / 256 * 256;
-constexpr uint32_t kPoolMaxWgSpans = kPoolMaxStatic + kPoolMaxSteal * kPoolSpans;
-constexpr uint32_t kPoolMinStatic = 32 * 256;  // two fixed chunks per wave before any claim
 constexpr uint32_t kDbgPerWg = 136;  // diagnostic stamps per workgroup: 8 + 16 waves x 8
 // the exponential counting kernel's stamps in the same rows (slots the ingest
 // kernel leaves free): start, prologue done, loop done, end at 4..7; its slab
@@ -456,21 +409,18 @@ constexpr uint32_t kDbgPerWg = 136;  // diagnostic stamps per workgroup: 8 + 16 
 constexpr uint32_t kXcStamp = 4, kXcStampSlab = kDbgPerWg - 1, kXcStampZeroed = kDbgPerWg - 9,
                    kXcStampSelected = kDbgPerWg - 17, kXcStampTail = kDbgPerWg - 25;
 // (kHllQueue, kErrTab, kLdsExtraBytes: sa_path.h)
-constexpr size_t kLdsTagBytesPerSlot = 4;
-constexpr int kLdsTagVariant = 21;  // the only small-table variant with LDS key tags
 
-// launchers (spanagg_kernels.hip)
-hipError_t launch_ingest_small(const IngestParams &P, uint32_t grid, size_t lds_bytes,
-                               hipStream_t s, int variant);
-hipError_t launch_ingest_hbm(const IngestParams &P, uint32_t grid, hipStream_t s, int variant);
+// launchers (spanagg_kernels.hip).  Small tables: the engine's kernel k
+// (sa_path.h), block small_block(k); diag (laboratory build only): the
+// ablation instance in its place, which has Generic1024's geometry.
+hipError_t launch_ingest_small(const IngestParams &P, uint32_t grid, size_t lds_bytes, hipStream_t s, SmallKernel k,
+                               bool diag);
+hipError_t launch_ingest_hbm(const IngestParams &P, uint32_t grid, hipStream_t s);
 hipError_t launch_ingest_part(const IngestParams &P, hipStream_t s);
 hipError_t prepare_ingest_part();
 hipError_t prepare_ingest_small(size_t lds_bytes);
-void ingest_small_node(const IngestParams &P, uint32_t grid, size_t lds_bytes, int variant, void **args,
-                       hipKernelNodeParams *np);
-uint32_t ingest_small_block(bool bt, int variant, uint32_t log2cap, uint32_t nbk, uint32_t p);
-uint32_t ingest_small_blocks_per_cu(bool bt, int variant, uint32_t log2cap, uint32_t nbk, uint32_t p,
-                                    size_t lds_bytes);
+void ingest_small_node(uint32_t grid, size_t lds_bytes, SmallKernel k, void **args, hipKernelNodeParams *np);
+uint32_t ingest_small_blocks_per_cu(SmallKernel k, bool diag, size_t lds_bytes);
 // exponential-histogram engines with an LDS-sized key table: the small-table
 // kernel in EXPO mode (header partials + per-span slots; spanagg_expo.hip
 // reduces and counts)

@@ -10,8 +10,6 @@
 struct LabKnobs {
   // per engine: sa_create takes a fresh reading (lab_for_create) and keeps what
   // it needs in the engine (tools/ switch these between engines of one process)
-  bool variant_set = false;  // SPANAGG_VARIANT: the ingest kernel variant (sa_create clamps it)
-  int variant = 0;
   uint32_t slab_sets = 0;    // SPANAGG_SLAB_SETS: slab sets, 1..4 (0: the default)
   bool xstream = false;      // SPANAGG_XSTREAM=1: the histogram kernels on an engine stream
   bool kmul_set = false;     // SPANAGG_KMUL: the binned path's id multiplier, fixed
@@ -36,7 +34,6 @@ inline bool ab_is(const char *name, bool zero) {  // set, and zero / non-zero as
 }
 inline LabKnobs lab_read() {
   LabKnobs k;
-  if (const char *v = ab_env("SPANAGG_VARIANT")) k.variant_set = true, k.variant = std::atoi(v);
   if (const char *v = ab_env("SPANAGG_SLAB_SETS")) k.slab_sets = (uint32_t)std::max(1, std::min(4, std::atoi(v)));
   k.xstream = ab_is("SPANAGG_XSTREAM", false);
   if (const char *v = ab_env("SPANAGG_KMUL")) k.kmul_set = true, k.kmul = std::strtoull(v, nullptr, 0);

@@ -38,10 +38,10 @@ constexpr uint32_t kPartMaxBk = 17;       // LDS counter row: nbk <= 17 (default
 
 constexpr uint32_t kHllQueue = 2048;  // deferred HLL raises per workgroup (8 B each)
 constexpr uint32_t kErrTab = 1024;    // LDS (window, slot) -> ERROR count table per workgroup (4 B each)
-// ingest_lds_kernel LDS beyond the table: HLL queue + its count + bin table
-// (+ the ERROR table and HLL bounds of the v2 kernels; their TAG forms add
-// cap u32 key tags, see kLdsTagBytes)
-// (+ 64 B: the POOL kernels' map of stolen pool blocks)
+// small-table kernels' LDS beyond the table: HLL queue + its count + bin table
+// (+ the ERROR table and HLL bounds of the v2 kernels)
+// (+ 64 B reserved: no kernel uses them, but the path decision's thresholds
+// and every recorded geometry count them)
 constexpr size_t kLdsExtraBytes = kHllQueue * 8 + 32 + kBins * sizeof(BinEntry) + kErrTab * 4 + kLbMaxSub + 64;
 constexpr size_t kLdsBudget = 144 * 1024;  // small-table path LDS ceiling per workgroup
 
@@ -181,7 +181,7 @@ constexpr bool default_geometry(uint32_t log2cap, uint32_t nbk, uint32_t hll_p) 
   return log2cap == 11 && (nbk + 1) / 2 == 9 && hll_p == 14;
 }
 
-// Which small-table kernel a Small engine runs (spanagg_kernels.hip small_fn):
+// Which small-table kernel a Small engine runs (spanagg_kernels.hip product_small_fn):
 // the linear-threshold kernel for bounds no bin table holds; otherwise the v2
 // kernel -- specialised for the default geometry, generic with 512-thread
 // workgroups where the LDS state fits a CU's 160 KiB twice (two workgroups per
@@ -193,6 +193,12 @@ inline SmallKernel small_kernel(bool has_bins, size_t lds_bytes, uint32_t log2ca
   if (default_geometry(log2cap, nbk, hll_p)) return SmallKernel::Default;
   return 2 * lds_bytes <= (size_t)160 * 1024 ? SmallKernel::Generic512 : SmallKernel::Generic1024;
 }
+// Its workgroup, the spans a lane takes per tile (block x spans = the least a
+// workgroup is given), and whether it is the v2 kernel (u16 LDS counters for a
+// whole launch, per-workgroup ERROR slabs) or the linear-threshold one.
+constexpr uint32_t small_block(SmallKernel k) { return k == SmallKernel::Generic512 ? 512u : 1024u; }
+constexpr uint32_t small_spans_per_lane(SmallKernel k) { return k == SmallKernel::Linear ? 4u : 2u; }
+constexpr bool small_is_v2(SmallKernel k) { return k != SmallKernel::Linear; }
 
 // The small exponential table's kernel: specialised for 2,048 slots and HLL
 // p = 14 (the buckets live in HBM, so their number does not matter).

@@ -17,7 +17,6 @@
 //   * HLL: u8 registers in HBM, read-filtered, CAS-max only when rho grows;
 //   * count-min: u64 cells, atomic add per ERROR span per row.
 #include <algorithm>
-#include <cstdlib>
 
 #include "sa_device.h"
 
@@ -187,36 +186,32 @@ __device__ __forceinline__ uint32_t lds_probe_rest(const unsigned long long *lke
   return kNotFound;
 }
 
-// Small-table path (key table mirrored in LDS), 1,024 threads, S spans per
-// lane per tile.  Per tile:
+// Small-table path (key table mirrored in LDS) for bounds no bin table holds:
+// buckets by linear thresholds, 1,024 threads, 4 spans per lane per tile.
+// Per tile:
 //   1. wait for the tile, compact it to (key, duration, bucket, HLL offset,
 //      rho, window slot) -- the raw 44 B/span registers are then free;
-//   2. S LDS key probes back to back -> key-table slots;
+//   2. 4 LDS key probes back to back -> key-table slots;
 //   3. ERROR spans: one no-return atomic on the exact (window, slot) counter;
-//   4. issue the S HLL register reads;
-//   5. PF: prefetch the next tile into the freed tile registers, then the LDS
+//   4. issue the 4 HLL register reads;
+//   5. prefetch the next tile into the freed tile registers, then the LDS
 //      counter / sum atomics;
 //   6. HLL compare (a counted vmcnt: the prefetch stays in flight); a register
 //      that grows is queued in LDS and raised after the loop, so no returning
 //      global atomic (and its vmcnt(0)) sits in the loop.
-// BK: 1 = bucket by the LDS bin table, 0 = linear thresholds.  DIAG: honour
-// the SA_DIAG_* ablation bits (profiling builds only).
 // LDS: lkeys[cap] u64 | lsum[cap] u64 | lcnt[cap][nw] u32 | hq[kHllQueue] u64 |
-//      hq_n (16 B) | bins[kBins]
-template <int BK, int S, bool PF, bool DIAG, int AUX = 0>
+//      hq_n (16 B)
 __global__ __launch_bounds__(kLdsBlock) void ingest_lds_kernel(IngestParams P) {
+  constexpr int S = 4;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  if (DIAG && P.dbg && threadIdx.x == 0) P.dbg[blockIdx.x * kDbgPerWg + 0] = __builtin_amdgcn_s_memrealtime();
   const uint32_t cap = 1u << P.log2cap;
   const uint32_t nbk = P.nbk;
   const uint32_t nw = (nbk + 1) >> 1;
-  const uint32_t diag = DIAG ? P.diag : 0u;
   unsigned long long *lkeys = reinterpret_cast<unsigned long long *>(smem);
   unsigned long long *lsum = lkeys + cap;
   uint32_t *lcnt = reinterpret_cast<uint32_t *>(lsum + cap);
   uint2 *hq = reinterpret_cast<uint2 *>(lcnt + cap * nw);
   uint32_t *hq_n = reinterpret_cast<uint32_t *>(hq + kHllQueue);
-  BinEntry *lbins = reinterpret_cast<BinEntry *>(hq_n + 4);
 
   uint64_t lo, hi;
   wg_range(P.n, lo, hi);
@@ -225,8 +220,8 @@ __global__ __launch_bounds__(kLdsBlock) void ingest_lds_kernel(IngestParams P) {
   const uint32_t tile = kLdsBlock * S;
   uint32_t off = threadIdx.x * S;
 
-  // Key-table (and bin-table) loads first, then the first tile's loads: the
-  // LDS setup waits only for the keys (vmcnt counts in issue order).
+  // Key-table loads first, then the first tile's loads: the LDS setup waits
+  // only for the keys (vmcnt counts in issue order).
   unsigned long long kv[8];
   const uint32_t per = (cap + kLdsBlock - 1) / kLdsBlock;  // <= 8 for cap <= 8192
 #pragma unroll
@@ -236,10 +231,8 @@ __global__ __launch_bounds__(kLdsBlock) void ingest_lds_kernel(IngestParams P) {
                 ? __hip_atomic_load(&P.gkeys[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
                 : 0ULL;
   }
-  uint4 bv = make_uint4(0, 0, 0, 0);
-  if (BK == 1 && threadIdx.x < kBins * 2) bv = reinterpret_cast<const uint4 *>(P.bintab)[threadIdx.x];
   SpanTile<S> cur;
-  load_tile<S, AUX>(c, off, len, cur);
+  load_tile<S>(c, off, len, cur);
 #pragma unroll
   for (int u = 0; u < 8; ++u) {
     const uint32_t i = threadIdx.x + u * kLdsBlock;
@@ -248,11 +241,9 @@ __global__ __launch_bounds__(kLdsBlock) void ingest_lds_kernel(IngestParams P) {
       lsum[i] = 0;
     }
   }
-  if (BK == 1 && threadIdx.x < kBins * 2) reinterpret_cast<uint4 *>(lbins)[threadIdx.x] = bv;
   for (uint32_t i = threadIdx.x; i < cap * nw; i += kLdsBlock) lcnt[i] = 0;
   if (threadIdx.x == 0) *hq_n = 0;
   __syncthreads();
-  if (DIAG && P.dbg && threadIdx.x == 0) P.dbg[blockIdx.x * kDbgPerWg + 1] = __builtin_amdgcn_s_memrealtime();
 
   LaneStats st{0, 0, 0, 0};
   uint32_t in_epoch = 0;
@@ -267,7 +258,7 @@ __global__ __launch_bounds__(kLdsBlock) void ingest_lds_kernel(IngestParams P) {
       key[j] = valid ? cur.key[j] : 0;
       st.zero_key += (valid && cur.key[j] == 0) ? 1u : 0u;
       dur[j] = cur.e[j] > cur.s[j] ? cur.e[j] - cur.s[j] : 0;
-      const uint32_t bkt = bucket_lds<BK>(dur[j], lbins, P);
+      const uint32_t bkt = bucket_of<-1>(dur[j], P);
       const uint32_t svc = cur.meta[j] & 0xFFFFu;
       const bool svc_ok = svc < P.n_services;
       const uint32_t ws = window_slot(P, cur.e[j]);
@@ -275,10 +266,10 @@ __global__ __launch_bounds__(kLdsBlock) void ingest_lds_kernel(IngestParams P) {
       st.bad_svc += (valid && !svc_ok) ? 1u : 0u;
       st.oor += (valid && svc_ok && !win_ok) ? 1u : 0u;
       const bool sk = valid && svc_ok && win_ok;
-      const uint32_t err = (sk && ((cur.meta[j] >> 19) & 3u) == 2u && !(diag & 4u)) ? 1u : 0u;
+      const uint32_t err = (sk && ((cur.meta[j] >> 19) & 3u) == 2u) ? 1u : 0u;
       uint32_t rho = 0;
       hoff[j] = 0;
-      if (sk && !(diag & 2u)) {
+      if (sk) {
         const uint64_t x = xxh64_16(cur.a[j], cur.b[j]);
         rho = (uint32_t)__clzll((long long)((x << P.p) | (1ULL << (P.p - 1)))) + 1;
         hoff[j] = (((ws * P.n_services + svc) << P.p) + (uint32_t)(x >> (64 - P.p)));
@@ -287,33 +278,25 @@ __global__ __launch_bounds__(kLdsBlock) void ingest_lds_kernel(IngestParams P) {
     }
     // 2. RED lookup: S LDS probes back to back (key no longer needed after)
     uint32_t found[S];
-    if (!(diag & 1u)) {
-      uint32_t sl[S];
-      unsigned long long k0[S];
+    uint32_t sl[S];
+    unsigned long long k0[S];
 #pragma unroll
-      for (int j = 0; j < S; ++j) {
-        sl[j] = probe_seq(key[j], P.log2cap).b1 * 4;
-        k0[j] = lkeys[sl[j]];
-      }
+    for (int j = 0; j < S; ++j) {
+      sl[j] = probe_seq(key[j], P.log2cap).b1 * 4;
+      k0[j] = lkeys[sl[j]];
+    }
 #pragma unroll
-      for (int j = 0; j < S; ++j) {
-        found[j] = kNotFound;
-        if (key[j] != 0) {
-          found[j] = k0[j] == key[j] ? sl[j]
-                     : k0[j] == 0    ? kNotFound
-                                     : lds_probe_rest(lkeys, key[j], P.log2cap, 1, P.max_probe);
-          if (found[j] == kNotFound) {
-            found[j] = g_find_insert(P.gkeys, key[j], P.log2cap, P.max_probe);
-            if (found[j] != kNotFound) lkeys[found[j]] = key[j];
-          }
-          st.dropped += found[j] == kNotFound ? 1u : 0u;
+    for (int j = 0; j < S; ++j) {
+      found[j] = kNotFound;
+      if (key[j] != 0) {
+        found[j] = k0[j] == key[j] ? sl[j]
+                   : k0[j] == 0    ? kNotFound
+                                   : lds_probe_rest(lkeys, key[j], P.log2cap, 1, P.max_probe);
+        if (found[j] == kNotFound) {
+          found[j] = g_find_insert(P.gkeys, key[j], P.log2cap, P.max_probe);
+          if (found[j] != kNotFound) lkeys[found[j]] = key[j];
         }
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < S; ++j) {
-        found[j] = kNotFound;
-        st.dropped += (uint32_t)(((key[j] ^ dur[j] ^ info[j]) & 0xFFFFFFFFFFFFULL) == 0x123456789ABCULL);
+        st.dropped += found[j] == kNotFound ? 1u : 0u;
       }
     }
     // 3. error counts: exact per (window, slot) -- one no-return atomic,
@@ -334,11 +317,9 @@ __global__ __launch_bounds__(kLdsBlock) void ingest_lds_kernel(IngestParams P) {
     for (int j = 0; j < S; ++j)
       hv[j] = *reinterpret_cast<const uint32_t *>(P.hll + (hoff[j] & ~3u));
     // 5. prefetch the next tile
-    if constexpr (PF) {
-      __builtin_amdgcn_sched_barrier(0);
-      load_tile<S, AUX>(c, off + tile, len, cur);
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    __builtin_amdgcn_sched_barrier(0);
+    load_tile<S>(c, off + tile, len, cur);
+    __builtin_amdgcn_sched_barrier(0);
     // 5b. RED update: LDS u16 bucket counter + u64 ns sum
 #pragma unroll
     for (int j = 0; j < S; ++j) {
@@ -358,7 +339,6 @@ __global__ __launch_bounds__(kLdsBlock) void ingest_lds_kernel(IngestParams P) {
         else hll_raise(P.hll + hoff[j], rho);
       }
     }
-    if constexpr (!PF) load_tile<S, AUX>(c, off + tile, len, cur);
     if (++in_epoch == P.epoch_tiles) {  // u16 LDS counters: flush before they can wrap
       __syncthreads();
       flush_lds(P, cap, nw, lsum, lcnt);
@@ -366,21 +346,19 @@ __global__ __launch_bounds__(kLdsBlock) void ingest_lds_kernel(IngestParams P) {
       in_epoch = 0;
     }
   }
-  if (DIAG && P.dbg && threadIdx.x == 0) P.dbg[blockIdx.x * kDbgPerWg + 2] = __builtin_amdgcn_s_memrealtime();
   __syncthreads();
   flush_lds(P, cap, nw, lsum, lcnt);
   const uint32_t nq = *hq_n < kHllQueue ? *hq_n : kHllQueue;
   for (uint32_t i = threadIdx.x; i < nq; i += kLdsBlock) hll_raise(P.hll + hq[i].x, hq[i].y);
-  if (DIAG && P.dbg && threadIdx.x == 0) P.dbg[blockIdx.x * kDbgPerWg + 3] = __builtin_amdgcn_s_memrealtime();
   flush_stats(P, st);
 }
 
 // ---------------------------------------------------------------------------
 // Small-table path, v2.  Same LDS layout and slab flush as ingest_lds_kernel;
 // the span loop is rebuilt for latency tolerance at 16 waves per CU:
-//   * NBUF tiles of S spans per lane in flight per wave (a register ring): a
-//     tile is re-filled right after it is compacted, so every wave keeps
-//     loads outstanding while it computes;
+//   * kTilesInFlight (2) tiles of kSpansPerLane (2) spans per lane in flight
+//     per wave (a register ring): a tile is re-filled right after it is
+//     compacted, so every wave keeps loads outstanding while it computes;
 //   * the key lookup reads the key's two 4-slot buckets from the LDS mirror
 //     (4 x 16-B reads, fixed cost, no probe loop); only keys outside their two
 //     buckets (a few % of a 0.7-load table, none at all after the first
@@ -452,7 +430,7 @@ __device__ __forceinline__ uint32_t wave_find_insert(unsigned long long *lkeys, 
 // Resolves the lanes with `need` one distinct key at a time (lanes sharing a
 // key are resolved together); call with all lanes active.
 __device__ __forceinline__ void cold_lookup_wave(unsigned long long *lkeys, bool need, uint64_t key,
-                                                 uint32_t log2cap, uint32_t &found, uint32_t *ltag = nullptr) {
+                                                 uint32_t log2cap, uint32_t &found) {
   uint64_t m = __ballot(need);
   while (m) {
     const int l = __builtin_ctzll(m);
@@ -460,7 +438,6 @@ __device__ __forceinline__ void cold_lookup_wave(unsigned long long *lkeys, bool
     const uint32_t khi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(key >> 32), l);
     const uint64_t k = ((uint64_t)khi << 32) | klo;
     const uint32_t f = wave_find_insert(lkeys, k, log2cap);
-    if (ltag && f != kNotFound && (threadIdx.x & 63u) == 0) ltag[f] = key_tag(k);  // (the mirror's tag of the slot)
     const bool same = need && key == k;
     found = same ? f : found;
     m &= ~__ballot(same);
@@ -504,22 +481,22 @@ __device__ __forceinline__ bool lds_err_add(uint32_t *etab, uint32_t ek) {
 
 // LC / NWC / PC: table log2 capacity, counter words per slot and HLL precision
 // fixed at compile time for the common geometry (0 = read from P).
-// HAUX >= 0: HLL register reads as buffer loads with that cache policy (gfx950:
-// 1 = sc0, 2 = nt, 16 = sc1); -1 = plain global loads.
-// DYN: inside the workgroup's range, waves claim chunks of NBUF wave-tiles
-// from an LDS counter instead of owning a fixed slice of every workgroup
-// tile, so waves the memory arbiter serves late simply take fewer chunks and
-// all 16 finish together (the fixed split left the 4 youngest waves of every
-// workgroup streaming alone for the last ~25% of the launch).  A grid-wide
-// counter in HBM was tried first: its returning atomic put a vmcnt(0) at the
-// top of every round and ran 3.4x slower.
-// OPT (DYN only): bit 0 = every wave issues its key-table loads before any
-// wave issues tile loads (a workgroup barrier between them), so the LDS setup
-// does not wait behind the other waves' first tiles; bit 1 = claims of one
-// wave tile instead of NBUF (a round takes NBUF claims), halving the work a
-// wave can still hold when its neighbours run out.
-// LEAN: the span hash on 32-bit halves (xxh64_16_h), rho / register index
-// without 64-bit shifts, the register row offset by a 24-bit multiply.
+// Tiles are read with the nt cache policy (streamed once), HLL registers with
+// plain global loads.
+// Inside the workgroup's range, waves claim chunks of kTilesInFlight
+// wave-tiles from an LDS counter instead of owning a fixed slice of every
+// workgroup tile, so waves the memory arbiter serves late simply take fewer
+// chunks and all 16 finish together (the fixed split left the 4 youngest waves
+// of every workgroup streaming alone for the last ~25% of the launch).  A
+// grid-wide counter in HBM was tried first: its returning atomic put a
+// vmcnt(0) at the top of every round and ran 3.4x slower.
+// LEAN: every wave issues its key-table loads before any wave issues tile
+// loads (a workgroup barrier between them), so the LDS setup does not wait
+// behind the other waves' first tiles; rare events in LDS counters and, with a
+// compile-time geometry, the two-phase epilogue (v2_epilogue); the span hash
+// on 32-bit halves (xxh64_16_h), rho / register index without 64-bit shifts,
+// the register row offset by a 24-bit multiply, and the wave-level dedup of
+// the hot series' counter adds.
 // EXPO: exponential-histogram engines (spanagg_expo.hip does the buckets).
 // The RED update becomes per-slot LDS header partials -- count, zero count,
 // ns sum, max of ~d and max d over positive durations (XHdr) -- in the space
@@ -549,28 +526,28 @@ __device__ __forceinline__ uint32_t wave_claim(uint32_t *ctr) {
 //
 // The kernel's template: its geometry (LC = log2 slots, NWC = counter words
 // per slot, PC = HLL precision; 0 = read from P), EXPO, the block size and an
-// option set O (S spans per lane per step, NBUF tiles in flight, AUX cache
-// policy, DYN / OPT / EPI / LEAN above).  The product's two option sets are
-// V2Lean (the default table and every EXPO engine) and V2Plain; the
-// laboratory's switches (DIAG ablations, TAG, POOL, the A/B sets) are defined
-// in lab/small_lab.inc, which only the laboratory build compiles.
-struct V2Plain {  // variant 15: chunk claims only
-  static constexpr int S = 2, NBUF = 2, AUX = 2, HAUX = -1, OPT = 0;
-  static constexpr bool DYN = true, EPI = false, LEAN = false, DIAG = false, TAG = false, POOL = false;
+// option set O (LEAN above; DIAG: honour the SA_DIAG_* ablation bits).  The
+// product's two option sets are V2Lean (the default table, the 512-thread
+// generic kernel and every EXPO engine) and V2Plain (the 1,024-thread generic
+// kernel); the laboratory's ablation set V2Diag is defined in
+// lab/small_lab.inc, which only the laboratory build compiles.
+struct V2Plain {
+  static constexpr bool LEAN = false, DIAG = false;
 };
-struct V2Lean : V2Plain {  // variant 20: + prologue barrier, LDS event counters, lean hash, two-phase epilogue
-  static constexpr int OPT = 1;
-  static constexpr bool EPI = true, LEAN = true;
+struct V2Lean : V2Plain {
+  static constexpr bool LEAN = true;
 };
+constexpr int kSpansPerLane = 2;   // one 16-B load per u64 column per lane and tile
+constexpr int kTilesInFlight = 2;  // a wave's register ring of tiles (= the tiles of one claim)
 template <int LC, int NWC, int PC, bool EXPO, uint32_t BLK, typename O>
 __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
-  constexpr int S = O::S, NBUF = O::NBUF, AUX = O::AUX, HAUX = O::HAUX, OPT = O::OPT;
-  constexpr bool DYN = O::DYN, EPI = O::EPI, LEAN = O::LEAN, DIAG = O::DIAG, TAG = O::TAG, POOL = O::POOL;
+  constexpr int S = kSpansPerLane, NBUF = kTilesInFlight, AUX = 2;  // (AUX 2: nt tile loads)
+  constexpr bool LEAN = O::LEAN, DIAG = O::DIAG;
 #ifndef SPANAGG_AB
-  static_assert(!DIAG && !TAG && !POOL, "laboratory switches: libspanagg_ab.so only");
+  static_assert(!DIAG, "laboratory switch: libspanagg_ab.so only");
 #endif
   static_assert(BLK % 64 == 0 && kErrTab % BLK == 0 && kHllQueue % BLK == 0 && BLK * 4 >= kLbMaxSub, "block size");
-  static_assert(!POOL || (DYN && !(OPT & 2)), "the tail pool extends the chunk claims");
+  static_assert(S == 2, "EXPO stores a lane's two spans as one vector");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   if (P.dbg && threadIdx.x == 0) P.dbg[blockIdx.x * kDbgPerWg + 0] = __builtin_amdgcn_s_memrealtime();
   const uint32_t log2cap = LC ? (uint32_t)LC : P.log2cap;
@@ -585,20 +562,16 @@ __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
   uint32_t *hq_n = reinterpret_cast<uint32_t *>(hq + kHllQueue);
   // the compile-time-geometry epilogue (v2_epilogue) raises from the word each
   // span saw: the queue region holds kQcap (hoff, rho) pairs, then their words
-  constexpr bool kObs = (LC != 0 && NWC != 0 && EPI) || EXPO;
+  constexpr bool kObs = (LC != 0 && NWC != 0 && LEAN) || EXPO;
   constexpr uint32_t kQcap = kObs ? kHllQueue / 2 : kHllQueue;
   static_assert(!kObs || kQcap * 12 <= kHllQueue * 8, "queue region");
   uint32_t *hqv = reinterpret_cast<uint32_t *>(hq + kQcap);
-  uint32_t *lstat = hq_n + 4;  // EPI: [4] event counts (zero key, bad service, out of ring, dropped)
+  uint32_t *lstat = hq_n + 4;  // LEAN: [4] event counts (zero key, bad service, out of ring, dropped)
   BinEntry *lbins = reinterpret_cast<BinEntry *>(hq_n + 8);
   uint32_t *etab = reinterpret_cast<uint32_t *>(lbins + kBins);  // [kErrTab]: (key+1) << 16 | count
   uint8_t *llb = reinterpret_cast<uint8_t *>(etab + kErrTab);       // [kLbMaxSub] HLL lower bounds
-  uint32_t *ltag = reinterpret_cast<uint32_t *>(llb + kLbMaxSub);    // TAG: [cap] key_tag of each slot's key
-  // POOL: [kPoolMaxSteal] the pool block behind this workgroup's k-th stolen
-  // block (0 = not known yet, block + 1, or kPoolDone)
-  uint32_t *pmap = ltag + (TAG ? cap : 0u);
   // EXPO with index records: [cap] each slot's scale when the kernel started
-  int8_t *lsc = reinterpret_cast<int8_t *>(pmap + (POOL ? kPoolMaxSteal : 0u));
+  int8_t *lsc = reinterpret_cast<int8_t *>(llb + kLbMaxSub);
   const bool err_lds = P.errslab != nullptr;
   const bool lb_on = P.lb_n != 0 && !(diag & 2u);
   // EXPO header partials (zeroed with lsum / lcnt): lsum = ns sums
@@ -608,38 +581,32 @@ __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
   uint64_t lo, hi;
   wg_range_p(P, lo, hi);
   const uint32_t len = (uint32_t)(hi - lo);
-  // static: a step covers one workgroup tile (BLK * S spans, lane_off
-  // by thread); DYN: one wave tile (64 * S spans, lane_off by lane) and a
-  // claim is NBUF consecutive wave tiles
-  constexpr uint32_t tile = DYN ? 64 * S : BLK * S;
-  constexpr bool kTileClaims = DYN && (OPT & 2);
-  constexpr uint32_t chunk = kTileClaims ? tile : NBUF * tile;
-  const uint32_t lane_off = (DYN ? (threadIdx.x & 63u) : threadIdx.x) * S;
+  // a step covers one wave tile (64 * S spans, lane_off by lane) and a claim
+  // is NBUF consecutive wave tiles
+  constexpr uint32_t tile = 64 * S;
+  constexpr uint32_t chunk = NBUF * tile;
+  const uint32_t lane_off = (threadIdx.x & 63u) * S;
   constexpr uint32_t kWaves = BLK / 64;
-  const uint32_t n_chunks = DYN ? (len + chunk - 1) / chunk : 0u;
+  const uint32_t n_chunks = (len + chunk - 1) / chunk;
   // wave-uniform by construction; readfirstlane keeps it (and every tile
   // base derived from it) in SGPRs for the buffer descriptors
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   // the first two chunks of every wave are fixed; claims continue after them
   uint32_t c0 = wave, c1 = wave + kWaves;
-  // tile claims: cur[b] / nxt[b] = the tile in buffer b this round / the next
-  // round; the first two rounds are fixed (tile (r * NBUF + b) * kWaves + wave)
-  uint32_t cur[NBUF], nxt[NBUF];
+  // Unused, and kept on purpose: the retired tile-claim loop initialised such
+  // an array here, and without it the compiler orders ~20 scalar prologue
+  // instructions of the three generic instances differently (same
+  // instructions and registers).  It stayed so that the change which removed
+  // that loop left this kernel's device code identical (tools/isa_diff.py);
+  // drop it with the next change that alters the kernel's code anyway.
+  uint32_t cur[NBUF];
 #pragma unroll
-  for (int b = 0; b < NBUF; ++b) {
-    cur[b] = (uint32_t)b * kWaves + wave;
-    nxt[b] = (uint32_t)(NBUF + b) * kWaves + wave;
-  }
-  auto tstart = [&](uint32_t unit, int b) -> uint32_t {  // step b's first span, relative to lo
-    return kTileClaims ? unit * tile : DYN ? unit * chunk + (uint32_t)b * tile : unit + (uint32_t)b * tile;
+  for (int b = 0; b < NBUF; ++b) cur[b] = (uint32_t)b * kWaves + wave;
+  (void)cur;
+  auto tstart = [&](uint32_t c, int b) -> uint32_t {  // step b's first span in chunk c, relative to lo
+    return c * chunk + (uint32_t)b * tile;
   };
-  // spans readable from lo: the workgroup's range, or (POOL) the rest of the
-  // batch, which the workgroup's stolen pool blocks lie in (its own range is
-  // whole 256-span chunks then, so only a pool block at the batch end is short)
-  // (a launch too small for two fixed chunks per wave has no pool: pool_n 0)
-  const bool pool_on = POOL && cold_params().pool_n != 0;
-  const uint32_t lim = pool_on ? (uint32_t)(cold_params().n - lo) : len;
-  auto tremain = [&](uint32_t t) -> uint32_t { return lim > t ? lim - t : 0u; };
+  auto tremain = [&](uint32_t t) -> uint32_t { return len > t ? len - t : 0u; };
 
   // Prologue: key-table loads (16 B per lane, <= 4 per lane for cap <= 8192)
   // and the bin table first, then the first NBUF tiles; the LDS setup then
@@ -662,7 +629,7 @@ __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
     if (P.xidx && SA_XIDX_SCALE(P) && 2 * threadIdx.x < cap) xsc = *reinterpret_cast<const uint16_t *>(P.xscale + 2 * threadIdx.x);
   uint32_t lbw = 0;
   if (lb_on && threadIdx.x * 4 < P.lb_n) lbw = *reinterpret_cast<const uint32_t *>(P.hll_lb + threadIdx.x * 4);
-  if constexpr (DYN && (OPT & 1)) {
+  if constexpr (LEAN) {
     // no wait here (gfx950 barriers do not drain vmcnt): only the issue order
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
@@ -675,7 +642,7 @@ __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
   Pending<S> pend;
 #pragma unroll
   for (int b = 0; b < NBUF; ++b) {
-    const uint32_t t = kTileClaims ? tstart(cur[b], b) : tstart(DYN ? c0 : 0u, b);
+    const uint32_t t = tstart(c0, b);
     load_tile_at<S, AUX>(P, (diag & 16u) ? t % (4 * tile) : lo + t, tremain(t), lane_off, buf[b]);
     if (b == NBUF - 1) {
       uint32_t z;  // a VGPR zero: keeps these vector loads (a uniform address would be s_load)
@@ -690,7 +657,6 @@ __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
     if (u < (int)per && i < cap) {
       reinterpret_cast<ulonglong2 *>(lkeys)[i / 2] = kv[u];
       reinterpret_cast<ulonglong2 *>(lsum)[i / 2] = make_ulonglong2(0, 0);
-      if constexpr (TAG) reinterpret_cast<uint2 *>(ltag)[i / 2] = make_uint2(key_tag(kv[u].x), key_tag(kv[u].y));
     }
   }
   if (threadIdx.x < kBins * 2) reinterpret_cast<uint4 *>(lbins)[threadIdx.x] = bv;
@@ -698,16 +664,13 @@ __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
     *reinterpret_cast<uint4 *>(lcnt + i) = make_uint4(0, 0, 0, 0);
   if (threadIdx.x == 0) {
     hq_n[0] = 0;
-    // DYN: next unclaimed chunk of this workgroup's range, x 64 (see the claims)
-    hq_n[1] = ((kTileClaims ? 2u * NBUF : 2u) * kWaves) << 6;
+    // the next unclaimed chunk of this workgroup's range, x 64 (see wave_claim)
+    hq_n[1] = (2u * kWaves) << 6;
     hq_n[2] = 0;  // HLL updates the lower-bound filter skipped (summed over the waves)
   }
   if (threadIdx.x < 4) lstat[threadIdx.x] = 0;
-  if (POOL && threadIdx.x < kPoolMaxSteal) pmap[threadIdx.x] = 0;
   if constexpr (EXPO)
     if (P.xidx && SA_XIDX_SCALE(P) && 2 * threadIdx.x < cap) *reinterpret_cast<uint16_t *>(lsc + 2 * threadIdx.x) = (uint16_t)xsc;
-  // the pool counter of the launch nsets ahead (it starts after this one ends)
-  if (POOL && blockIdx.x == 0 && threadIdx.x == 0) *cold_params().pool_next = 0;
   for (uint32_t i = threadIdx.x; i < kErrTab; i += BLK) etab[i] = 0;
   // (filter off: the first bound word stays 0, and every span's sub-block
   // index is 0 or 1 below, so no rho can be at or below it)
@@ -729,7 +692,6 @@ __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
     }
   };
   stamp(-1);
-  const __amdgpu_buffer_rsrc_t hll_rsrc = rsrc(P.hll, 0xFFFFFFFFu);
   // the bound's shift as a VGPR operand (31 with the filter off): a loop-long
   // scalar here was one of the kernel's SGPR spills, read back by a
   // v_readlane on every span
@@ -772,12 +734,12 @@ __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
     bool err[S];
 #pragma unroll
     for (int j = 0; j < S; ++j) {
-      const bool valid = lane_off + toff + (uint32_t)j < lim;
+      const bool valid = lane_off + toff + (uint32_t)j < len;
       // 0 past the range (buffer bounds check).  An explicit copy: the key is
       // used after the tile registers are re-filled, and sharing them would
       // make the allocator rotate the tile ring through copies that wait.
       key[j] = copy_u64(T.key[j]);
-      if (!(diag & 128u) && !EPI) n_zero += wave_count(valid && key[j] == 0);
+      if (!(diag & 128u) && !LEAN) n_zero += wave_count(valid && key[j] == 0);
       dur[j] = T.e[j] > T.s[j] ? T.e[j] - T.s[j] : 0;
       bkt[j] = EXPO ? 0u : (diag & 32u) ? (uint32_t)dur[j] & 15u : bucket_lds<1>(dur[j], lbins, P);
       const uint32_t meta = copy_u32(T.meta[j]);  // see key
@@ -786,7 +748,7 @@ __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
       ws[j] = (diag & 64u) ? (uint32_t)(T.e[j] >> 34) & 7u : LEAN ? window_slot_lean(P, T.e[j], wmask_v) : window_slot(P, T.e[j]);
       const bool win_ok = ws[j] != 0xFFFFFFFFu;
       if (!(diag & 128u)) {
-        if constexpr (EPI) {
+        if constexpr (LEAN) {
           // rare events: LDS counters (no wave-uniform accumulators held in
           // scalar registers across the loop)
           const uint32_t ev = (valid && key[j] == 0 ? 1u : 0u) | (valid && !svc_ok ? 2u : 0u) |
@@ -842,9 +804,7 @@ __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
       } else if (DIAG && (diag & 1024u)) {  // diag: no read at all
         hv[j] = 0xFFFFFFFFu;
       } else {
-        hv[j] = HAUX < 0 ? *reinterpret_cast<const uint32_t *>(P.hll + (hoff[j] & ~3u))
-                         : (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(
-                               hll_rsrc, (int)(hoff[j] & ~3u), 0, HAUX < 0 ? 0 : HAUX);
+        hv[j] = *reinterpret_cast<const uint32_t *>(P.hll + (hoff[j] & ~3u));
       }
     }
     // 3. re-fill the tile registers with the tile NBUF steps ahead
@@ -856,12 +816,6 @@ __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
     uint32_t found[S];
     if (!(diag & 1u)) {
       bool need[S];
-#ifdef SPANAGG_AB
-      if constexpr (TAG) {
-#include "lab/v2_tag_lookup.inc"
-      } else
-#endif
-      {
 #pragma unroll
       for (int j = 0; j < S; ++j) {
         const ProbeSeq pr = probe_seq(key[j], log2cap);
@@ -881,14 +835,13 @@ __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
         found[j] = k != 0 ? f : kNotFound;
         need[j] = k != 0 && f == kNotFound;
       }
-      }
       // 5. cold path (wave-uniform): keys outside their two buckets or not yet
       //    in this workgroup's mirror
 #pragma unroll
       for (int j = 0; j < S; ++j) {
         if (__builtin_expect(__ballot(need[j]) != 0, 0)) {
-          cold_lookup_wave(lkeys, need[j], key[j], log2cap, found[j], TAG ? ltag : nullptr);
-          if constexpr (EPI) {
+          cold_lookup_wave(lkeys, need[j], key[j], log2cap, found[j]);
+          if constexpr (LEAN) {
             if (need[j] && found[j] == kNotFound) atomicAdd(&lstat[3], 1u);
           } else {
             n_drop += wave_count(need[j] && found[j] == kNotFound);
@@ -979,7 +932,7 @@ __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
             w = nf ? kSpanRecNoSlot << kIxSlotShift
                    : d == 0 ? (f << kIxSlotShift | kIxZero)
                             : ok ? ixrec_of(f, sc, ix) : (f << kIxSlotShift | kIxLong);
-            if (!nf && d != 0 && !ok && lane_off + toff + (uint32_t)j < lim) P.span_long[lo + toff + lane_off + j] = d;
+            if (!nf && d != 0 && !ok && lane_off + toff + (uint32_t)j < len) P.span_long[lo + toff + lane_off + j] = d;
           }
           xw[j] = w;
         }
@@ -989,36 +942,24 @@ __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
       if (!P.span_rec) {
         const uint32_t i0 = toff + lane_off;
         uint32_t *wp = P.slot_of + lo + i0;
-        if constexpr (S == 2) {
-          if (i0 + 1 < lim) *reinterpret_cast<uint2 *>(wp) = make_uint2(xw[0], xw[1]);
-          else if (i0 < lim) wp[0] = xw[0];
-        } else {
-#pragma unroll
-          for (int j = 0; j < S; ++j)
-            if (i0 + (uint32_t)j < lim) wp[j] = xw[j];
-        }
+        if (i0 + 1 < len) *reinterpret_cast<uint2 *>(wp) = make_uint2(xw[0], xw[1]);
+        else if (i0 < len) wp[0] = xw[0];
       }
       // the lane's span records: one 16-B store for its two spans (two 8-B
       // stores per lane cost the kernel ~24 us per 10 M spans)
       if (P.span_rec) {
         const uint32_t i0 = toff + lane_off;
         unsigned long long *rp = P.span_rec + lo + i0;
-        if constexpr (S == 2) {
-          if (i0 + 1 < lim) {
-            *reinterpret_cast<ulonglong2 *>(rp) =
-                make_ulonglong2(span_rec_of(found[0], dur[0]), span_rec_of(found[1], dur[1]));
-          } else if (i0 < lim) {
-            rp[0] = span_rec_of(found[0], dur[0]);
-          }
-        } else {
-#pragma unroll
-          for (int j = 0; j < S; ++j)
-            if (i0 + (uint32_t)j < lim) rp[j] = span_rec_of(found[j], dur[j]);
+        if (i0 + 1 < len) {
+          *reinterpret_cast<ulonglong2 *>(rp) =
+              make_ulonglong2(span_rec_of(found[0], dur[0]), span_rec_of(found[1], dur[1]));
+        } else if (i0 < len) {
+          rp[0] = span_rec_of(found[0], dur[0]);
         }
         // (durations past the record's field, 52 days or more: in full beside it)
 #pragma unroll
         for (int j = 0; j < S; ++j)
-          if (dur[j] >= kSpanRecDurMask && i0 + (uint32_t)j < lim) P.span_long[lo + i0 + j] = dur[j];
+          if (dur[j] >= kSpanRecDurMask && i0 + (uint32_t)j < len) P.span_long[lo + i0 + j] = dur[j];
       }
     } else if constexpr (LEAN) {
       const uint32_t lane = threadIdx.x & 63u;
@@ -1070,46 +1011,15 @@ __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
   // lanes and does nothing): no exit between the steps of a round, so the
   // register allocator keeps each in-flight tile in one set of registers
   // across the back-edge instead of copying it (a copy waits for the loads).
-  const uint32_t loop_len = (diag & 256u) ? 0u : len;  // diag: prologue/epilogue only
-  if constexpr (kTileClaims) {
-    // NBUF claims per round, each returning while the round runs; claims of a
-    // wave increase, so cur[0] is its smallest outstanding tile
-    while (cur[0] * tile < len) {
-      uint32_t nw_[NBUF];
+  // c0: this round's chunk (its tiles are in buf), c1: the next round's
+  // (prefetched during this round), c2: claimed now for the round after.
+  // The claim returns while the round runs; its result is read at the end.
+  while (c0 < n_chunks) {
+    const uint32_t c2 = wave_claim(&hq_n[1]);
 #pragma unroll
-      for (int b = 0; b < NBUF; ++b) nw_[b] = wave_claim(&hq_n[1]);
-#pragma unroll
-      for (int b = 0; b < NBUF; ++b) step(buf[b], tstart(cur[b], b), tstart(nxt[b], b));
-#pragma unroll
-      for (int b = 0; b < NBUF; ++b) {
-        cur[b] = nxt[b];
-        nxt[b] = nw_[b];
-      }
-    }
-  } else if constexpr (DYN) {
-    // c0: this round's chunk (its tiles are in buf), c1: the next round's
-    // (prefetched during this round), c2: claimed now for the round after.
-    // The claim returns while the round runs; its result is read at the end.
-    // (POOL, the laboratory's tail pool, has its own loop: lab/v2_pool_loop.inc.)
-    if constexpr (!POOL) {
-      while (c0 < n_chunks) {
-        const uint32_t c2 = wave_claim(&hq_n[1]);
-#pragma unroll
-        for (int b = 0; b < NBUF; ++b) step(buf[b], tstart(c0, b), tstart(c1, b));
-        c0 = c1;
-        c1 = c2;
-      }
-    }
-#ifdef SPANAGG_AB
-    if constexpr (POOL) {
-#include "lab/v2_pool_loop.inc"
-    }
-#endif
-  } else {
-    for (uint32_t t0 = 0; t0 < loop_len; t0 += NBUF * tile) {
-#pragma unroll
-      for (int b = 0; b < NBUF; ++b) step(buf[b], t0 + b * tile, t0 + (NBUF + b) * tile);
-    }
+    for (int b = 0; b < NBUF; ++b) step(buf[b], tstart(c0, b), tstart(c1, b));
+    c0 = c1;
+    c1 = c2;
   }
   hll_settle(pend);
   if (hot_slot < cap) {  // the hot series' ns sum: one add per wave
@@ -1128,7 +1038,7 @@ __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
   const uint64_t wave_loop_end = dbg ? __builtin_amdgcn_s_memrealtime() : 0;
   if (dbg && threadIdx.x == 0) dbg[blockIdx.x * kDbgPerWg + 2] = __builtin_amdgcn_s_memrealtime();
   // the two-phase epilogues' loads, before the barrier (v2_epi_pre)
-  constexpr bool kSlabPre = LC != 0 && NWC != 0 && EPI && !EXPO;
+  constexpr bool kSlabPre = LC != 0 && NWC != 0 && LEAN && !EXPO;
   constexpr uint32_t kCapC = 1u << (LC ? LC : 1);
   constexpr int kUpt = kSlabPre ? (int)(kCapC * NWC / 2 / BLK) : 1, kSpt = kSlabPre ? (int)(kCapC / 2 / BLK) : 1;
   EpiPre<kUpt, kSpt> epre;
@@ -1154,7 +1064,7 @@ __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
       }
     }
     epi_raise_and_bound<BLK, kQcap>(cold_params(), hq, hqv, nq, epre.lv);
-  } else if constexpr (LC != 0 && NWC != 0 && EPI) {
+  } else if constexpr (kSlabPre) {
     // compile-time geometry: the two-phase epilogue (words prefetched above)
     v2_epilogue<kUpt, kSpt, BLK, kQcap>(cold_params(), cap, nw, log2cap, lsum, lcnt, etab, err_lds, hq, hqv, nq,
                                         epre);
@@ -1177,7 +1087,7 @@ __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
     for (int i = 0; i < 6 && DIAG; ++i) dbg[blockIdx.x * kDbgPerWg + 8 + (threadIdx.x >> 6) * 8 + i] = seg[i];
     dbg[blockIdx.x * kDbgPerWg + 8 + (threadIdx.x >> 6) * 8 + 6] = wave_loop_end;
   }
-  if constexpr (EPI) {  // (lstat is final: the epilogue follows a workgroup barrier)
+  if constexpr (LEAN) {  // (lstat is final: the epilogue follows a workgroup barrier)
     if (threadIdx.x < 4 && lstat[threadIdx.x]) {
       constexpr uint32_t kIdx[4] = {kStatZeroKey, kStatInvalidService, kStatWindowOOR, kStatDropped};
       atomicAdd(&cold_params().stats[kIdx[threadIdx.x]], (unsigned long long)lstat[threadIdx.x]);
@@ -1198,9 +1108,12 @@ __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
 }
 
 // ---------------------------------------------------------------------------
-// HBM-table path (table larger than LDS): CAS insert + u64 atomics per span.
-template <int NB, int S, bool PF, int BLOCK>
-__global__ __launch_bounds__(BLOCK) void ingest_hbm_kernel(IngestParams P) {
+// HBM-table path (table larger than LDS): CAS insert + u64 atomics per span;
+// 256 threads, 4 spans per lane per tile, no prefetch.  NB >= 0: unrolled for
+// NB non-negative bounds; -1: any bounds.
+template <int NB>
+__global__ __launch_bounds__(kHbmBlock) void ingest_hbm_kernel(IngestParams P) {
+  constexpr int S = kHbmSpansPerLane;
   LaneStats st{0, 0, 0, 0};
   const uint32_t nbk = NB >= 0 ? (uint32_t)NB + 1 : P.nbk;
   const uint32_t stride = row_stride(nbk);
@@ -1208,19 +1121,13 @@ __global__ __launch_bounds__(BLOCK) void ingest_hbm_kernel(IngestParams P) {
   wg_range(P.n, lo, hi);
   const Cols c = make_cols(P, lo, hi);
   const uint32_t len = (uint32_t)(hi - lo);
-  const uint32_t tile = BLOCK * S;
+  const uint32_t tile = kHbmBlock * S;
   uint32_t off = threadIdx.x * S;
   SpanTile<S> cur;
   load_tile<S>(c, off, len, cur);
   for (uint32_t t0 = 0; t0 < len; t0 += tile, off += tile) {
     SketchPre<S> k;
     sketch_pre<S>(P, cur, k, st);
-    SpanTile<S> nxt;
-    if constexpr (PF) {
-      __builtin_amdgcn_sched_barrier(0);
-      load_tile<S>(c, off + tile, len, nxt);
-      __builtin_amdgcn_sched_barrier(0);
-    }
     uint32_t slot[S], bk[S];
     uint64_t dd[S];
 #pragma unroll
@@ -1266,11 +1173,7 @@ __global__ __launch_bounds__(BLOCK) void ingest_hbm_kernel(IngestParams P) {
       }
     }
     sketch_post<S>(P, cur, k, slot);
-    if constexpr (PF) {
-      cur = nxt;
-    } else {
-      load_tile<S>(c, off + tile, len, cur);
-    }
+    load_tile<S>(c, off + tile, len, cur);
   }
   flush_stats(P, st);
 }
@@ -1303,21 +1206,21 @@ __device__ __forceinline__ void direct_red(const IngestParams &P, uint64_t key, 
 #ifndef PART_U
 #define PART_U 4
 #endif
-// STAGE: records go through a kPartStage-record LDS stage per bin and leave
-// as whole chunks (runs are reserved in multiples of kPartStage records, so
-// chunks stay aligned); without it each record is its own 16-B store.
+// Records go through a kPartStage-record LDS stage per bin and leave as whole
+// chunks (runs are reserved in multiples of kPartStage records, so chunks
+// stay aligned).
 #ifndef SA_PART_SKIP_USED
 #define SA_PART_SKIP_USED 1
 #endif
 #ifndef SA_PART_WAVES_EU
 #define SA_PART_WAVES_EU 1  // 8 caps VGPRs at 64: two 1,024-thread workgroups per CU
 #endif
-template <int NB, bool STAGE>
+template <int NB>
 __global__ __launch_bounds__(kPartBlock, SA_PART_WAVES_EU) void part_scatter_kernel(IngestParams P) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint32_t *cur = reinterpret_cast<uint32_t *>(smem);  // phase 1: counts; then next record index
   uint32_t *lim = cur + kPartBins;                      // end of this workgroup's run in the bin
-  uint32_t *scnt = lim + kPartBins;                     // STAGE: records staged per bin
+  uint32_t *scnt = lim + kPartBins;                     // records staged per bin
   ulonglong2 *stage = reinterpret_cast<ulonglong2 *>(scnt + kPartBins);  // [kPartBins][kPartStage]
   unsigned long long *hkey = reinterpret_cast<unsigned long long *>(stage + kPartBins * kPartStage);
   unsigned long long *hsum = hkey + kPartHot;                           // overflow table
@@ -1348,7 +1251,7 @@ __global__ __launch_bounds__(kPartBlock, SA_PART_WAVES_EU) void part_scatter_ker
   __syncthreads();
   // 2. reserve one contiguous run per bin (one returning atomic per bin)
   for (uint32_t b = threadIdx.x; b < kPartBins; b += blockDim.x) {
-    const uint32_t c = STAGE ? (cur[b] + kPartStage - 1) & ~(kPartStage - 1) : cur[b];
+    const uint32_t c = (cur[b] + kPartStage - 1) & ~(kPartStage - 1);
     uint32_t base = 0;
     if (c) base = atomicAdd(&P.part_fill[b], c);
     const uint64_t b0 = (uint64_t)b * P.part_cap;
@@ -1379,7 +1282,7 @@ __global__ __launch_bounds__(kPartBlock, SA_PART_WAVES_EU) void part_scatter_ker
   };
   // 3. every span: stats, sketches, and its record (or the direct path);
   //    U spans per thread with all their loads issued first; rounds are
-  //    workgroup-uniform (STAGE flushes between them)
+  //    workgroup-uniform (the stages are flushed between them)
   constexpr int U = PART_U;
   for (uint64_t r0 = lo; r0 < hi; r0 += (uint64_t)U * blockDim.x) {
    const uint64_t i0 = r0 + threadIdx.x;
@@ -1438,12 +1341,10 @@ __global__ __launch_bounds__(kPartBlock, SA_PART_WAVES_EU) void part_scatter_ker
         direct_red(P, key, d, bk, stride, st);
       } else if (SA_PART_SKIP_USED && cur[b] >= lim[b]) {  // run used up (stays so): no stage, no cur atomic
         spill(key, d, bk);
-      } else if (STAGE) {
+      } else {
         const uint32_t slot = atomicAdd(&scnt[b], 1u);
         if (slot < kPartStage) stage[b * kPartStage + slot] = rec;
         else put(b, rec, d, bk);
-      } else {
-        put(b, rec, d, bk);
       }
     }
     // ERROR spans: the exact per-(window, slot) counter (count-min cells are
@@ -1457,32 +1358,29 @@ __global__ __launch_bounds__(kPartBlock, SA_PART_WAVES_EU) void part_scatter_ker
 #pragma unroll
    for (int u = 0; u < U; ++u)
      if ((CUR[u] & 0xFFu) < RHO[u]) hll_raise(REG[u], RHO[u]);
-   if constexpr (STAGE) {  // full stages leave as one 64-B chunk
-     __syncthreads();
-     for (uint32_t b = threadIdx.x; b < kPartBins; b += blockDim.x) {
-       if (scnt[b] < kPartStage) continue;
-       const uint32_t r = cur[b];
-       cur[b] = r + kPartStage;
-       scnt[b] = 0;
+   // full stages leave as one chunk
+   __syncthreads();
+   for (uint32_t b = threadIdx.x; b < kPartBins; b += blockDim.x) {
+     if (scnt[b] < kPartStage) continue;
+     const uint32_t r = cur[b];
+     cur[b] = r + kPartStage;
+     scnt[b] = 0;
 #pragma unroll
-       for (int j = 0; j < (int)kPartStage; ++j) {
-         const ulonglong2 rec = stage[b * kPartStage + j];
-         if (r + j < lim[b]) P.part_rec[r + j] = rec;
-         else spill(rec.x, rec.y >> 7, (uint32_t)(rec.y & 127u));
-       }
+     for (int j = 0; j < (int)kPartStage; ++j) {
+       const ulonglong2 rec = stage[b * kPartStage + j];
+       if (r + j < lim[b]) P.part_rec[r + j] = rec;
+       else spill(rec.x, rec.y >> 7, (uint32_t)(rec.y & 127u));
      }
-     __syncthreads();
    }
+   __syncthreads();
   }
   // partial stages, then zero records over the run's unused tail (the
   // padding, and the slots of spans that took the direct path)
   __syncthreads();
   for (uint32_t b = threadIdx.x; b < kPartBins; b += blockDim.x) {
-    if constexpr (STAGE) {
-      for (uint32_t j = 0; j < scnt[b]; ++j) {
-        const ulonglong2 rec = stage[b * kPartStage + j];
-        put(b, rec, rec.y >> 7, (uint32_t)(rec.y & 127u));
-      }
+    for (uint32_t j = 0; j < scnt[b]; ++j) {
+      const ulonglong2 rec = stage[b * kPartStage + j];
+      put(b, rec, rec.y >> 7, (uint32_t)(rec.y & 127u));
     }
     for (uint32_t r = cur[b]; r < lim[b]; ++r) P.part_rec[r] = make_ulonglong2(0, 0);
   }
@@ -1836,122 +1734,72 @@ uint32_t grid_for(uint64_t work, uint32_t block, uint32_t cap_blocks) {
   return (uint32_t)g;
 }
 
-// Small-table kernels.  Product build: the v2 kernel specialised for the
-// default geometry (variant 20: 2,048 slots, 17 buckets, HLL p 14, LEAN), the
-// generic v2 kernel with 512-thread workgroups (variant 26, two per CU) for
-// other geometries whose LDS state fits a CU twice and with 1,024 threads
-// (variant 15) for the rest with a bucket bin table, and the
-// linear-threshold kernel for bounds no bin table can hold.
-// The laboratory build (SPANAGG_AB) keeps every variant and the diagnostic
-// (ablation) kernels.
-#ifndef SPANAGG_AB
-static const void *small_fn(bool bt, int v, bool diag) {
-  (void)diag;
-  if (!bt) return (const void *)&ingest_lds_kernel<0, 4, true, false>;
-  if (v == 20) return (const void *)&ingest_v2_kernel<11, 9, 14, false, 1024, V2Lean>;
-  if (v == kLdsHalfBlockVariant) return (const void *)&ingest_v2_kernel<0, 0, 0, false, 512, V2Lean>;
-  return (const void *)&ingest_v2_kernel<0, 0, 0, false, 1024, V2Plain>;
+// The small-table kernels by name (sa_path.h SmallKernel): the v2 kernel
+// specialised for the default geometry (2,048 slots, 17 buckets, HLL p 14),
+// the generic v2 kernel with 512-thread workgroups (two per CU) or 1,024, and
+// the linear-threshold kernel for bounds no bin table can hold.
+// (the lean window quotient of V2Lean needs window_ns < 2^56, which sa_create
+// enforces; SA_OPT_STAMPS engines run the same kernels: the v2 kernels'
+// workgroup and wave-end stamps are written whenever P.dbg is set)
+constexpr SmallKernel kSmallKernels[] = {SmallKernel::Default, SmallKernel::Generic512, SmallKernel::Generic1024,
+                                         SmallKernel::Linear};
+static const void *product_small_fn(SmallKernel k) {
+  switch (k) {
+    case SmallKernel::Default: return (const void *)&ingest_v2_kernel<11, 9, 14, false, 1024, V2Lean>;
+    case SmallKernel::Generic512: return (const void *)&ingest_v2_kernel<0, 0, 0, false, 512, V2Lean>;
+    case SmallKernel::Generic1024: return (const void *)&ingest_v2_kernel<0, 0, 0, false, 1024, V2Plain>;
+    case SmallKernel::Linear: break;
+  }
+  return (const void *)&ingest_lds_kernel;
 }
-constexpr int kSmallFnVariants[] = {15, 20, kLdsHalfBlockVariant};
+#ifndef SPANAGG_AB
+static const void *small_fn(SmallKernel k, bool) { return product_small_fn(k); }
 #else
-// every variant and the diagnostic kernels (tools/ A/B runs)
+// + the ablation instance (tools/ablate.py, tools/stamps.py)
 #include "lab/small_lab.inc"
 #endif
-
-template <int NB>
-static void launch_hbm_nb(const IngestParams &P, uint32_t grid, hipStream_t s, int v) {
-#ifndef SPANAGG_AB
-  (void)v;
-  hipLaunchKernelGGL((ingest_hbm_kernel<NB, 4, false, 256>), dim3(grid), dim3(256), 0, s, P);
-#else
-  switch (v) {
-    case 1: hipLaunchKernelGGL((ingest_hbm_kernel<NB, 2, true, 256>), dim3(grid), dim3(256), 0, s, P); break;
-    case 2: hipLaunchKernelGGL((ingest_hbm_kernel<NB, 4, true, 256>), dim3(grid), dim3(256), 0, s, P); break;
-    case 3: hipLaunchKernelGGL((ingest_hbm_kernel<NB, 2, false, 256>), dim3(grid), dim3(256), 0, s, P); break;
-    default: hipLaunchKernelGGL((ingest_hbm_kernel<NB, 4, false, 256>), dim3(grid), dim3(256), 0, s, P); break;
-  }
-#endif
-}
 
 }  // namespace
 
 hipError_t prepare_ingest_small(size_t lds_bytes) {
-#ifndef SPANAGG_AB
-  for (int bt = 0; bt < 2; ++bt)
-    for (int v : kSmallFnVariants) {
-      hipError_t e = hipFuncSetAttribute(small_fn(bt, v, false), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)lds_bytes);
-      if (e != hipSuccess) return e;
-    }
-#else
-  for (int bt = 0; bt < 2; ++bt)
-    for (int v = 0; v < kNumLdsVariants; ++v)
-      for (int d = 0; d < 2; ++d) {
-        hipError_t e = hipFuncSetAttribute(small_fn(bt, v, d),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return e;
-      }
-#endif
+  for (int diag = 0; diag < 2; ++diag)  // (product build: the same four twice)
+    for (SmallKernel k : kSmallKernels)
+      if (hipError_t e = hipFuncSetAttribute(small_fn(k, diag), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+          e != hipSuccess)
+        return e;
   return hipSuccess;
 }
 
-// the variant that runs for a geometry: the specialised v2 builds are only
-// valid for their compile-time geometry (2,048 slots, 17 buckets, HLL p 14)
-static int small_variant(int variant, uint32_t log2cap, uint32_t nbk, uint32_t p) {
-  if ((variant == 12 || variant == 13 || (variant >= 14 && variant != 25 && variant != 26)) &&
-      !default_geometry(log2cap, nbk, p))
-    variant = variant == 12 ? 8 : variant == 13 ? 11 : 15;
-  return variant;
-}
-// (the linear-threshold kernel, for bounds no bin table holds, is 1,024 threads)
-static uint32_t small_block(bool bt, int variant) { return bt ? lds_variant_block(variant) : kLdsBlock; }
-
-hipError_t launch_ingest_small(const IngestParams &P, uint32_t grid, size_t lds_bytes,
-                               hipStream_t s, int variant) {
-  variant = small_variant(variant, P.log2cap, P.nbk, P.p);
-  // (the lean window quotient of variant 20 needs window_ns < 2^56, which
-  // sa_create enforces; SA_OPT_STAMPS engines keep the production v2 kernels:
-  // their workgroup and wave-end stamps are written whenever P.dbg is set)
-  const bool bt = P.bintab != nullptr;
-  const void *fn = small_fn(bt, variant, P.diag != 0 || (P.dbg != nullptr && variant < 8));
+hipError_t launch_ingest_small(const IngestParams &P, uint32_t grid, size_t lds_bytes, hipStream_t s, SmallKernel k,
+                               bool diag) {
   void *args[] = {const_cast<IngestParams *>(&P)};
-  return hipLaunchKernel(fn, dim3(grid), dim3(small_block(bt, variant)), args, lds_bytes, s);
+  return hipLaunchKernel(small_fn(k, diag), dim3(grid), dim3(small_block(k)), args, lds_bytes, s);
 }
 
 // The same launch as a HIP graph kernel node (sa_ingest_device_many): the
 // kernel, its geometry and `args` (args[0] = &P, owned by the caller, read
 // when the node is added or its parameters set).
-void ingest_small_node(const IngestParams &P, uint32_t grid, size_t lds_bytes, int variant, void **args,
-                       hipKernelNodeParams *np) {
-  variant = small_variant(variant, P.log2cap, P.nbk, P.p);
-  const bool bt = P.bintab != nullptr;
+void ingest_small_node(uint32_t grid, size_t lds_bytes, SmallKernel k, void **args, hipKernelNodeParams *np) {
   *np = hipKernelNodeParams{};
-  np->func = const_cast<void *>(small_fn(bt, variant, P.diag != 0 || (P.dbg != nullptr && variant < 8)));
+  np->func = const_cast<void *>(small_fn(k, false));
   np->gridDim = dim3(grid);
-  np->blockDim = dim3(small_block(bt, variant));
+  np->blockDim = dim3(small_block(k));
   np->sharedMemBytes = (unsigned int)lds_bytes;
   np->kernelParams = args;
   np->extra = nullptr;
 }
 
-uint32_t ingest_small_block(bool bt, int variant, uint32_t log2cap, uint32_t nbk, uint32_t p) {
-  return small_block(bt, small_variant(variant, log2cap, nbk, p));
-}
-
 // workgroups of the small-table kernel resident per CU (registers and LDS);
 // 0 when the runtime cannot tell.  After prepare_ingest_small.
-uint32_t ingest_small_blocks_per_cu(bool bt, int variant, uint32_t log2cap, uint32_t nbk, uint32_t p,
-                                    size_t lds_bytes) {
-  variant = small_variant(variant, log2cap, nbk, p);
+uint32_t ingest_small_blocks_per_cu(SmallKernel k, bool diag, size_t lds_bytes) {
   int n = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, small_fn(bt, variant, false), (int)small_block(bt, variant),
-                                                   lds_bytes) != hipSuccess)
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, small_fn(k, diag), (int)small_block(k), lds_bytes) != hipSuccess)
     return 0;
   return n > 0 ? (uint32_t)n : 0u;
 }
 
 // the EXPO kernel: specialised for the default small table (2,048 slots, HLL
-// p = 14: C2's geometry) like variant 20, generic otherwise
+// p = 14: C2's geometry) like SmallKernel::Default, generic otherwise
 static const void *expo_small_fn(bool spec) {
   return spec ? (const void *)&ingest_v2_kernel<11, 0, 14, true, 1024, V2Lean>
               : (const void *)&ingest_v2_kernel<0, 0, 0, true, 1024, V2Lean>;
@@ -1981,28 +1829,8 @@ hipError_t launch_ingest_expo_small(const IngestParams &P, uint32_t grid, size_t
 }
 
 hipError_t launch_ingest_part(const IngestParams &P, hipStream_t s) {
-#ifdef SPANAGG_AB
-  static const uint32_t max_grid = [] {
-    const char *v = std::getenv("SPANAGG_PART_GRID");  // laboratory knob
-    return v ? (uint32_t)std::max(1, std::atoi(v)) : kPartMaxGrid;
-  }();
-  static const bool stage = [] {
-    const char *v = std::getenv("SPANAGG_PART_STAGE");  // laboratory knob
-    return !(v && std::atoi(v) == 0);
-  }();
-#else
-  constexpr uint32_t max_grid = kPartMaxGrid;
-  constexpr bool stage = true;
-#endif
-  const uint32_t grid = (uint32_t)std::min<uint64_t>(max_grid, (P.n + kPartBlock - 1) / kPartBlock);
-  const bool b16 = bounds16(P.nneg, P.npos);
-#ifdef SPANAGG_AB
-  const void *fn = stage ? (b16 ? (const void *)&part_scatter_kernel<16, true> : (const void *)&part_scatter_kernel<-1, true>)
-                         : (b16 ? (const void *)&part_scatter_kernel<16, false> : (const void *)&part_scatter_kernel<-1, false>);
-#else
-  (void)stage;
-  const void *fn = b16 ? (const void *)&part_scatter_kernel<16, true> : (const void *)&part_scatter_kernel<-1, true>;
-#endif
+  const uint32_t grid = (uint32_t)std::min<uint64_t>(kPartMaxGrid, (P.n + kPartBlock - 1) / kPartBlock);
+  const void *fn = bounds16(P.nneg, P.npos) ? (const void *)&part_scatter_kernel<16> : (const void *)&part_scatter_kernel<-1>;
   void *args[] = {const_cast<IngestParams *>(&P)};
   if (hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(kPartBlock), args, kPartScatterLds, s); e != hipSuccess)
     return e;
@@ -2012,12 +1840,7 @@ hipError_t launch_ingest_part(const IngestParams &P, hipStream_t s) {
 }
 
 hipError_t prepare_ingest_part() {
-#ifdef SPANAGG_AB
-  for (const void *fn : {(const void *)&part_scatter_kernel<16, true>, (const void *)&part_scatter_kernel<-1, true>,
-                         (const void *)&part_scatter_kernel<16, false>, (const void *)&part_scatter_kernel<-1, false>})
-#else
-  for (const void *fn : {(const void *)&part_scatter_kernel<16, true>, (const void *)&part_scatter_kernel<-1, true>})
-#endif
+  for (const void *fn : {(const void *)&part_scatter_kernel<16>, (const void *)&part_scatter_kernel<-1>})
     if (hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPartScatterLds);
         e != hipSuccess)
       return e;
@@ -2025,12 +1848,11 @@ hipError_t prepare_ingest_part() {
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPartLdsBytes);
 }
 
-hipError_t launch_ingest_hbm(const IngestParams &P, uint32_t grid, hipStream_t s, int variant) {
-  if (bounds16(P.nneg, P.npos)) launch_hbm_nb<16>(P, grid, s, variant);
-  else launch_hbm_nb<-1>(P, grid, s, variant);
+hipError_t launch_ingest_hbm(const IngestParams &P, uint32_t grid, hipStream_t s) {
+  if (bounds16(P.nneg, P.npos)) hipLaunchKernelGGL(ingest_hbm_kernel<16>, dim3(grid), dim3(kHbmBlock), 0, s, P);
+  else hipLaunchKernelGGL(ingest_hbm_kernel<-1>, dim3(grid), dim3(kHbmBlock), 0, s, P);
   return hipGetLastError();
 }
-
 
 hipError_t launch_reduce_slabs(uint32_t *slab_cnt, unsigned long long *slab_sum,
                                unsigned long long *gcounts, uint32_t G, uint64_t cap,

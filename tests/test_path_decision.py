@@ -115,8 +115,16 @@ int main() {
                          : sa::bounds16(h.nneg, h.npos)   ? "bounds16"
                                                           : "bounds_generic";
     const sa::LbGeom lb = sa::hll_filter_geometry(c);
-    std::printf("%s %u %zu %s %u %u %d %u\n", names[(int)pc.path], log2cap, pc.lds_bytes, kernel, lb.shift, lb.n,
-                (int)(sa::lds_table(pc.path) && sa::error_table(c.n_windows, cap)), h.nneg);
+    // the small-table kernel's workgroup and spans per lane (0 0: not a Small engine)
+    unsigned block = 0, spl = 0, v2 = 0;
+    if (pc.path == sa::Path::Small) {
+      const sa::SmallKernel k = sa::small_kernel(h.has_bins, pc.lds_bytes, log2cap, h.nbk, c.hll_p);
+      block = sa::small_block(k);
+      spl = sa::small_spans_per_lane(k);
+      v2 = sa::small_is_v2(k);
+    }
+    std::printf("%s %u %zu %s %u %u %d %u %u %u %u\n", names[(int)pc.path], log2cap, pc.lds_bytes, kernel, lb.shift, lb.n,
+                (int)(sa::lds_table(pc.path) && sa::error_table(c.n_windows, cap)), h.nneg, block, spl, v2);
   }
   return 0;
 }
@@ -177,3 +185,11 @@ def _assert_rows(rows, got):
         if r["lds"]:
             assert int(g[2]) == r["lds"], (name, g)
         assert int(g[7]) == sum(b < 0 for b in r["cfg"].get("bounds", DEFAULT)), (name, g)
+        # small tables (geometry_util.assert_geometry's rule on the GPU): 512-thread workgroups for
+        # small_512, 1,024 otherwise; 4 spans per lane for the linear-threshold kernel, 2 for the v2 kernels
+        if r["path"] == "Small":
+            linear = r["kernel"] == "small_linear"
+            assert int(g[8]) == (512 if r["kernel"] == "small_512" else 1024), (name, g)
+            assert (int(g[9]), int(g[10])) == ((4, 0) if linear else (2, 1)), (name, g)
+        else:
+            assert (int(g[8]), int(g[9]), int(g[10])) == (0, 0, 0), (name, g)

@@ -11,7 +11,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "opentelemetry-demo_amd"))
-# the laboratory build (variants, ablation flags): make -C opentelemetry-demo_amd ab
+# the laboratory build (ablation flags, environment knobs): make -C opentelemetry-demo_amd ab
 os.environ.setdefault("SPANAGG_LIB", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                                                   "opentelemetry-demo_amd", "spanagg", "libspanagg_ab.so"))
 
@@ -79,9 +79,7 @@ def main():
     stream = torch.cuda.Stream(dev)
     torch.cuda.set_stream(stream)
     engines = {}
-    base_variant = os.environ.get("SPANAGG_VARIANT", "0")
-    os.environ["SPANAGG_VARIANT"] = os.environ.get("ABL_BASE", base_variant)
-    if os.environ.get("ABL_NO_DIAG"):  # structure variants only
+    if os.environ.get("ABL_NO_DIAG"):  # ABL_ENVS / ABL_KCAPS engines only
         VARIANTS.clear()
     if os.environ.get("ABL_FLAGS"):  # explicit set: "name:flags,name:flags"
         VARIANTS.clear()
@@ -94,13 +92,6 @@ def main():
         e = Engine(Config(n_services=wl.n_services, n_windows=16, flags=fl, key_capacity=kcap))
         e.window_advance(wl.first_window)
         engines[name] = e
-    # kernel-structure variants (sa_internal.h kVariants), full work
-    for v in [int(x) for x in os.environ.get("ABL_VARS", "0,8,11,12").split(",") if x]:
-        os.environ["SPANAGG_VARIANT"] = str(v)
-        e = Engine(Config(n_services=wl.n_services, n_windows=16, key_capacity=kcap))
-        e.window_advance(wl.first_window)
-        engines[f"variant{v}"] = e
-    os.environ["SPANAGG_VARIANT"] = base_variant
     # engine-creation environment variants: "name:VAR=v;VAR2=v,name2:VAR=v"
     for spec in [x for x in os.environ.get("ABL_ENVS", "").split(",") if x]:
         name, kv = spec.split(":", 1)

@@ -10,9 +10,8 @@
 #   rehearse_<n>     bench.py's n-rank path (torch.distributed.run) with every
 #                    rank on this one GPU and gloo collectives (a rehearsal)
 #   bench_<wl>       a short bench of one workload (c2, c4, c4zipf), no baselines
-#   abvar_<a>_<b>..  C2 bench of laboratory-build kernel variants a, b, ... (3 rounds)
 #   streams_<wl>     bench of <wl> with 1 and with 2 launch streams (2 rounds)
-#   labtests_<v>     the small-table parity suites on laboratory-build variant v
+#   labtests         the small-table parity suites on the laboratory build
 #   libab_<wl>_<name>  bench of <wl> on the product library and on spanagg/lib<name>.so (3 rounds)
 #   btpair_<wl>      bench of <wl> with binned aggregates in pairs / one per launch (3 rounds)
 #   btagg_<wl>       bench of <wl> with 512- and 1,024-thread aggregate workgroups (2 rounds)
@@ -27,7 +26,7 @@
 #   labtrace_<wl>_<VAR=v>  rocprofv3 trace of a 100-step bench of <wl> on the laboratory build with VAR=v
 #   btpipe_<wl>      bench of <wl> with the binned launch pipeline on and off (2 rounds)
 #   ablate_<wl>      tools/ablate.py over the ABL_FLAGS / ABL_ENVS variant set for <wl>
-#   c2stamps         tools/stamps.py: per-workgroup phases of the C2 kernel (STAMP_VARS variants)
+#   c2stamps         tools/stamps.py: per-workgroup phases of the C2 kernel (STAMP_SETS flag sets)
 #   xcstamps[_<d>]   tools/xc_stamps.py: c2expo counting-kernel phases (_d: laboratory, SPANAGG_XC_DIAG=d)
 #   stamps_<wl>      tools/bt_stamps.py: per-workgroup phase timeline (c4, c4zipf)
 #   sweep            C2 kernel time vs batch size (SIZES="1000000 5000000 ...")
@@ -66,7 +65,7 @@ for step in "$@"; do
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
     sweep) for N in ${SIZES:-1000000 2500000 5000000 10000000 15000000}; do
         run "sweep_n$N" 200 python bench.py --sub "" --spans "$N" --steps 30 --warmup 3 $BQ; done ;;
-    c2stamps) STAMP_SETS=${STAMP_SETS:-full} STAMP_VARS=${STAMP_VARS:-20,21} run c2stamps 300 python tools/stamps.py ;;
+    c2stamps) STAMP_SETS=${STAMP_SETS:-full} run c2stamps 300 python tools/stamps.py ;;
     stamps_*) wl=${step#stamps_}; WL=$wl run "stamps_$wl" 300 python tools/bt_stamps.py ;;
     tests) run tests 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread ;;
     tests:*) f=${step#tests:}; run "tests_$(basename "$f" .py)" 600 python -u -m pytest "$f" -m gpu -x -v --timeout 300 --timeout-method thread ;;
@@ -97,18 +96,6 @@ for step in "$@"; do
     hostc4_*) t=${step#hostc4_}; run "hostc4_t$t" 200 node --max-old-space-size=16000 host/node/test/host_rate.js 2000000 --gpu --threads "$t" --batch 128 --highcard ;;
     host_*) t=${step#host_}; run "host_t$t" 200 node --max-old-space-size=16000 host/node/test/host_rate.js 2000000 --gpu --threads "$t" --batch 128 ;;
     bench_*) wl=${step#bench_}; run "bench_$wl" 300 python bench.py --workload "$wl" --sub "" --steps 20 $BQ ;;
-    abvar_*) vs=${step#abvar_}  # A/B of small-table kernel variants (laboratory build), rounds interleaved
-      for r in 1 2 3; do for v in ${vs//_/ }; do
-        SPANAGG_LIB=$ROOTDIR/opentelemetry-demo_amd/spanagg/libspanagg_ab.so SPANAGG_VARIANT=$v \
-          run "abvar_v${v}_r$r" 200 python bench.py --workload c2 --sub "" --steps 50 --soak-s 0 --no-filter-off $BQ
-      done; done ;;
-    abhalf_*) rest=${step#abhalf_}; nps=${rest%%_*}; vs=${rest#*_}; [ "$vs" = "$rest" ] && vs=15_25
-      # small-table variants (default 15 against 25, 512-thread workgroups) on a C2 vocabulary of 20 x nps names
-      for r in 1 2 3; do for v in ${vs//_/ }; do
-        SPANAGG_LIB=$ROOTDIR/opentelemetry-demo_amd/spanagg/libspanagg_ab.so SPANAGG_VARIANT=$v \
-          run "abhalf${nps}_v${v}_r$r" 200 python bench.py --workload c2 --sub "" --steps 50 --soak-s 0 --no-filter-off \
-          --names-per-service "$nps" $BQ
-      done; done ;;
     btpipe_*) wl=${step#btpipe_}  # the binned launch pipeline on / off (laboratory build), rounds interleaved
       for r in 1 2; do for pp in 1 0; do
         SPANAGG_LIB=$ROOTDIR/opentelemetry-demo_amd/spanagg/libspanagg_ab.so SPANAGG_BT_PIPE=$pp \
@@ -181,15 +168,15 @@ for step in "$@"; do
         SPANAGG_LIB=$ROOTDIR/opentelemetry-demo_amd/spanagg/libspanagg_ab.so SPANAGG_EV_SYS=$es \
           run "evscope_${wl}_sys${es}_r$r" 200 python bench.py --workload "$wl" --sub "" --steps 50 --soak-s 0 --no-filter-off $BQ
       done; done ;;
-    labtests_*) v=${step#labtests_}  # small-table parity suites on a laboratory-build variant
-      SPANAGG_LIB=$ROOTDIR/opentelemetry-demo_amd/spanagg/libspanagg_ab.so SPANAGG_VARIANT=$v \
-        run "labtests_v$v" 600 python -u -m pytest tests/test_gpu_parity.py tests/test_c5_windows.py tests/test_gpu_churn.py \
+    labtests)  # small-table parity suites on the laboratory build
+      SPANAGG_LIB=$ROOTDIR/opentelemetry-demo_amd/spanagg/libspanagg_ab.so \
+        run labtests 600 python -u -m pytest tests/test_gpu_parity.py tests/test_c5_windows.py tests/test_gpu_churn.py \
         "tests/test_gpu_regime.py::test_c2_bench_regime_40_variants_bit_exact" -m gpu -x -v --timeout 300 --timeout-method thread ;;
     streams_*) wl=${step#streams_}  # one launch stream against two, rounds interleaved
       for r in 1 2; do for n in 1 2; do
         run "streams_${wl}_s${n}_r$r" 200 python bench.py --workload "$wl" --sub "" --steps 50 --streams $n --soak-s 0 --no-filter-off $BQ
       done; done ;;
-    ablate_*) wl=${step#ablate_}; ABL_WORKLOAD=$wl ABL_VARS=${ABL_VARS:-} run "ablate_$wl" 400 python tools/ablate.py ;;
+    ablate_*) wl=${step#ablate_}; ABL_WORKLOAD=$wl run "ablate_$wl" 400 python tools/ablate.py ;;
     ptrace_*) wl=${step#ptrace_}  # the rocprofv3 summary the bench line's kernel_ms is checked against:
       # a long timed region so the cold and settling launches weigh little in the average
       (cd /tmp && run "ptrace_$wl" 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/ptrace_$wl" -o run \

@@ -24,6 +24,23 @@ RENAMED = {
         "_ZN2sa12_GLOBAL__N_118bt_scatter2_kernelINS0_8BtHashedELi0EEEvNS_12IngestParamsE",
     "_ZN2sa12_GLOBAL__N_117dn_scatter_kernelENS_12IngestParamsE":
         "_ZN2sa12_GLOBAL__N_118bt_scatter2_kernelINS0_7BtDenseELi0EEEvNS_12IngestParamsE",
+    # ingest kernels without their retired template parameters
+    "_ZN2sa12_GLOBAL__N_117ingest_lds_kernelILi0ELi4ELb1ELb0ELi0EEEvNS_12IngestParamsE":
+        "_ZN2sa12_GLOBAL__N_117ingest_lds_kernelENS_12IngestParamsE",
+    "_ZN2sa12_GLOBAL__N_117ingest_hbm_kernelILi16ELi4ELb0ELi256EEEvNS_12IngestParamsE":
+        "_ZN2sa12_GLOBAL__N_117ingest_hbm_kernelILi16EEEvNS_12IngestParamsE",
+    "_ZN2sa12_GLOBAL__N_117ingest_hbm_kernelILin1ELi4ELb0ELi256EEEvNS_12IngestParamsE":
+        "_ZN2sa12_GLOBAL__N_117ingest_hbm_kernelILin1EEEvNS_12IngestParamsE",
+    "_ZN2sa12_GLOBAL__N_119part_scatter_kernelILi16ELb1EEEvNS_12IngestParamsE":
+        "_ZN2sa12_GLOBAL__N_119part_scatter_kernelILi16EEEvNS_12IngestParamsE",
+    "_ZN2sa12_GLOBAL__N_119part_scatter_kernelILin1ELb1EEEvNS_12IngestParamsE":
+        "_ZN2sa12_GLOBAL__N_119part_scatter_kernelILin1EEEvNS_12IngestParamsE",
+    # (the laboratory build's small-table ablation instance: LabV2<...> -> V2Diag)
+    "_ZN2sa12_GLOBAL__N_116ingest_v2_kernelILi0ELi0ELi0ELb0ELj1024ENS0_5LabV2ILi2ELi2ELi2ELb1ELin1ELb1ELi0ELb0ELb0ELb0ELb0EEEEEvNS_12IngestParamsE":
+        "_ZN2sa12_GLOBAL__N_116ingest_v2_kernelILi0ELi0ELi0ELb0ELj1024ENS0_6V2DiagEEEvNS_12IngestParamsE",
+    # (the laboratory build now takes the 512-thread kernel from the product's option set: LabV2<...> -> V2Lean)
+    "_ZN2sa12_GLOBAL__N_116ingest_v2_kernelILi0ELi0ELi0ELb0ELj512ENS0_5LabV2ILi2ELi2ELi2ELb0ELin1ELb1ELi1ELb1ELb1ELb0ELb0EEEEEvNS_12IngestParamsE":
+        "_ZN2sa12_GLOBAL__N_116ingest_v2_kernelILi0ELi0ELi0ELb0ELj512ENS0_6V2LeanEEEvNS_12IngestParamsE",
 }
 # (the laboratory build's ablation instances: <MODE> -> <BtHashed, MODE>)
 for _m in (1, 2, 3, 4, 8, 16, 32, 64):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Profiling driver: N ingest launches of the C2 10M-span batch (device-resident)
-with the library / variant selected by SPANAGG_LIB / SPANAGG_VARIANT.  Every
+with the library selected by SPANAGG_LIB (PROF_FLAGS: the laboratory build).  Every
 launch aggregates a distinct trace-id variant of the batch (bench.py's
 trace_variants; PROF_FRESH=0: the same trace ids every launch), so the last
 launches of a long run are in the regime bench.py times."""
@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "opentelemetry-demo_amd"))
 sys.path.insert(0, ROOT)
 flags = int(os.environ.get("PROF_FLAGS", 0))
-if flags or os.environ.get("SPANAGG_VARIANT"):  # ablations and variants: the laboratory build
+if flags:  # ablations: the laboratory build
     os.environ.setdefault("SPANAGG_LIB", os.path.join(ROOT, "opentelemetry-demo_amd", "spanagg", "libspanagg_ab.so"))
 
 import numpy as np  # noqa: E402

@@ -6,7 +6,7 @@ import json
 import os
 import sys
 
-# the laboratory build (variants, ablation flags): make -C opentelemetry-demo_amd ab
+# the laboratory build (ablation flags): make -C opentelemetry-demo_amd ab
 os.environ.setdefault("SPANAGG_LIB", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                                                   "opentelemetry-demo_amd", "spanagg", "libspanagg_ab.so"))
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -58,17 +58,16 @@ def main():
     out = {}
     for name, fl in [x for x in (("full", 0), ("loads_only", 15), ("no_sketch", 6))
                      if x[0] in os.environ.get("STAMP_SETS", "full,loads_only,no_sketch").split(",")]:
-        for v in [int(x) for x in os.environ.get("STAMP_VARS", "0,8").split(",")]:
-            os.environ["SPANAGG_VARIANT"] = str(v)
-            with Engine(Config(n_services=wl.n_services, n_windows=16, flags=fl, options=_lib.OPT_STAMPS)) as e:
-                e.window_advance(wl.first_window)
-                for i in range(int(os.environ.get("STAMP_LAUNCHES", "24"))):
-                    # a fresh trace-id variant per launch (as bench.py), so HLL raises do not idle
-                    c = list(cols)
-                    c[3] = cols[3] ^ (0x5DEECE66D * (i + 1))
-                    e.ingest_device(*c, n=n, stream=s.cuda_stream)
-                torch.cuda.synchronize()
-                out[f"{name}/v{v}"] = timeline(e)
+        # (flags 0: the product's kernel for the config; flags set: the ablation instance)
+        with Engine(Config(n_services=wl.n_services, n_windows=16, flags=fl, options=_lib.OPT_STAMPS)) as e:
+            e.window_advance(wl.first_window)
+            for i in range(int(os.environ.get("STAMP_LAUNCHES", "24"))):
+                # a fresh trace-id variant per launch (as bench.py), so HLL raises do not idle
+                c = list(cols)
+                c[3] = cols[3] ^ (0x5DEECE66D * (i + 1))
+                e.ingest_device(*c, n=n, stream=s.cuda_stream)
+            torch.cuda.synchronize()
+            out[name] = timeline(e)
     print(json.dumps(out, indent=1))
 
 
