@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "sa_path.h"  // constants the path decision shares: BinEntry, kBins, kLdsExtraBytes, ...
+#include "sa_probe.h"  // the key tables' probe sequences: probe_seq, seq_slot, bt_seq, bt_pos, part_bin, ...
 
 namespace sa {
 
@@ -253,7 +254,7 @@ constexpr uint64_t kPartMaxCap = kPartMaxSpans / kPartBins * 5 / 4 + 64;  // a m
 // a bin holds < 2^16 records, so its LDS bucket counters are u16 pairs
 static_assert(kPartMaxCap < 65536, "u16 LDS counters");
 constexpr uint32_t kPartWords = (kPartMaxBk + 1) / 2;
-__host__ __device__ inline uint32_t part_bin(uint64_t key) { return (uint32_t)(key >> (64 - kPartBinBits)); }
+// (part_bin: sa_probe.h)
 constexpr size_t kPartLdsBytes = (size_t)kPartSlots * (16 + 4 * kPartWords);  // 52 KiB at 1,024 slots
 // scatter: cur, lim, stage counts (u32 per bin) + a 4-record stage per bin
 // scatter overflow table: spans whose bin run is full are pre-aggregated per
@@ -282,38 +283,10 @@ __host__ __device__ inline uint32_t row_count_cell(uint32_t b) {
 __host__ __device__ inline uint32_t row_sum_cell(uint32_t b) { return b / kSegBuckets * 8; }
 
 // ---------------------------------------------------------------------------
-// Binned key table (high-cardinality path, spanagg_binned.hip).
-// The table of cap = 2^log2cap slots is split into kPartBins bins of
-// SB = 2^log2sb slots: a key lives in the bin given by the top kPartBinBits
-// bits of m = key * kmul (kmul odd, so the map is a bijection and 0 stays the
-// EMPTY marker).  Within the bin the sub-table is buckets of 4 slots with two
-// choices, as the small table (probe_seq): positions 0-3 are bucket b1,
-// then bucket b2 and the buckets after it in order (wrapping inside the bin),
-// so a lookup is two 32-B bucket reads for nearly every key.  One aggregate
-// workgroup per bin mirrors the whole sub-table in LDS at the same positions,
-// so the bin's keys and counter rows are read and written as one contiguous
-// block.
-constexpr uint32_t kBinShift = 64 - kPartBinBits;          // bin = m >> kBinShift
+// Binned key table (high-cardinality path, spanagg_binned.hip): its layout and
+// probe sequence (kBinShift, bt_seq, bt_pos, bt_probe_max, bt_slot) are in
+// sa_probe.h.
 constexpr uint64_t kBinRest = (1ULL << kBinShift) - 1;     // m's bits below the bin
-struct BtSeq {
-  uint32_t b1, b2, nbmask;
-};
-__host__ __device__ inline BtSeq bt_seq(uint64_t m, uint32_t log2sb) {
-  const uint32_t h1 = ((uint32_t)m ^ (uint32_t)(m >> 29)) * 0x9E3779B1u;
-  const uint32_t h2 = (h1 ^ (h1 >> 16)) * 0x85EBCA6Bu;
-  const uint32_t sh = 34 - log2sb;  // top (log2sb - 2) bits
-  return BtSeq{h1 >> sh, h2 >> sh, (1u << (log2sb - 2)) - 1};
-}
-// in-bin slot of probe position i (i < bt_probe_max: every slot is reached)
-__host__ __device__ inline uint32_t bt_pos(const BtSeq &q, uint32_t i) {
-  if (i < 4) return q.b1 * 4 + i;
-  const uint32_t r = i - 4;
-  return ((q.b2 + (r >> 2)) & q.nbmask) * 4 + (r & 3);
-}
-__host__ __device__ inline uint32_t bt_probe_max(uint32_t log2sb) { return (1u << log2sb) + 4; }
-__host__ __device__ inline uint32_t bt_slot(uint64_t m, uint32_t log2sb, uint32_t i) {
-  return ((uint32_t)(m >> kBinShift) << log2sb) | bt_pos(bt_seq(m, log2sb), i);
-}
 // Counter rows of the binned path: 32 B per key slot, the u64 ns sum then one
 // u8 count per bucket (bytes 8 .. 8 + nbk), so two rows share a 64-B half
 // line and the aggregate's row read-modify-write moves 32 B per touched key.
@@ -369,32 +342,8 @@ struct RowGeom {
   unsigned long long *dropped;
 };
 
-// Key-table layout: cap = 2^log2cap slots in buckets of 4 (log2cap in 4..31).
-// A key's probe sequence is its first-choice bucket b1, then its second-choice
-// bucket b2, then the buckets after b2 in order (every slot within cap + 4
-// positions).  Inserts CAS into the first empty slot of the sequence and slots
-// never empty again, so concurrent inserts of one key meet at the same slot.
-// Two choices keep 97-99 % of a ~0.7-load table's keys in b1/b2, so the LDS
-// lookup of the ingest kernel is two fixed 32-B bucket reads with no probe
-// loop (ids are xxh64 outputs from the host; any bits are usable).
-struct ProbeSeq {
-  uint32_t b1, b2, nbmask;
-};
-__host__ __device__ inline ProbeSeq probe_seq(uint64_t key, uint32_t log2cap) {
-  const uint32_t h1 = ((uint32_t)key ^ (uint32_t)(key >> 32)) * 0x9E3779B1u;
-  // second choice from a 24-bit multiply (v_mul_u32_u24, full rate; a 32-bit
-  // multiply is quarter rate): the top bits of its low word mix all 24 inputs
-  const uint32_t h2 = ((h1 ^ (h1 >> 16)) & 0xFFFFFFu) * 0x85EBCAu;
-  const uint32_t sh = 34 - log2cap;  // top (log2cap - 2) bits
-  return ProbeSeq{h1 >> sh, h2 >> sh, (1u << (log2cap - 2)) - 1};
-}
-__host__ __device__ inline uint32_t seq_slot(const ProbeSeq &p, uint32_t i) {
-  if (i < 4) return p.b1 * 4 + i;
-  const uint32_t q = i - 4;
-  return ((p.b2 + (q >> 2)) & p.nbmask) * 4 + (q & 3);
-}
-inline uint32_t max_probe_of(uint32_t log2cap) { return (1u << log2cap) + 4; }
-
+// (the key table's layout and probe sequence -- ProbeSeq, probe_seq, seq_slot,
+// max_probe_of: sa_probe.h)
 
 // HBM-table kernel (ingest_hbm_kernel): 256 threads, 4 spans per lane per tile
 constexpr uint32_t kHbmBlock = 256;
