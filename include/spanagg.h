@@ -18,6 +18,7 @@
  *   Shutdown                                        sa_destroy
  *   (new) per-service HLL + error count-min         sa_window_read / sa_window_advance
  *   (new) the same over a span of windows           sa_window_range (merged on the device)
+ *   (new) every trailing span of a window series    sa_window_series (one pass over the ring)
  *
  * Boundary rules (mirroring the connector's contracts):
  *  - Ownership: batches are borrowed for the duration of the call (page-locked
@@ -333,6 +334,42 @@ typedef struct {
 int sa_window_range(sa_engine *e, uint64_t first, uint64_t last, const uint64_t *keys,
                     uint64_t n_keys, uint32_t flags, sa_range_result **out);
 void sa_range_result_free(sa_range_result *r);
+
+/* ---- sliding series over the window ring ----
+ * A detector's time series in one call: for every window t = first..last the
+ * answers of sa_window_range over the trailing span t-width+1 .. t ("the last
+ * 5 minutes, evaluated every 10 s").  The ring is read a constant number of
+ * times whatever the width, and only the answers cross the bus. */
+typedef struct {
+    uint64_t first_window, last_window;  /* outputs t = first..last, inclusive */
+    uint32_t width, n_out;               /* output t covers windows t-width+1 .. t; n_out = last-first+1 */
+    uint32_t n_services, hll_p;
+    const uint32_t *hll_hist;    /* [n_out][n_services][SA_HLL_HIST_BINS], every row sums to 2^hll_p */
+    const double   *distinct;    /* [n_out][n_services] sa_hll_estimate_hist(row, hll_p) */
+    const uint64_t *error_spans; /* [n_out] sum of count-min row 0 over the covered windows:
+                                    the ERROR spans the sketches counted there, exact */
+    uint64_t n_keys;
+    const uint64_t *errors;      /* [n_out][n_keys] point query on the covered windows' summed cells */
+} sa_series_result;
+
+/* Row t is bit for bit what sa_window_range(e, t-width+1, t, keys, n_keys, 0, ..)
+ * returns in hll_hist, distinct and errors.  Ordering and waiting as
+ * sa_window_range: joins every launch in flight, runs on the engine stream,
+ * waits, clears nothing (two calls give equal bits); works on every ingest
+ * path; `keys` are hashes, also on an SA_OPT_DENSE_IDS engine, and key 0 is
+ * allowed.  SA_ERANGE when first > last, width == 0, width > n_windows,
+ * first + 1 < width, or first-width+1 or last is not resident; SA_EINVAL for a
+ * null `out`, n_keys != 0 with null `keys`, or flags != 0 (reserved);
+ * SA_ENOMEM when the result or the device scratch cannot be allocated.  The
+ * engine stays usable after any error.  Free the result with
+ * sa_series_result_free.
+ * There is no group entry point: histograms are not additive over members
+ * (the maximum is taken register by register first), so a group series would
+ * have to all-reduce every window's registers -- the traffic this call exists
+ * to avoid.  A group's caller loops sa_group_window_range. */
+int sa_window_series(sa_engine *e, uint64_t first, uint64_t last, uint32_t width,
+                     const uint64_t *keys, uint64_t n_keys, uint32_t flags, sa_series_result **out);
+void sa_series_result_free(sa_series_result *r);
 
 int sa_get_stats(sa_engine *e, sa_stats *out);
 

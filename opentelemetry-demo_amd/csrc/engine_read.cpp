@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cstring>
 #include <memory>
+#include <new>
 #include <numeric>
 #include <string>
 #include <vector>
@@ -199,6 +200,19 @@ int range_buffers(sa_engine *e, uint64_t n_keys, bool regs, bool cells) {
   return SA_OK;
 }
 
+// On `s`: fold_window for every window of first..last, with the windows'
+// count folds as one launch (the ERROR slabs of the small rings that have
+// them go window by window first)
+int range_fold_on(sa_engine *e, uint64_t first, uint64_t last, hipStream_t s) {
+  const uint32_t W = e->cfg.n_windows, n = (uint32_t)(last - first + 1);
+  for (uint32_t k = 0; k < n; ++k)
+    if (int rc = fold_errslab(e, (first + k) & (W - 1), s)) return rc;
+  SA_HIP(e, sa::launch_range_fold(e->gkeys, e->errcnt, e->cap, e->cms, e->cms_slot_elems, e->cfg.cms_d, e->cfg.cms_w,
+                                  64 - sa::log2u(e->cfg.cms_w), e->d_seeds, e->binned.kinv, e->dense() ? 1u : 0u, W,
+                                  first, n, s));
+  return SA_OK;
+}
+
 // On `s`: every window of first..last folded (its per-slot ERROR counts go to
 // its cells before any cell is summed), then the registers max-merged into
 // hist (zeroed here) and regs, and the cells summed into cells -- each where
@@ -206,13 +220,7 @@ int range_buffers(sa_engine *e, uint64_t n_keys, bool regs, bool cells) {
 int range_merge_on(sa_engine *e, uint64_t first, uint64_t last, uint32_t *hist, uint8_t *regs,
                    unsigned long long *cells, hipStream_t s) {
   const uint32_t W = e->cfg.n_windows, n = (uint32_t)(last - first + 1);
-  // fold_window for each, with the windows' count folds as one launch (the
-  // ERROR slabs of the small rings that have them go window by window first)
-  for (uint32_t k = 0; k < n; ++k)
-    if (int rc = fold_errslab(e, (first + k) & (W - 1), s)) return rc;
-  SA_HIP(e, sa::launch_range_fold(e->gkeys, e->errcnt, e->cap, e->cms, e->cms_slot_elems, e->cfg.cms_d, e->cfg.cms_w,
-                                  64 - sa::log2u(e->cfg.cms_w), e->d_seeds, e->binned.kinv, e->dense() ? 1u : 0u, W,
-                                  first, n, s));
+  if (int rc = range_fold_on(e, first, last, s)) return rc;
   if (hist) SA_HIP(e, hipMemsetAsync(hist, 0, (size_t)e->cfg.n_services * SA_HLL_HIST_BINS * 4, s));
   if (hist || regs) SA_HIP(e, sa::launch_range_merge(e->hll, W, e->cfg.n_services, e->cfg.hll_p, first, n, hist, regs, s));
   if (cells) SA_HIP(e, sa::launch_range_cells(e->cms, e->cms_slot_elems, W, first, n, cells, s));
@@ -249,6 +257,30 @@ int range_result(sa_engine *e, uint64_t first, uint64_t last, const uint32_t *d_
   return SA_OK;
 }
 
+// ---- sliding series (sa_window_series; kernels in spanagg_range.hip) ----
+// p (holding cap elements) grown to at least `want`
+template <class T>
+int series_grow(sa_engine *e, T *&p, uint64_t &cap, uint64_t want, const char *what) {
+  if (want <= cap) return SA_OK;
+  dfree(e, p);  // (hipFree waits for the device)
+  cap = 0;
+  if (int rc = dalloc(e, p, want, false, what)) return rc;
+  cap = want;
+  return SA_OK;
+}
+
+int series_buffers(sa_engine *e, uint64_t n_out, uint64_t n_keys) {
+  sa_engine::Series &S = e->series;
+  if (int rc = series_grow(e, S.hist, S.hist_cap, n_out * e->cfg.n_services * SA_HLL_HIST_BINS,
+                           "window series: histogram hipMalloc failed"))
+    return rc;
+  if (!S.row0)
+    if (int rc = dalloc(e, S.row0, e->cfg.n_windows, false, "window series: row sum hipMalloc failed")) return rc;
+  if (int rc = series_grow(e, S.keys, S.key_cap, n_keys ? std::max<uint64_t>(n_keys, 1u << 10) : 0,
+                           "window series: key buffer hipMalloc failed"))
+    return rc;
+  return series_grow(e, S.errors, S.err_cap, n_out * n_keys, "window series: answer buffer hipMalloc failed");
+}
 }  // namespace
 
 namespace sa_grp {
@@ -538,6 +570,62 @@ int sa_window_range(sa_engine *e, uint64_t first, uint64_t last, const uint64_t 
 }
 
 void sa_range_result_free(sa_range_result *r) { delete reinterpret_cast<range_holder *>(r); }
+
+int sa_window_series(sa_engine *e, uint64_t first, uint64_t last, uint32_t width, const uint64_t *keys,
+                     uint64_t n_keys, uint32_t flags, sa_series_result **out) {
+  if (!e || !out) return SA_EINVAL;
+  *out = nullptr;
+  if (n_keys && !keys) return fail(e, SA_EINVAL, "window series: n_keys != 0 with null keys");
+  if (flags) return fail(e, SA_EINVAL, "window series: flags are reserved (0)");
+  const uint32_t W = e->cfg.n_windows;
+  if (first > last || width == 0 || width > W || first + 1 < width || !resident(e, first - width + 1) ||
+      !resident(e, last))
+    return fail(e, SA_ERANGE, "window series: first > last, a width outside 1..n_windows, or a covered window is not resident");
+  if (int rc = begin_read(e)) return rc;
+  const uint64_t a = first - width + 1;
+  const uint32_t n_out = (uint32_t)(last - first + 1), n_in = n_out + width - 1;  // (a and last resident: n_in <= W)
+  std::unique_ptr<series_holder> h;
+  std::vector<uint64_t> row0;
+  try {
+    h.reset(new series_holder());
+    h->shape(first, last, width, e->cfg, n_keys);
+    row0.resize(n_in);
+  } catch (const std::bad_alloc &) {
+    return fail(e, SA_ENOMEM, "window series: the result does not fit in host memory");
+  }
+  if (int rc = series_buffers(e, n_out, n_keys)) return rc;
+  const sa_engine::Series &S = e->series;
+  hipStream_t s = e->stream;
+  // every covered window folded before any cell is read
+  if (int rc = range_fold_on(e, a, last, s)) return rc;
+  SA_HIP(e, sa::launch_series_hll(e->hll, W, e->cfg.n_services, e->cfg.hll_p, a, width, n_out, S.hist, s));
+  SA_HIP(e, sa::launch_series_row0(e->cms, e->cms_slot_elems, W, a, n_in, e->cfg.cms_w, S.row0, s));
+  hipError_t st = hipSuccess;
+  if (n_keys) {
+    st = hipMemcpyAsync(S.keys, keys, n_keys * 8, hipMemcpyHostToDevice, s);
+    if (st == hipSuccess)
+      st = sa::launch_series_query(e->cms, e->cms_slot_elems, W, a, width, n_out, e->cfg.cms_d, e->cfg.cms_w,
+                                   64 - sa::log2u(e->cfg.cms_w), e->d_seeds, S.keys, n_keys, S.errors, s);
+    if (st == hipSuccess) st = hipMemcpyAsync(h->errors.data(), S.errors, h->errors.size() * 8, hipMemcpyDeviceToHost, s);
+  }
+  if (st == hipSuccess) st = hipMemcpyAsync(h->hist.data(), S.hist, h->hist.size() * 4, hipMemcpyDeviceToHost, s);
+  if (st == hipSuccess) st = hipMemcpyAsync(row0.data(), S.row0, (size_t)n_in * 8, hipMemcpyDeviceToHost, s);
+  const hipError_t waited = hipStreamSynchronize(s);  // (also after a failure: a copy into h may be in flight)
+  if (st != hipSuccess || waited != hipSuccess)
+    return fail(e, SA_EDEVICE, std::string("window series: ") + hipGetErrorString(st != hipSuccess ? st : waited));
+  uint64_t run = 0;  // the sliding sum of the windows' row-0 sums
+  for (uint32_t k = 0; k < n_in; ++k) {
+    run += row0[k];
+    if (k >= width) run -= row0[k - width];
+    if (k + 1 >= width) h->error_spans[k + 1 - width] = run;
+  }
+  for (size_t i = 0; i < h->distinct.size(); ++i)
+    h->distinct[i] = sa_hll_estimate_hist(h->hist.data() + i * SA_HLL_HIST_BINS, e->cfg.hll_p);
+  *out = &h.release()->r;
+  return SA_OK;
+}
+
+void sa_series_result_free(sa_series_result *r) { delete reinterpret_cast<series_holder *>(r); }
 
 int sa_window_advance(sa_engine *e, uint64_t new_base) {
   if (!e) return SA_EINVAL;

@@ -198,6 +198,16 @@ struct sa_engine {
     uint64_t *keys = nullptr;
     uint64_t key_cap = 0;
   } range;
+  // sa_window_series (grown by the calls that need more): every output's
+  // histogram [n_out][n_services][SA_HLL_HIST_BINS], the windows' row-0 sums
+  // [n_windows], the keys and their answers [n_out][n_keys]
+  struct Series {
+    uint32_t *hist = nullptr;
+    uint64_t hist_cap = 0;
+    unsigned long long *row0 = nullptr, *errors = nullptr;
+    uint64_t *keys = nullptr;
+    uint64_t key_cap = 0, err_cap = 0;
+  } series;
   // sa_ingest: two pinned host slots and their HBM copies; a slot is refilled
   // once its event (H2D copy + aggregation of the previous use) has passed
   struct HostStage {

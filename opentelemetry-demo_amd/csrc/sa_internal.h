@@ -430,6 +430,19 @@ hipError_t launch_range_cells(const unsigned long long *cms, uint64_t slot_elems
 hipError_t launch_range_query(const unsigned long long *cells, uint32_t d, uint32_t w, uint32_t shift,
                               const uint64_t *seeds, const uint64_t *keys, uint64_t n, unsigned long long *out,
                               hipStream_t s);
+// sliding series over the ring (sa_window_series): output o of n_out covers
+// the windows a + o .. a + o + width - 1.  hist [n_out][n_services][SA_HLL_HIST_BINS]
+// (zeroed here): every output's max-merged registers counted by value
+hipError_t launch_series_hll(const uint8_t *hll, uint32_t n_windows, uint32_t n_services, uint32_t p, uint64_t a,
+                             uint32_t width, uint32_t n_out, uint32_t *hist, hipStream_t s);
+// out [n_out][n_keys] = range_query on the cells summed over each output's windows
+hipError_t launch_series_query(const unsigned long long *cms, uint64_t slot_elems, uint32_t n_windows, uint64_t a,
+                               uint32_t width, uint32_t n_out, uint32_t d, uint32_t w, uint32_t shift,
+                               const uint64_t *seeds, const uint64_t *keys, uint64_t n_keys, unsigned long long *out,
+                               hipStream_t s);
+// out [n_in] = count-min row 0 of each window a .. a + n_in - 1, summed
+hipError_t launch_series_row0(const unsigned long long *cms, uint64_t slot_elems, uint32_t n_windows, uint64_t a,
+                              uint32_t n_in, uint32_t w, unsigned long long *out, hipStream_t s);
 // sorted union of series ids on the device (spanagg_union.hip): out = the
 // distinct non-zero ids of in[0..n) ascending, *d_total (device u32) their
 // count; scratch >= key_union_scratch_bytes(n); big_scratch / big_bytes: a

@@ -124,6 +124,24 @@ struct range_holder {
   }
 };
 
+struct series_holder {
+  sa_series_result r;
+  std::vector<uint32_t> hist;
+  std::vector<double> distinct;
+  std::vector<uint64_t> error_spans, errors;
+  // the columns sized for outputs first..last of config c and n_keys keys, and r pointing at them
+  __attribute__((visibility("hidden"))) void shape(uint64_t first, uint64_t last, uint32_t width, const sa_config &c,
+                                                   uint64_t n_keys) {
+    const size_t n_out = (size_t)(last - first + 1);
+    hist.resize(n_out * c.n_services * SA_HLL_HIST_BINS), distinct.resize(n_out * c.n_services);
+    error_spans.resize(n_out), errors.resize(n_out * n_keys);
+    r.first_window = first, r.last_window = last, r.width = width, r.n_out = (uint32_t)n_out;
+    r.n_services = c.n_services, r.hll_p = c.hll_p;
+    r.hll_hist = hist.data(), r.distinct = distinct.data(), r.error_spans = error_spans.data();
+    r.n_keys = n_keys, r.errors = errors.data();
+  }
+};
+
 struct sketch_holder {
   sa_sketch_result r;
   std::vector<uint8_t> hll;

@@ -14,6 +14,14 @@
 //   range_cells_kernel   count-min cells summed over the windows (u64).
 //   range_query_kernel   point queries on the summed cells, one thread a key.
 //
+// and for sa_window_series, the same answers for every trailing span of
+// `width` windows in one pass over the ring:
+//
+//   series_hll_kernel    the sliding maximum of the registers by blocks of
+//                        `width` windows and every output's histogram.
+//   series_query_kernel  sliding sums of the keys' cells, their minimum per output.
+//   series_row0_kernel   count-min row 0 summed per window (error_spans).
+//
 // Every result is an integer maximum or an integer sum, so the order of the
 // atomics does not show: two calls, and one engine against a group, give the
 // same bits.
@@ -151,7 +159,303 @@ __global__ __launch_bounds__(256) void range_query_kernel(const unsigned long lo
   }
 }
 
+// ---- sliding series (sa_window_series): output o of n_out covers the windows
+// a + o .. a + o + width - 1 of the ring ----
+constexpr uint32_t kSeriesLanes = 64;          // one wave a workgroup: the walk is one chain per column
+constexpr uint32_t kSeriesStashBytes = 32768;  // LDS stash of a workgroup (the bound on width)
+constexpr uint32_t kSeriesChunk1 = 16;         // width 1: outputs a workgroup takes
+// A tile inside one service counts into 8 copies of the 64 bins, by lane & 7:
+// most registers hold one of a few values, and 64 lanes on one LDS word take
+// turns.  68 words a copy: a bin's copies lie in different banks.
+constexpr uint32_t kSeriesCopies = 8, kSeriesCopyWords = 68;
+
+__device__ __forceinline__ uint32_t series_hist_words(uint32_t nsv) {
+  return nsv == 1 ? kSeriesCopies * kSeriesCopyWords : nsv * kRangeBins;
+}
+
+// One output's registers m (16 a thread that is `on`) counted into the LDS
+// histogram h (zero before and after), then one atomicAdd per non-zero bin
+// into out = hist[output][svc0]; nsv: services of the tile.
+__device__ __forceinline__ void series_count(uint4 m, bool on, uint32_t *h, uint32_t hbase, uint32_t nsv,
+                                             uint32_t lane, uint32_t *out, uint32_t svc0, uint32_t n_services) {
+  if (on) {
+    const uint32_t w4[4] = {m.x, m.y, m.z, m.w};
+#pragma unroll
+    for (uint32_t b = 0; b < 16; ++b) {
+      const uint32_t x = (w4[b >> 2] >> (8 * (b & 3))) & 0xFFu;
+      atomicAdd(&h[hbase + (x < kRangeBins ? x : kRangeBins - 1)], 1u);
+    }
+  }
+  __syncthreads();
+  if (nsv == 1) {  // (64 lanes, 64 bins)
+    uint32_t n = 0;
+#pragma unroll
+    for (uint32_t cp = 0; cp < kSeriesCopies; ++cp) {
+      n += h[cp * kSeriesCopyWords + lane];
+      h[cp * kSeriesCopyWords + lane] = 0;
+    }
+    if (n) atomicAdd(out + lane, n);
+  } else {
+    for (uint32_t i = lane; i < nsv * kRangeBins; i += kSeriesLanes) {
+      const uint32_t n = h[i];
+      if (n && svc0 + i / kRangeBins < n_services) atomicAdd(out + i, n);
+      h[i] = 0;
+    }
+  }
+  __syncthreads();
+}
+
+// Sliding maximum by blocks of `width` windows (van Herk / Gil-Werman).  The
+// window slot is S * tps columns of 16 registers; a workgroup takes one tile
+// of L consecutive columns (L a power of two <= 64: a tile lies in one
+// service or covers L / tps whole ones) and one block j of `width` windows.
+//   backward  block j from its end to its start: the running suffix maximum
+//             of step r goes to stash[r] (LDS, [width][L] uint4)
+//   forward   block j + 1 from its start with the running prefix maximum P
+//             (zero before the first step): output j * width + r has the
+//             registers max(stash[r], P before step r)
+// so a window's registers are read twice.  A block whose stash would pass
+// kSeriesStashBytes goes chunk by chunk (chunk < width steps): a first walk
+// over block j leaves later[c], the maximum of the chunks after c; then for
+// each chunk in turn the backward walk fills the stash with the suffix
+// maxima inside the chunk, and step r's suffix maximum is max(stash[r - chunk
+// start], later[c]).  The stash holds chunk + width / chunk entries and block
+// j is read twice: three reads a window.  At width 1 every window is its own
+// output: no stash, one read, kSeriesChunk1 outputs a workgroup.  Every
+// output's registers are counted into an LDS histogram per service of the
+// tile and leave as one atomicAdd per non-zero bin.  hist
+// [n_out][n_services][64] must be zero.  Grid: tiles * blocks.
+__global__ __launch_bounds__(kSeriesLanes) void series_hll_kernel(const uint4 *regs, uint64_t slot16, uint32_t win_mask,
+                                                                  uint64_t a, uint32_t width, uint32_t n_out,
+                                                                  uint32_t log2tps, uint32_t n_services, uint32_t L,
+                                                                  uint32_t chunk, uint32_t tiles, uint32_t *hist) {
+  extern __shared__ uint4 series_lds[];
+  const uint32_t lane = threadIdx.x;
+  const uint32_t nsv = max(1u, L >> log2tps);  // services of a tile
+  const uint32_t C = (width + chunk - 1) / chunk;  // chunks of a block (1: the whole block in the stash)
+  uint4 *stash = series_lds;                       // [chunk][L] (none at width 1)
+  uint4 *later = stash + (size_t)chunk * L;        // [C][L] (none when C == 1)
+  uint32_t *h = reinterpret_cast<uint32_t *>(series_lds + (width == 1 ? 0 : (size_t)(chunk + (C > 1 ? C : 0)) * L));
+  for (uint32_t i = lane; i < series_hist_words(nsv); i += kSeriesLanes) h[i] = 0;
+  const uint32_t tile = blockIdx.x % tiles, j = blockIdx.x / tiles;
+  const uint64_t c = (uint64_t)tile * L + lane;  // the thread's column of the slot
+  const bool on = lane < L && c < slot16;
+  const uint32_t svc0 = (uint32_t)(((uint64_t)tile * L) >> log2tps);  // the tile's first service
+  const uint32_t hbase = nsv == 1 ? (lane & (kSeriesCopies - 1)) * kSeriesCopyWords : (lane >> log2tps) * kRangeBins;
+
+  if (width == 1) {
+    const uint32_t o0 = j * kSeriesChunk1, R = min(kSeriesChunk1, n_out - o0);
+    __syncthreads();  // (the zeroed histogram)
+    for (uint32_t r0 = 0; r0 < R; r0 += kRangeInFlight) {  // (the same trips for every thread)
+      uint4 v[kRangeInFlight];
+#pragma unroll
+      for (uint32_t k = 0; k < kRangeInFlight; ++k) {
+        v[k] = uint4{0, 0, 0, 0};
+        if (on && r0 + k < R) v[k] = regs[((a + o0 + r0 + k) & win_mask) * slot16 + c];
+      }
+#pragma unroll
+      for (uint32_t k = 0; k < kRangeInFlight; ++k) {
+        if (r0 + k >= R) break;  // (uniform)
+        series_count(v[k], on, h, hbase, nsv, lane, hist + ((uint64_t)(o0 + r0 + k) * n_services + svc0) * kRangeBins,
+                     svc0, n_services);
+      }
+    }
+    return;
+  }
+
+  const uint32_t o0 = j * width;                // the block's first output, and its first window past a
+  const uint32_t R = min(width, n_out - o0);    // outputs of this block
+  const uint64_t w0 = a + o0, w1 = w0 + width;  // first windows of block j and of block j + 1
+  if (on && C > 1) {  // later[c] = the maximum of block j's chunks after c
+    uint4 run{0, 0, 0, 0};
+    for (uint32_t cc = C; cc-- > 0;) {
+      later[(size_t)cc * L + lane] = run;
+      const uint32_t lo = cc * chunk, hi = min(width, lo + chunk);
+      uint32_t r = lo;
+      for (; r + kRangeInFlight <= hi; r += kRangeInFlight) {
+        uint4 v[kRangeInFlight];
+#pragma unroll
+        for (uint32_t k = 0; k < kRangeInFlight; ++k) v[k] = regs[((w0 + r + k) & win_mask) * slot16 + c];
+#pragma unroll
+        for (uint32_t k = 0; k < kRangeInFlight; ++k) run = max_u8x16(run, v[k]);
+      }
+      for (; r < hi; ++r) run = max_u8x16(run, regs[((w0 + r) & win_mask) * slot16 + c]);
+    }
+  }
+  __syncthreads();  // (the zeroed histogram; a thread reads only its own stash and later column)
+
+  uint4 P{0, 0, 0, 0};
+  for (uint32_t cc = 0; cc < C && cc * chunk < R; ++cc) {  // (the same trips for every thread)
+    const uint32_t lo = cc * chunk, hi = min(width, lo + chunk), end = min(hi, R);
+    uint4 E{0, 0, 0, 0};
+    if (on) {  // backward: steps hi - 1 .. lo
+      uint4 acc{0, 0, 0, 0};
+      uint32_t r = hi;
+      for (; r >= lo + kRangeInFlight; r -= kRangeInFlight) {
+        uint4 v[kRangeInFlight];
+#pragma unroll
+        for (uint32_t k = 0; k < kRangeInFlight; ++k) v[k] = regs[((w0 + r - 1 - k) & win_mask) * slot16 + c];
+#pragma unroll
+        for (uint32_t k = 0; k < kRangeInFlight; ++k) {
+          acc = max_u8x16(acc, v[k]);
+          stash[(size_t)(r - 1 - k - lo) * L + lane] = acc;
+        }
+      }
+      for (; r > lo; --r) {
+        acc = max_u8x16(acc, regs[((w0 + r - 1) & win_mask) * slot16 + c]);
+        stash[(size_t)(r - 1 - lo) * L + lane] = acc;
+      }
+      if (C > 1) E = later[(size_t)cc * L + lane];
+    }
+    for (uint32_t r0 = lo; r0 < end; r0 += kRangeInFlight) {
+      uint4 v[kRangeInFlight];
+#pragma unroll
+      for (uint32_t k = 0; k < kRangeInFlight; ++k) {
+        // step r's window of block j + 1 is needed by the outputs after r only
+        v[k] = uint4{0, 0, 0, 0};
+        if (on && r0 + k < end && r0 + k + 1 < R) v[k] = regs[((w1 + r0 + k) & win_mask) * slot16 + c];
+      }
+#pragma unroll
+      for (uint32_t k = 0; k < kRangeInFlight; ++k) {
+        const uint32_t r = r0 + k;
+        if (r >= end) break;  // (uniform)
+        uint4 m{0, 0, 0, 0};
+        if (on) {
+          m = max_u8x16(max_u8x16(stash[(size_t)(r - lo) * L + lane], E), P);
+          P = max_u8x16(P, v[k]);
+        }
+        series_count(m, on, h, hbase, nsv, lane, hist + ((uint64_t)(o0 + r) * n_services + svc0) * kRangeBins, svc0,
+                     n_services);
+      }
+    }
+  }
+}
+
+// Point queries of every output: thread (key i, chunk blockIdx.y of the
+// outputs) seeds d running sums with the `width` covered cells at the key's d
+// columns, then adds the entering window's cell and takes off the leaving
+// one's per output (u64, exact).  out [n_out][n_keys].
+__global__ __launch_bounds__(256) void series_query_kernel(const unsigned long long *cms, uint64_t slot_elems,
+                                                           uint32_t win_mask, uint64_t a, uint32_t width,
+                                                           uint32_t n_out, uint32_t per_chunk, uint32_t d, uint32_t w,
+                                                           uint32_t shift, const uint64_t *seeds, const uint64_t *keys,
+                                                           uint64_t n_keys, unsigned long long *out) {
+  const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+  if (i >= n_keys) return;
+  const uint32_t o0 = blockIdx.y * per_chunk, o1 = min(n_out, o0 + per_chunk);
+  const uint64_t key = keys[i];
+  uint64_t at[8];  // (cms_d <= 8) the key's cell of each row within a slot
+  unsigned long long sum[8];
+#pragma unroll
+  for (uint32_t r = 0; r < 8; ++r) {
+    at[r] = r < d ? (uint64_t)r * w + (splitmix64(key ^ seeds[r]) >> shift) : 0;  // col < w: shift = 64 - log2 w
+    sum[r] = 0;
+  }
+#pragma unroll 4
+  for (uint32_t k = 0; k < width; ++k) {
+    const unsigned long long *slot = cms + ((a + o0 + k) & win_mask) * slot_elems;
+#pragma unroll
+    for (uint32_t r = 0; r < 8; ++r)
+      if (r < d) sum[r] += slot[at[r]];
+  }
+  for (uint32_t o = o0; o < o1; ++o) {
+    if (o > o0) {
+      const unsigned long long *in = cms + ((a + o + width - 1) & win_mask) * slot_elems;
+      const unsigned long long *gone = cms + ((a + o - 1) & win_mask) * slot_elems;
+#pragma unroll
+      for (uint32_t r = 0; r < 8; ++r)
+        if (r < d) sum[r] += in[at[r]] - gone[at[r]];
+    }
+    unsigned long long m = ~0ULL;
+#pragma unroll
+    for (uint32_t r = 0; r < 8; ++r)
+      if (r < d) m = sum[r] < m ? sum[r] : m;
+    out[(uint64_t)o * n_keys + i] = m;
+  }
+}
+
+// out[k] = the sum of count-min row 0 of window a + k (every ERROR span the
+// window's sketch counted, once); one workgroup a window
+__global__ __launch_bounds__(256) void series_row0_kernel(const unsigned long long *cms, uint64_t slot_elems,
+                                                          uint32_t win_mask, uint64_t a, uint32_t w,
+                                                          unsigned long long *out) {
+  __shared__ unsigned long long part[256];
+  const unsigned long long *row = cms + ((a + blockIdx.x) & win_mask) * slot_elems;
+  unsigned long long acc = 0;
+  for (uint32_t i = threadIdx.x; i < w; i += 256) acc += row[i];
+  part[threadIdx.x] = acc;
+  __syncthreads();
+  for (uint32_t s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[blockIdx.x] = part[0];
+}
+
 }  // namespace
+
+// The tile and the stash of a width.  Up to 32 windows the whole block's
+// suffix maxima fit kSeriesStashBytes at 64 columns (chunk = width).  Above,
+// chunks: the stash holds chunk + ceil(width / chunk) entries of L columns,
+// half the entries for each, so width <= chunk^2 -- 64 columns and chunks of
+// 16 up to 256 windows, 32 and 32 up to 1,024, 16 and 64 up to 4,096 (the
+// largest ring).
+static void series_shape(uint32_t width, uint32_t *L, uint32_t *chunk) {
+  *L = kSeriesLanes, *chunk = width;
+  if ((uint64_t)width * kSeriesLanes * 16 <= kSeriesStashBytes) return;
+  for (;; *L >>= 1) {
+    *chunk = kSeriesStashBytes / 16 / *L / 2;
+    if ((uint64_t)*chunk * *chunk >= width || *L == 1) return;
+  }
+}
+
+hipError_t launch_series_hll(const uint8_t *hll, uint32_t n_windows, uint32_t n_services, uint32_t p, uint64_t a,
+                             uint32_t width, uint32_t n_out, uint32_t *hist, hipStream_t s) {
+  uint32_t L, chunk;
+  series_shape(width, &L, &chunk);
+  const uint32_t log2tps = p - 4, C = (width + chunk - 1) / chunk;
+  const uint64_t slot16 = (uint64_t)n_services << log2tps;
+  const uint32_t per_block = width == 1 ? kSeriesChunk1 : width;  // outputs a workgroup takes
+  const uint64_t tiles = (slot16 + L - 1) / L, blocks = (n_out + per_block - 1) / per_block;
+  if (tiles * blocks >= (1ULL << 26)) return hipErrorInvalidConfiguration;  // (grid x block below 2^32)
+  if (hipError_t e = hipMemsetAsync(hist, 0, (size_t)n_out * n_services * kRangeBins * 4, s); e != hipSuccess) return e;
+  const uint32_t nsv = std::max(1u, L >> log2tps);
+  const size_t lds = (width == 1 ? 0 : (size_t)(chunk + (C > 1 ? C : 0)) * L * 16) +
+                     (size_t)(nsv == 1 ? kSeriesCopies * kSeriesCopyWords : nsv * kRangeBins) * 4;
+  if (lds > 32768)  // (many services a tile)
+    if (hipError_t e = hipFuncSetAttribute((const void *)&series_hll_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)lds);
+        e != hipSuccess)
+      return e;
+  hipLaunchKernelGGL(series_hll_kernel, dim3((uint32_t)(tiles * blocks)), dim3(kSeriesLanes), lds, s,
+                     reinterpret_cast<const uint4 *>(hll), slot16, n_windows - 1, a, width, n_out, log2tps, n_services,
+                     L, chunk, (uint32_t)tiles, hist);
+  return hipGetLastError();
+}
+
+hipError_t launch_series_query(const unsigned long long *cms, uint64_t slot_elems, uint32_t n_windows, uint64_t a,
+                               uint32_t width, uint32_t n_out, uint32_t d, uint32_t w, uint32_t shift,
+                               const uint64_t *seeds, const uint64_t *keys, uint64_t n_keys, unsigned long long *out,
+                               hipStream_t s) {
+  if (n_keys == 0) return hipSuccess;
+  const uint64_t key_blocks = (n_keys + 255) / 256;
+  // chunks of the outputs: enough workgroups for a short key list (~2,048),
+  // none shorter than a quarter of the seeding it pays for (width cells a
+  // row), nor than 16 outputs
+  const uint32_t most = std::max(1u, n_out / std::max(width / 4, 16u));
+  const uint32_t chunks = (uint32_t)std::min<uint64_t>(most, std::max<uint64_t>(1, 2048 / key_blocks));
+  const uint32_t per_chunk = (n_out + chunks - 1) / chunks;
+  const dim3 grid((uint32_t)key_blocks, (n_out + per_chunk - 1) / per_chunk);
+  hipLaunchKernelGGL(series_query_kernel, grid, dim3(256), 0, s, cms, slot_elems, n_windows - 1, a, width, n_out,
+                     per_chunk, d, w, shift, seeds, keys, n_keys, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_series_row0(const unsigned long long *cms, uint64_t slot_elems, uint32_t n_windows, uint64_t a,
+                              uint32_t n_in, uint32_t w, unsigned long long *out, hipStream_t s) {
+  hipLaunchKernelGGL(series_row0_kernel, dim3(n_in), dim3(256), 0, s, cms, slot_elems, n_windows - 1, a, w, out);
+  return hipGetLastError();
+}
 
 hipError_t launch_range_merge(const uint8_t *hll, uint32_t n_windows, uint32_t n_services, uint32_t p, uint64_t first,
                               uint32_t n_win, uint32_t *hist, uint8_t *out, hipStream_t s) {

@@ -89,6 +89,14 @@ class sa_range_result(C.Structure):
     ]
 
 
+class sa_series_result(C.Structure):
+    _fields_ = [
+        ("first_window", C.c_uint64), ("last_window", C.c_uint64), ("width", C.c_uint32), ("n_out", C.c_uint32),
+        ("n_services", C.c_uint32), ("hll_p", C.c_uint32), ("hll_hist", u32p), ("distinct", f64p),
+        ("error_spans", u64p), ("n_keys", C.c_uint64), ("errors", u64p),
+    ]
+
+
 class sa_stats(C.Structure):
     _fields_ = [
         ("spans", C.c_uint64), ("zero_key", C.c_uint64), ("invalid_service", C.c_uint64),
@@ -148,6 +156,9 @@ SIGNATURES = [
     ("sa_group_window_range", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, u64p, C.c_uint64, C.c_uint32,
                                         C.POINTER(C.POINTER(sa_range_result))]),
     ("sa_range_result_free", None, [C.POINTER(sa_range_result)]),
+    ("sa_window_series", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, u64p, C.c_uint64, C.c_uint32,
+                                   C.POINTER(C.POINTER(sa_series_result))]),
+    ("sa_series_result_free", None, [C.POINTER(sa_series_result)]),
     ("sa_hll_estimate_hist", C.c_double, [u32p, C.c_uint32]),
     ("sa_get_stats", C.c_int, [C.c_void_p, C.POINTER(sa_stats)]),
     ("sa_bind_ids", C.c_int, [C.c_void_p, u64p, u64p, C.c_uint64]),

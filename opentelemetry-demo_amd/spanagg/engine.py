@@ -157,6 +157,27 @@ class RangeResult:
         return est[:k]
 
 
+@dataclass
+class SeriesResult:
+    """sa_series_result: row i is window first + i's answer over the trailing
+    `width` windows (what window_range(first + i - width + 1, first + i, keys) returns)."""
+    first: int
+    last: int
+    width: int
+    hist: np.ndarray              # [n_out, n_services, 64] u32
+    distinct: np.ndarray          # [n_out, n_services] f64: hll_estimate_hist(hist[i, s], p)
+    error_spans: np.ndarray       # [n_out] u64: ERROR spans the covered windows' sketches counted, exact
+    errors: np.ndarray            # [n_out, n_keys] u64: the summed count-min's estimate for keys[j]
+    keys: np.ndarray              # [n_keys] u64, as given
+    p: int = 14
+
+    def top_errors(self, i: int, k: int = 10):
+        """Row i's top-k (key, estimate) of the queried keys, ordered as sketch.heavy_hitters."""
+        est = [(int(key), int(e)) for key, e in zip(self.keys, self.errors[i]) if e > 0]
+        est.sort(key=lambda e: (-e[1], e[0]))
+        return est[:k]
+
+
 def hll_estimate(regs: np.ndarray, p: int) -> float:
     lib = _lib.load()
     r = np.ascontiguousarray(regs, dtype=np.uint8)
@@ -414,6 +435,29 @@ class Engine:
         (series hashes, also on a dense-index engine).  registers / cells:
         also the merged registers / the summed cells themselves."""
         return _window_range(self, self.lib.sa_window_range, "sa_window_range", first, last, keys, registers, cells)
+
+    def window_series(self, first: int, last: int, width: int = 1, keys=None) -> SeriesResult:
+        """sa_window_series: for every window t of first..last the answers of
+        window_range(t - width + 1, t, keys), from one pass over the ring on
+        the device (numpy copies; `keys` are series hashes, also on a
+        dense-index engine)."""
+        k = np.ascontiguousarray(() if keys is None else keys, dtype=np.uint64).reshape(-1)
+        out = C.POINTER(_lib.sa_series_result)()
+        self._check(self.lib.sa_window_series(self._h, int(first), int(last), int(width),
+                                              k.ctypes.data_as(_lib.u64p) if len(k) else None, len(k), 0,
+                                              C.byref(out)), "sa_window_series")
+        try:
+            r = out.contents
+            n, S, p = int(r.n_out), int(r.n_services), int(r.hll_p)
+            return SeriesResult(
+                int(r.first_window), int(r.last_window), int(r.width),
+                np.ctypeslib.as_array(r.hll_hist, shape=(n, S, _lib.SA_HLL_HIST_BINS)).copy(),
+                np.ctypeslib.as_array(r.distinct, shape=(n, S)).copy(),
+                np.ctypeslib.as_array(r.error_spans, shape=(n,)).copy(),
+                np.ctypeslib.as_array(r.errors, shape=(n, len(k))).copy() if len(k) else np.zeros((n, 0), np.uint64),
+                k, p)
+        finally:
+            self.lib.sa_series_result_free(out)
 
     def flush_exp(self, allow_drops: bool = False) -> ExpoResult:
         out = C.POINTER(_lib.sa_exp_result)()
