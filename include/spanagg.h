@@ -19,6 +19,7 @@
  *   (new) per-service HLL + error count-min         sa_window_read / sa_window_advance
  *   (new) the same over a span of windows           sa_window_range (merged on the device)
  *   (new) every trailing span of a window series    sa_window_series (one pass over the ring)
+ *   (new) heavy hitters over a span of windows      sa_window_top (key table scanned on the device)
  *
  * Boundary rules (mirroring the connector's contracts):
  *  - Ownership: batches are borrowed for the duration of the call (page-locked
@@ -371,6 +372,45 @@ int sa_window_series(sa_engine *e, uint64_t first, uint64_t last, uint32_t width
                      const uint64_t *keys, uint64_t n_keys, uint32_t flags, sa_series_result **out);
 void sa_series_result_free(sa_series_result *r);
 
+/* ---- heavy hitters over the window ring ----
+ * "Which series fail most over these windows": the engine's own key table is
+ * the candidate list, so the caller sends no keys and gets k rows back. */
+#define SA_TOP_MAX_K 4096u
+typedef struct {
+    uint64_t first_window, last_window;   /* inclusive */
+    uint32_t k, n;                        /* asked for; returned (n <= k) */
+    uint64_t n_resident;                  /* series in the key table when the call ran: the candidates */
+    uint64_t n_matched;                   /* candidates with estimate >= min_count */
+    uint64_t error_spans;                 /* sum of row 0 of the summed cells: ERROR spans counted in the range, exact */
+    const uint64_t *key_hash;             /* [n] */
+    const uint64_t *errors;               /* [n] */
+} sa_top_result;
+
+/* Candidates: every non-zero key resident in the key table when the call
+ * runs -- the series seen since the last reclaim, on every ingest path.  On an
+ * SA_OPT_DENSE_IDS engine key_hash is the bound hash, and unbound indices are
+ * not candidates.  Key 0 is never a candidate; spans that got no slot (table
+ * full) are never candidates, although their ERROR spans are in the cells and
+ * in error_spans.  A reclaim (sa_reclaim_keys, or the one a flush does once
+ * the table is more than half taken) empties the candidates while the cells
+ * stay: a caller that must not lose them asks before the flush that reclaims.
+ * Estimate: errors[i] is bit for bit what sa_window_range(e, first, last,
+ * &key_hash[i], 1, 0, ..) returns -- the minimum over the rows of the cells
+ * summed in u64 over first..last.
+ * Order: the n_matched candidates with an estimate >= max(min_count, 1),
+ * sorted by estimate descending, then key_hash ascending (sketch.heavy_hitters'
+ * order; a total order, so ties do not show); the first n = min(k, n_matched)
+ * of them are returned, in that order.
+ * Ordering and waiting as sa_window_range: joins every launch in flight, runs
+ * on the engine stream, waits, clears nothing (two calls give equal bits).
+ * SA_EINVAL for a null `out`, k == 0, k > SA_TOP_MAX_K, flags != 0 (reserved);
+ * SA_ERANGE as sa_window_range; SA_ENOMEM when the device scratch (16 bytes a
+ * table slot, allocated by the first call) or the result cannot be allocated.
+ * The engine stays usable after any error.  Free with sa_top_result_free. */
+int sa_window_top(sa_engine *e, uint64_t first, uint64_t last, uint32_t k, uint64_t min_count,
+                  uint32_t flags, sa_top_result **out);
+void sa_top_result_free(sa_top_result *r);
+
 int sa_get_stats(sa_engine *e, sa_stats *out);
 
 /* ---- multi-GPU merge hooks (device pointers on this engine's device) ----
@@ -457,6 +497,16 @@ int sa_group_window_advance(sa_group *g, uint64_t new_base);
  * queries.  Results equal those of one engine fed every span. */
 int sa_group_window_range(sa_group *g, uint64_t first, uint64_t last, const uint64_t *keys,
                           uint64_t n_keys, uint32_t flags, sa_range_result **out);
+/* sa_window_top of a group: the members merge their cells as for
+ * sa_group_window_range, every member scans its own key table against the
+ * merged cells (an estimate depends on the key and the merged cells only, so
+ * the group's first k are among the members' first k), and the host drops the
+ * repeats and cuts to k in the same order.  key_hash / errors equal those of
+ * one engine fed every span; n_resident and n_matched are summed over members
+ * (a series on several members counts once per member, as n_keys of
+ * sa_group_get_stats does). */
+int sa_group_window_top(sa_group *g, uint64_t first, uint64_t last, uint32_t k, uint64_t min_count,
+                        uint32_t flags, sa_top_result **out);
 /* Counters summed over members (n_keys and table_capacity too; window_base and
  * small_table from member 0). */
 int sa_group_get_stats(sa_group *g, sa_stats *out);

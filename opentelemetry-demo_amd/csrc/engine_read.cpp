@@ -281,6 +281,36 @@ int series_buffers(sa_engine *e, uint64_t n_out, uint64_t n_keys) {
     return rc;
   return series_grow(e, S.errors, S.err_cap, n_out * n_keys, "window series: answer buffer hipMalloc failed");
 }
+
+// ---- heavy hitters (sa_window_top; kernels in spanagg_range.hip) ----
+int top_buffers(sa_engine *e) {
+  sa_engine::Top &T = e->top;
+  if (!T.cand)
+    if (int rc = dalloc(e, T.cand, e->cap, false, "window top: candidate buffer hipMalloc failed")) return rc;
+  if (!T.ctl)
+    if (int rc = dalloc(e, T.ctl, 1, false, "window top: control block hipMalloc failed")) return rc;
+  return SA_OK;
+}
+
+// On `s`, not waited for: e's key table scanned against d_cells [d][w], the
+// first k matches selected and sorted, the counters and k rows copied into *h.
+int top_on(sa_engine *e, const unsigned long long *d_cells, uint32_t k, uint64_t min_count, hipStream_t s,
+           sa_grp::TopHost *h) {
+  const sa_engine::Top &T = e->top;
+  try {
+    h->rows.resize(k);
+  } catch (const std::bad_alloc &) {
+    return fail(e, SA_ENOMEM, "window top: the rows do not fit in host memory");
+  }
+  hipError_t st = sa::launch_top(e->gkeys, e->cap, e->binned.kinv, d_cells, e->cfg.cms_d, e->cfg.cms_w,
+                                 64 - sa::log2u(e->cfg.cms_w), e->d_seeds, k, std::max<uint64_t>(min_count, 1), T.cand,
+                                 T.ctl, s);
+  if (st == hipSuccess) st = hipMemcpyAsync(h->head, T.ctl, sizeof h->head, hipMemcpyDeviceToHost, s);
+  if (st == hipSuccess) st = hipMemcpyAsync(h->rows.data(), T.ctl->sel, (size_t)k * 16, hipMemcpyDeviceToHost, s);
+  if (st == hipSuccess) return SA_OK;
+  (void)hipStreamSynchronize(s);  // (a copy into h may be in flight)
+  return fail(e, SA_EDEVICE, std::string("window top: ") + hipGetErrorString(st));
+}
 }  // namespace
 
 namespace sa_grp {
@@ -324,7 +354,7 @@ int sync_stream(sa_engine *e) {
 
 int window_range_export_async(sa_engine *e, uint64_t first, uint64_t last, uint8_t *d_hll, uint64_t *d_cms,
                               hipStream_t s) {
-  if (!e || !d_hll || !d_cms) return SA_EINVAL;
+  if (!e || !d_cms) return SA_EINVAL;
   if (int rc = range_args(e, first, last, nullptr, 0, 0)) return rc;
   if (int rc = begin_read(e)) return rc;
   if (int rc = hop_to(e, s)) return rc;
@@ -343,6 +373,47 @@ int window_range_finish(sa_engine *e, uint64_t first, uint64_t last, const uint8
   SA_HIP(e, sa::launch_hll_hist(d_hll, e->cfg.n_services, e->cfg.hll_p, hist, s));
   return range_result(e, first, last, hist, d_hll, reinterpret_cast<const unsigned long long *>(d_cms), keys, n_keys,
                       flags, s, out);
+}
+
+int window_top_async(sa_engine *e, const uint64_t *d_cms, uint32_t k, uint64_t min_count, hipStream_t s, TopHost *out) {
+  if (!e || !d_cms || !out) return SA_EINVAL;
+  if (int rc = set_dev(e)) return rc;
+  if (int rc = top_buffers(e)) return rc;
+  // (the scratch is the engine's: after its own earlier use, before its next)
+  if (int rc = hop_to(e, s)) return rc;
+  if (int rc = top_on(e, reinterpret_cast<const unsigned long long *>(d_cms), k, min_count, s, out)) return rc;
+  return hop_back(e, s);
+}
+
+int top_result(uint64_t first, uint64_t last, uint32_t k, const TopHost *m, uint32_t n_members, sa_top_result **out) {
+  try {
+    std::unique_ptr<top_holder> h(new top_holder());
+    auto rows_of = [&](const TopHost &t) { return (size_t)std::min<uint64_t>(k, t.head[0]); };
+    if (n_members == 1) {  // the device's order, as it is
+      const size_t n = rows_of(m[0]);
+      h->shape(first, last, k, (uint32_t)n);
+      for (size_t i = 0; i < n; ++i) h->errors[i] = m[0].rows[i].x, h->keys[i] = m[0].rows[i].y;
+    } else {
+      // a series on several members has the same estimate on each: once
+      std::vector<std::pair<uint64_t, uint64_t>> all;  // (key, estimate)
+      for (uint32_t j = 0; j < n_members; ++j)
+        for (size_t i = 0; i < rows_of(m[j]); ++i) all.emplace_back(m[j].rows[i].y, m[j].rows[i].x);
+      std::sort(all.begin(), all.end());
+      all.erase(std::unique(all.begin(), all.end()), all.end());
+      std::sort(all.begin(), all.end(), [](const auto &a, const auto &b) {
+        return a.second != b.second ? a.second > b.second : a.first < b.first;
+      });
+      const size_t n = std::min<size_t>(k, all.size());
+      h->shape(first, last, k, (uint32_t)n);
+      for (size_t i = 0; i < n; ++i) h->keys[i] = all[i].first, h->errors[i] = all[i].second;
+    }
+    for (uint32_t j = 0; j < n_members; ++j) h->r.n_matched += m[j].head[0], h->r.n_resident += m[j].head[1];
+    h->r.error_spans = m[0].head[3];  // (the merged cells are the same on every member)
+    *out = &h.release()->r;
+    return SA_OK;
+  } catch (const std::bad_alloc &) {
+    return SA_ENOMEM;
+  }
 }
 }  // namespace sa_grp
 
@@ -626,6 +697,27 @@ int sa_window_series(sa_engine *e, uint64_t first, uint64_t last, uint32_t width
 }
 
 void sa_series_result_free(sa_series_result *r) { delete reinterpret_cast<series_holder *>(r); }
+
+int sa_window_top(sa_engine *e, uint64_t first, uint64_t last, uint32_t k, uint64_t min_count, uint32_t flags,
+                  sa_top_result **out) {
+  if (!e || !out) return SA_EINVAL;
+  *out = nullptr;
+  if (k == 0 || k > SA_TOP_MAX_K) return fail(e, SA_EINVAL, "window top: k outside 1..SA_TOP_MAX_K");
+  if (flags) return fail(e, SA_EINVAL, "window top: flags are reserved (0)");
+  if (int rc = range_args(e, first, last, nullptr, 0, 0)) return rc;
+  if (int rc = begin_read(e)) return rc;
+  if (int rc = range_buffers(e, 0, false, true)) return rc;
+  if (int rc = top_buffers(e)) return rc;
+  unsigned long long *cells = e->range.cells;
+  if (int rc = range_merge_on(e, first, last, nullptr, nullptr, cells, e->stream)) return rc;
+  sa_grp::TopHost th;
+  if (int rc = top_on(e, cells, k, min_count, e->stream, &th)) return rc;
+  SA_HIP(e, hipStreamSynchronize(e->stream));  // the call's one wait
+  if (int rc = sa_grp::top_result(first, last, k, &th, 1, out)) return fail(e, rc, "window top: the result does not fit in host memory");
+  return SA_OK;
+}
+
+void sa_top_result_free(sa_top_result *r) { delete reinterpret_cast<top_holder *>(r); }
 
 int sa_window_advance(sa_engine *e, uint64_t new_base) {
   if (!e) return SA_EINVAL;

@@ -208,6 +208,13 @@ struct sa_engine {
     uint64_t *keys = nullptr;
     uint64_t key_cap = 0, err_cap = 0;
   } series;
+  // sa_window_top (allocated by its first call): the matches as (estimate,
+  // key) pairs [cap] -- 16 bytes a table slot -- and the counters, the
+  // select's state and the k sorted rows (sa::TopCtl, 65 KiB whatever the table)
+  struct Top {
+    ulonglong2 *cand = nullptr;
+    sa::TopCtl *ctl = nullptr;
+  } top;
   // sa_ingest: two pinned host slots and their HBM copies; a slot is refilled
   // once its event (H2D copy + aggregation of the previous use) has passed
   struct HostStage {

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <vector>
 
 #include "spanagg.h"
 
@@ -31,8 +32,8 @@ int sync_stream(sa_engine *e);
 uint64_t table_capacity(const sa_engine *e);
 // sa_window_range's device part for one member, without the wait: every
 // window of first..last folded, then d_hll [n_services][2^p] = their registers
-// max-merged and d_cms [d][w] = their cells summed (u64), on `s`.  SA_ERANGE
-// as sa_window_range.
+// max-merged (nullptr: the cells only) and d_cms [d][w] = their cells summed
+// (u64), on `s`.  SA_ERANGE as sa_window_range.
 int window_range_export_async(sa_engine *e, uint64_t first, uint64_t last, uint8_t *d_hll, uint64_t *d_cms,
                               hipStream_t s);
 // the rest of a group's range query, on member 0 (`e`, whose device holds the
@@ -41,4 +42,22 @@ int window_range_export_async(sa_engine *e, uint64_t first, uint64_t last, uint8
 // sa_window_range.
 int window_range_finish(sa_engine *e, uint64_t first, uint64_t last, const uint8_t *d_hll, const uint64_t *d_cms,
                         const uint64_t *keys, uint64_t n_keys, uint32_t flags, hipStream_t s, sa_range_result **out);
+// What one engine's heavy-hitter scan leaves on the host once its stream
+// passes the copies: head = the matches, the resident keys, the largest
+// estimate, error_spans; rows [k] = (estimate, key) pairs, the first
+// min(k, head[0]) of them the engine's answer in order.
+struct TopHost {
+  unsigned long long head[4] = {};
+  std::vector<ulonglong2> rows;
+};
+// sa_window_top's device part for one member against the merged cells d_cms
+// [d][w] on its device, on `s`, without the wait: fills *out (which must stay
+// until `s` has been waited for).  k and min_count as sa_window_top.
+int window_top_async(sa_engine *e, const uint64_t *d_cms, uint32_t k, uint64_t min_count, hipStream_t s, TopHost *out);
+// The sa_top_result of n_members scans (each waited for): one member's rows
+// as they are; several members' merged -- repeats dropped, ordered by
+// (estimate descending, key ascending), cut to k -- with n_resident and
+// n_matched summed.  SA_ENOMEM when the result cannot be allocated.
+int top_result(uint64_t first, uint64_t last, uint32_t k, const TopHost *members, uint32_t n_members,
+               sa_top_result **out);
 }  // namespace sa_grp

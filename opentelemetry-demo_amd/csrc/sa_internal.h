@@ -443,6 +443,29 @@ hipError_t launch_series_query(const unsigned long long *cms, uint64_t slot_elem
 // out [n_in] = count-min row 0 of each window a .. a + n_in - 1, summed
 hipError_t launch_series_row0(const unsigned long long *cms, uint64_t slot_elems, uint32_t n_windows, uint64_t a,
                               uint32_t n_in, uint32_t w, unsigned long long *out, hipStream_t s);
+// heavy hitters over summed cells (sa_window_top; DESIGN.md section 4, "Heavy
+// hitters over the window ring").  kTopCellsLds: the scan stages cells [d][w]
+// in LDS up to this size -- 64 KiB, the default 4 x 2,048 sketch, two
+// workgroups in a CU's 160 KiB -- and reads larger ones through global memory.
+// kTopSel: pairs the final sort holds in one workgroup's LDS (16 B each).
+constexpr uint32_t kTopCellsLds = 65536;
+constexpr uint32_t kTopSel = 4096;  // = SA_TOP_MAX_K (asserted in spanagg_range.hip)
+constexpr uint32_t kTopDigits = 16;  // bytes of (estimate, key): the select's launches
+// The call's counters, the select's state and its output, on the device.
+struct TopCtl {
+  unsigned long long n_matched, n_resident, max_est, error_spans;  // (the host reads these four)
+  unsigned long long pref_est, pref_nkey;  // the class's resolved digits (estimate, ~key), the others zero
+  unsigned long long n_above, n_class;     // the gather's tickets
+  uint32_t level, need, want, done, ticket, pad[3];
+  uint32_t hist[256];
+  ulonglong2 sel[kTopSel];  // the gather's pairs; the first `want` sorted, after the sort
+};
+// The whole query on `s`: gkeys [cap] scanned against cells [d][w] into cand
+// [cap], then T->sel[0 .. min(k, T->n_matched)) = the first k matches by
+// (estimate descending, key ascending).  k <= kTopSel, min_count >= 1.
+hipError_t launch_top(const unsigned long long *gkeys, uint64_t cap, uint64_t kinv, const unsigned long long *cells,
+                      uint32_t d, uint32_t w, uint32_t shift, const uint64_t *seeds, uint32_t k,
+                      unsigned long long min_count, ulonglong2 *cand, TopCtl *T, hipStream_t s);
 // sorted union of series ids on the device (spanagg_union.hip): out = the
 // distinct non-zero ids of in[0..n) ascending, *d_total (device u32) their
 // count; scratch >= key_union_scratch_bytes(n); big_scratch / big_bytes: a

@@ -142,6 +142,18 @@ struct series_holder {
   }
 };
 
+struct top_holder {
+  sa_top_result r;
+  std::vector<uint64_t> keys, errors;
+  // the columns sized for n rows, and r pointing at them
+  __attribute__((visibility("hidden"))) void shape(uint64_t first, uint64_t last, uint32_t k, uint32_t n) {
+    keys.resize(n), errors.resize(n);
+    r.first_window = first, r.last_window = last, r.k = k, r.n = n;
+    r.n_resident = r.n_matched = r.error_spans = 0;
+    r.key_hash = keys.data(), r.errors = errors.data();
+  }
+};
+
 struct sketch_holder {
   sa_sketch_result r;
   std::vector<uint8_t> hll;

@@ -1127,6 +1127,60 @@ int sa_group_window_range(sa_group *g, uint64_t first, uint64_t last, const uint
   return SA_OK;
 }
 
+// The members' cells merged as for sa_group_window_range and left on every
+// member's device (RCCL's all-reduce leaves them there; the copy transport
+// copies member 0's sum back), then every member's scan and select against
+// them over its own key table, one wait per member, and the host's merge of
+// the members' rows.
+int sa_group_window_top(sa_group *g, uint64_t first, uint64_t last, uint32_t k, uint64_t min_count, uint32_t flags,
+                        sa_top_result **out) {
+  if (!g || !out) return SA_EINVAL;
+  *out = nullptr;
+  if (k == 0 || k > SA_TOP_MAX_K) return gfail(g, SA_EINVAL, "window top: k outside 1..SA_TOP_MAX_K");
+  if (flags) return gfail(g, SA_EINVAL, "window top: flags are reserved (0)");
+  const uint32_t n = (uint32_t)g->eng.size();
+  for (uint32_t i = 0; i < n; ++i) {
+    if (int rc = ensure(g, g->dev[i], g->cms[i], g->cms_elems * 8)) return rc;
+    if (int rc = sa_grp::window_range_export_async(g->eng[i], first, last, nullptr, static_cast<uint64_t *>(g->cms[i].p),
+                                                   g->st[i]))
+      return member_error(g, i, rc, "window top");
+  }
+  if (g->rccl) {
+    SG_NCCL(g, ncclGroupStart());
+    for (uint32_t i = 0; i < n; ++i)
+      SG_NCCL(g, ncclAllReduce(g->cms[i].p, g->cms[i].p, g->cms_elems, ncclUint64, ncclSum, g->comm[i], g->st[i]));
+    SG_NCCL(g, ncclGroupEnd());
+  } else if (n > 1) {
+    if (int rc = copy_reduce(g, g->cms, g->cms_elems, false)) return rc;  // (the members' streams are drained)
+    SG_HIP(g, hipSetDevice(g->dev[0]));
+    for (uint32_t i = 1; i < n; ++i) {
+      if (g->dev[i] == g->dev[0])
+        SG_HIP(g, hipMemcpyAsync(g->cms[i].p, g->cms[0].p, g->cms_elems * 8, hipMemcpyDeviceToDevice, g->st[0]));
+      else
+        SG_HIP(g, hipMemcpyPeerAsync(g->cms[i].p, g->dev[i], g->cms[0].p, g->dev[0], g->cms_elems * 8, g->st[0]));
+    }
+    SG_HIP(g, hipStreamSynchronize(g->st[0]));  // the sum is on every member before its scan starts
+  }
+  std::vector<sa_grp::TopHost> th(n);
+  int rc = SA_OK;
+  uint32_t started = 0;
+  for (; started < n && rc == SA_OK; ++started)
+    rc = sa_grp::window_top_async(g->eng[started], static_cast<const uint64_t *>(g->cms[started].p), k, min_count,
+                                  g->st[started], &th[started]);
+  const uint32_t failed = started - 1;  // (when rc != SA_OK)
+  hipError_t st = hipSuccess;
+  for (uint32_t i = 0; i < n; ++i) {  // (also after a failure: copies into th may be in flight)
+    hipError_t a = hipSetDevice(g->dev[i]);
+    if (a == hipSuccess) a = hipStreamSynchronize(g->st[i]);
+    if (st == hipSuccess) st = a;
+  }
+  if (rc) return member_error(g, failed, rc, "window top");
+  if (st != hipSuccess) return gfail(g, SA_EDEVICE, std::string("window top: ") + hipGetErrorString(st));
+  if (int rc2 = sa_grp::top_result(first, last, k, th.data(), n, out))
+    return gfail(g, rc2, "window top: the result does not fit in host memory");
+  return SA_OK;
+}
+
 int sa_group_window_advance(sa_group *g, uint64_t new_base) {
   if (!g) return SA_EINVAL;
   for (uint32_t i = 0; i < g->eng.size(); ++i)

@@ -22,10 +22,22 @@
 //   series_query_kernel  sliding sums of the keys' cells, their minimum per output.
 //   series_row0_kernel   count-min row 0 summed per window (error_spans).
 //
+// and for sa_window_top / sa_group_window_top, the heaviest series of the
+// summed cells among those resident in the key table:
+//
+//   top_scan_kernel      the key table against the cells: (estimate, key) of
+//                        every match, the resident keys, the largest estimate.
+//   top_prepare_kernel   error_spans and the select's first state.
+//   top_digit_kernel     one digit of the radix select over (estimate, ~key),
+//                        chosen on the device.
+//   top_gather_kernel    the selected pairs and the threshold's class.
+//   top_sort_kernel      their order, in one workgroup's LDS.
+//
 // Every result is an integer maximum or an integer sum, so the order of the
 // atomics does not show: two calls, and one engine against a group, give the
 // same bits.
 #include <algorithm>
+#include <cstddef>
 
 #include "sa_device.h"
 #include "spanagg.h"
@@ -392,7 +404,279 @@ __global__ __launch_bounds__(256) void series_row0_kernel(const unsigned long lo
   if (threadIdx.x == 0) out[blockIdx.x] = part[0];
 }
 
+// ---- heavy hitters (sa_window_top): the key table scanned against the summed
+// cells, the first k of (estimate descending, key ascending) selected ----
+constexpr uint32_t kTopScanBlock = 1024;  // 16 waves: two workgroups of 64 KiB of cells fill a CU's 32
+constexpr uint32_t kTopBlock = 256;       // the select's digit and gather kernels
+constexpr uint32_t kTopSortBlock = 1024;
+static_assert(kTopSel == SA_TOP_MAX_K, "the sort holds the largest k");
+
+// A candidate is the pair (estimate, key), ordered by estimate descending then
+// key ascending: as a 128-bit number (estimate, ~key) the largest comes first.
+// Its 16 bytes are the select's digits, 15 (the estimate's top byte) .. 0 (~key's
+// lowest).  top_high: the digits >= level kept, those below cleared.
+__device__ __forceinline__ void top_high(unsigned long long est, unsigned long long nkey, uint32_t level,
+                                         unsigned long long &he, unsigned long long &hk) {
+  if (level >= 16) {
+    he = 0, hk = 0;
+  } else if (level >= 8) {
+    const uint32_t sh = 8 * (level - 8);
+    he = (est >> sh) << sh, hk = 0;
+  } else {
+    const uint32_t sh = 8 * level;
+    he = est, hk = (nkey >> sh) << sh;
+  }
+}
+__device__ __forceinline__ uint32_t top_digit(unsigned long long est, unsigned long long nkey, uint32_t level) {
+  return (uint32_t)((level >= 8 ? est >> (8 * (level - 8)) : nkey >> (8 * level)) & 0xFFu);
+}
+
+// One returning atomic for the lanes of `m` (a ballot this lane is part of):
+// the wave's first position from *counter, this lane's own behind it.
+__device__ __forceinline__ unsigned long long wave_ticket(unsigned long long *counter, uint64_t m) {
+  const int leader = __builtin_ctzll(m);
+  unsigned long long base = 0;
+  if ((int)(threadIdx.x & 63u) == leader) base = atomicAdd(counter, (unsigned long long)__popcll(m));
+  base = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(base >> 32), leader) << 32) |
+         (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)base, leader);
+  return base + lane_rank(m);
+}
+
+// Walks gkeys[0..cap) once.  A slot's key is recovered as fold_errcnt_slots
+// does (stored id * kinv; a dense engine's bound hash, 0 when unbound); its
+// estimate is the minimum over the rows of cells [d][w] -- staged in LDS
+// (LDS = 1: d * w * 8 <= kTopCellsLds dynamic bytes) or read through global
+// memory.  Keys with an estimate >= min_count (>= 1) leave as (estimate, key)
+// into cand [cap] through one returning atomic per wave (compact_kernel's
+// idiom); T counts the resident keys, the matches and the largest estimate.
+template <int LDS>
+__global__ __launch_bounds__(kTopScanBlock) void top_scan_kernel(const unsigned long long *gkeys, uint64_t cap,
+                                                                 uint64_t kinv, const unsigned long long *cells,
+                                                                 uint32_t d, uint32_t w, uint32_t shift,
+                                                                 const uint64_t *seeds, unsigned long long min_count,
+                                                                 ulonglong2 *cand, TopCtl *T) {
+  extern __shared__ unsigned long long top_cells[];
+  const unsigned long long *c = cells;
+  if constexpr (LDS) {
+    for (uint32_t i = threadIdx.x; i < d * w; i += kTopScanBlock) top_cells[i] = cells[i];
+    __syncthreads();
+    c = top_cells;
+  }
+  uint64_t sd[8];  // (cms_d <= 8)
+#pragma unroll
+  for (uint32_t r = 0; r < 8; ++r) sd[r] = r < d ? seeds[r] : 0;
+  uint32_t resident = 0;
+  unsigned long long largest = 0;
+  for (uint64_t s = blockIdx.x * (uint64_t)kTopScanBlock + threadIdx.x; s < cap;
+       s += (uint64_t)gridDim.x * kTopScanBlock) {
+    const uint64_t key = gkeys[s] * kinv;
+    if (!key) continue;
+    ++resident;
+    unsigned long long est = ~0ULL;
+#pragma unroll
+    for (uint32_t r = 0; r < 8; ++r) {
+      if (r < d) {
+        const uint64_t col = splitmix64(key ^ sd[r]) >> shift;  // < w: shift = 64 - log2 w, w >= 2
+        const unsigned long long v = c[(uint64_t)r * w + col];
+        est = v < est ? v : est;
+      }
+    }
+    if (est < min_count) continue;
+    largest = est > largest ? est : largest;
+    const unsigned long long pos = wave_ticket(&T->n_matched, __ballot(true));
+    if (pos < cap) cand[pos] = ulonglong2{est, key};  // (a table holds a key once: at most cap matches)
+  }
+  resident = wave_sum(resident);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long other = ((unsigned long long)(uint32_t)__shfl_xor((int)(uint32_t)(largest >> 32), o, 64) << 32) |
+                                     (uint32_t)__shfl_xor((int)(uint32_t)largest, o, 64);
+    largest = other > largest ? other : largest;
+  }
+  if ((threadIdx.x & 63u) == 0) {
+    if (resident) atomicAdd(&T->n_resident, (unsigned long long)resident);
+    if (largest) atomicMax(&T->max_est, largest);
+  }
+}
+
+// After the scan (one workgroup): error_spans = the sum of row 0 of the
+// cells, and the select's first state.  At most kTopSel matches: nothing to
+// select (level 16: no digit resolved, every match is in the class).
+// Otherwise the first digit is the top non-zero byte of the largest estimate.
+__global__ __launch_bounds__(kTopBlock) void top_prepare_kernel(const unsigned long long *cells, uint32_t w, uint32_t k,
+                                                                TopCtl *T) {
+  __shared__ unsigned long long part[kTopBlock];
+  unsigned long long acc = 0;
+  for (uint32_t i = threadIdx.x; i < w; i += kTopBlock) acc += cells[i];
+  part[threadIdx.x] = acc;
+  __syncthreads();
+  for (uint32_t s = kTopBlock / 2; s > 0; s >>= 1) {
+    if (threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x) return;
+  T->error_spans = part[0];
+  const unsigned long long n = T->n_matched;
+  const uint32_t want = (uint32_t)(n < k ? n : k);
+  T->want = want, T->need = want;
+  T->pref_est = 0, T->pref_nkey = 0;
+  T->done = n <= kTopSel ? 1u : 0u;
+  T->level = n <= kTopSel ? 16u : 8u + (63u - (uint32_t)__clzll((long long)T->max_est)) / 8u;
+}
+
+// One digit of the radix select, chosen on the device.  The class is the
+// matches whose digits above T->level equal the prefix; `need` of the class's
+// largest are still to be found.  Every workgroup counts its stripe of the
+// class by the digit at T->level (LDS, then one atomic per non-zero bin); the
+// last one to finish walks the bins from 255 down to the bin b the need-th
+// largest falls in: the bins above b are selected whole, b joins the prefix,
+// need shrinks by what was above.  Done once the selected matches and the new
+// class fit the sort (kTopSel) or digit 0 is resolved; a launch after that
+// returns at once.  T->hist and T->ticket are zero between launches.
+__global__ __launch_bounds__(kTopBlock) void top_digit_kernel(const ulonglong2 *cand, TopCtl *T) {
+  __shared__ uint32_t h[256];
+  __shared__ uint32_t last;
+  if (T->done) return;  // (every workgroup reads the state before the last one changes it)
+  const uint32_t level = T->level;
+  const unsigned long long pe = T->pref_est, pk = T->pref_nkey, n = T->n_matched;
+  h[threadIdx.x] = 0;
+  __syncthreads();
+  for (uint64_t i = blockIdx.x * (uint64_t)kTopBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kTopBlock) {
+    const ulonglong2 c = cand[i];
+    unsigned long long he, hk;
+    top_high(c.x, ~c.y, level + 1, he, hk);
+    if (he != pe || hk != pk) continue;
+    // ties put a whole wave on one bin: the lanes that share the first lane's
+    // digit leave as one add, the others one by one
+    const uint32_t dg = top_digit(c.x, ~c.y, level);
+    const uint32_t d0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)dg);
+    const uint64_t same = __ballot(dg == d0);
+    if (dg != d0)
+      atomicAdd(&h[dg], 1u);
+    else if (lane_rank(same) == 0)
+      atomicAdd(&h[d0], (uint32_t)__popcll(same));
+  }
+  __syncthreads();
+  if (h[threadIdx.x]) atomicAdd(&T->hist[threadIdx.x], h[threadIdx.x]);
+  __threadfence();
+  __syncthreads();
+  if (threadIdx.x == 0) last = atomicAdd(&T->ticket, 1u) == gridDim.x - 1 ? 1u : 0u;
+  __syncthreads();
+  if (!last) return;
+  __threadfence();
+  h[threadIdx.x] = __hip_atomic_load(&T->hist[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  T->hist[threadIdx.x] = 0;
+  __syncthreads();
+  if (threadIdx.x) return;
+  T->ticket = 0;
+  uint32_t need = T->need, above = 0, b = 255;
+  for (;; --b) {  // (the class holds at least `need`: some bin reaches it)
+    if (above + h[b] >= need || b == 0) break;
+    above += h[b];
+  }
+  need -= above;
+  T->need = need;
+  if (level >= 8)
+    T->pref_est = pe | ((unsigned long long)b << (8 * (level - 8)));
+  else
+    T->pref_nkey = pk | ((unsigned long long)b << (8 * level));
+  if (level == 0 || (unsigned long long)(T->want - need) + h[b] <= kTopSel)
+    T->done = 1;
+  else
+    T->level = level - 1;
+}
+
+// The matches above the class (digits >= T->level greater than the prefix)
+// into T->sel from the front, the class itself from the back; a class member
+// that would meet the front is dropped (only when digit 0 left equal pairs:
+// they are interchangeable).
+__global__ __launch_bounds__(kTopBlock) void top_gather_kernel(const ulonglong2 *cand, TopCtl *T) {
+  const uint32_t level = T->level;
+  const unsigned long long pe = T->pref_est, pk = T->pref_nkey, n = T->n_matched;
+  const unsigned long long room = kTopSel - (T->want - T->need);  // the class's share of sel
+  for (uint64_t i = blockIdx.x * (uint64_t)kTopBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kTopBlock) {
+    const ulonglong2 c = cand[i];
+    unsigned long long he, hk;
+    top_high(c.x, ~c.y, level, he, hk);
+    const bool above = he > pe || (he == pe && hk > pk), in_class = he == pe && hk == pk;
+    if (above) {
+      const unsigned long long pos = wave_ticket(&T->n_above, __ballot(true));
+      if (pos < kTopSel) T->sel[pos] = c;
+    } else if (in_class) {
+      const unsigned long long pos = wave_ticket(&T->n_class, __ballot(true));
+      if (pos < room) T->sel[kTopSel - 1 - pos] = c;
+    }
+  }
+}
+
+// One workgroup: T->sel's two ends into LDS, padded to a power of two with
+// pairs that sort last, a bitonic sort by (estimate descending, key
+// ascending), and the first T->want back to the front of T->sel.
+__global__ __launch_bounds__(kTopSortBlock) void top_sort_kernel(TopCtl *T) {
+  extern __shared__ ulonglong2 top_sel[];  // [kTopSel]
+  const uint32_t na = (uint32_t)min(T->n_above, (unsigned long long)kTopSel);
+  const uint32_t nc = (uint32_t)min(T->n_class, (unsigned long long)(kTopSel - na));
+  const uint32_t n = na + nc, want = min(T->want, n);
+  uint32_t P = 64;
+  while (P < n) P <<= 1;
+  for (uint32_t i = threadIdx.x; i < P; i += kTopSortBlock)
+    top_sel[i] = i < na ? T->sel[i] : i < n ? T->sel[kTopSel - 1 - (i - na)] : ulonglong2{0ULL, ~0ULL};
+  __syncthreads();
+  for (uint32_t k2 = 2; k2 <= P; k2 <<= 1) {
+    for (uint32_t j = k2 >> 1; j > 0; j >>= 1) {
+      for (uint32_t i = threadIdx.x; i < P; i += kTopSortBlock) {
+        const uint32_t o = i ^ j;
+        if (o > i) {
+          const ulonglong2 a = top_sel[i], b = top_sel[o];
+          const bool b_first = b.x > a.x || (b.x == a.x && b.y < a.y);
+          if (b_first == ((i & k2) == 0)) top_sel[i] = b, top_sel[o] = a;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  for (uint32_t i = threadIdx.x; i < want; i += kTopSortBlock) T->sel[i] = top_sel[i];
+}
+
 }  // namespace
+
+// The scan's grid: 4 slots a thread, at most two workgroups a CU's worth (they stride)
+static uint32_t top_scan_grid(uint64_t cap) {
+  return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, (cap + 4 * kTopScanBlock - 1) / (4 * kTopScanBlock)), 512);
+}
+
+hipError_t launch_top(const unsigned long long *gkeys, uint64_t cap, uint64_t kinv, const unsigned long long *cells,
+                      uint32_t d, uint32_t w, uint32_t shift, const uint64_t *seeds, uint32_t k,
+                      unsigned long long min_count, ulonglong2 *cand, TopCtl *T, hipStream_t s) {
+  if (hipError_t e = hipMemsetAsync(T, 0, offsetof(TopCtl, sel), s); e != hipSuccess) return e;
+  const size_t cell_bytes = (size_t)d * w * 8;
+  if (cell_bytes <= kTopCellsLds) {
+    if (hipError_t e = hipFuncSetAttribute((const void *)&top_scan_kernel<1>,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTopCellsLds);
+        e != hipSuccess)
+      return e;
+    hipLaunchKernelGGL(top_scan_kernel<1>, dim3(top_scan_grid(cap)), dim3(kTopScanBlock), cell_bytes, s, gkeys, cap,
+                       kinv, cells, d, w, shift, seeds, min_count, cand, T);
+  } else {
+    hipLaunchKernelGGL(top_scan_kernel<0>, dim3(top_scan_grid(cap)), dim3(kTopScanBlock), 0, s, gkeys, cap, kinv, cells,
+                       d, w, shift, seeds, min_count, cand, T);
+  }
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  hipLaunchKernelGGL(top_prepare_kernel, dim3(1), dim3(kTopBlock), 0, s, cells, w, k, T);
+  // the select's workgroups stride the matches (at most cap); every digit's
+  // launch is enqueued, the device decides which ones work
+  const uint32_t grid = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, (cap + 8 * kTopBlock - 1) / (8 * kTopBlock)), 1024);
+  for (uint32_t digit = 0; digit < kTopDigits; ++digit)
+    hipLaunchKernelGGL(top_digit_kernel, dim3(grid), dim3(kTopBlock), 0, s, cand, T);
+  hipLaunchKernelGGL(top_gather_kernel, dim3(grid), dim3(kTopBlock), 0, s, cand, T);
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  if (hipError_t e = hipFuncSetAttribute((const void *)&top_sort_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int)(kTopSel * sizeof(ulonglong2)));
+      e != hipSuccess)
+    return e;
+  hipLaunchKernelGGL(top_sort_kernel, dim3(1), dim3(kTopSortBlock), kTopSel * sizeof(ulonglong2), s, T);
+  return hipGetLastError();
+}
 
 // The tile and the stash of a width.  Up to 32 windows the whole block's
 // suffix maxima fit kSeriesStashBytes at 64 columns (chunk = width).  Above,

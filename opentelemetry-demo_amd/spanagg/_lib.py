@@ -97,6 +97,17 @@ class sa_series_result(C.Structure):
     ]
 
 
+SA_TOP_MAX_K = TOP_MAX_K = 4096
+
+
+class sa_top_result(C.Structure):
+    _fields_ = [
+        ("first_window", C.c_uint64), ("last_window", C.c_uint64), ("k", C.c_uint32), ("n", C.c_uint32),
+        ("n_resident", C.c_uint64), ("n_matched", C.c_uint64), ("error_spans", C.c_uint64),
+        ("key_hash", u64p), ("errors", u64p),
+    ]
+
+
 class sa_stats(C.Structure):
     _fields_ = [
         ("spans", C.c_uint64), ("zero_key", C.c_uint64), ("invalid_service", C.c_uint64),
@@ -159,6 +170,11 @@ SIGNATURES = [
     ("sa_window_series", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, u64p, C.c_uint64, C.c_uint32,
                                    C.POINTER(C.POINTER(sa_series_result))]),
     ("sa_series_result_free", None, [C.POINTER(sa_series_result)]),
+    ("sa_window_top", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32,
+                                C.POINTER(C.POINTER(sa_top_result))]),
+    ("sa_group_window_top", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32,
+                                      C.POINTER(C.POINTER(sa_top_result))]),
+    ("sa_top_result_free", None, [C.POINTER(sa_top_result)]),
     ("sa_hll_estimate_hist", C.c_double, [u32p, C.c_uint32]),
     ("sa_get_stats", C.c_int, [C.c_void_p, C.POINTER(sa_stats)]),
     ("sa_bind_ids", C.c_int, [C.c_void_p, u64p, u64p, C.c_uint64]),

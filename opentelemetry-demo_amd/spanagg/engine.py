@@ -178,6 +178,23 @@ class SeriesResult:
         return est[:k]
 
 
+@dataclass
+class TopResult:
+    """sa_top_result: the heaviest ERROR series of windows first..last among the
+    series resident in the engine's key table, by the summed count-min."""
+    first: int
+    last: int
+    keys: np.ndarray              # [n] u64, by estimate descending then key ascending
+    errors: np.ndarray            # [n] u64: window_range(first, last, [keys[i]]).errors[0]
+    n_resident: int               # series in the key table when the call ran: the candidates
+    n_matched: int                # candidates with an estimate >= min_count
+    error_spans: int              # ERROR spans the range's sketches counted, exact
+
+    def items(self):
+        """[(key, estimate)] as sketch.heavy_hitters returns them."""
+        return [(int(k), int(e)) for k, e in zip(self.keys, self.errors)]
+
+
 def hll_estimate(regs: np.ndarray, p: int) -> float:
     lib = _lib.load()
     r = np.ascontiguousarray(regs, dtype=np.uint8)
@@ -274,6 +291,20 @@ def _window_range(obj, fn, what, first, last, keys, registers, cells) -> RangeRe
             k, p)
     finally:
         obj.lib.sa_range_result_free(out)
+
+
+def _window_top(obj, fn, what, first, last, k, min_count) -> TopResult:
+    """sa_window_top / sa_group_window_top -> TopResult (copies), freeing the library's result."""
+    out = C.POINTER(_lib.sa_top_result)()
+    obj._check(fn(obj._h, int(first), int(last), int(k), int(min_count), 0, C.byref(out)), what)
+    try:
+        r = out.contents
+        n = int(r.n)
+        col = lambda p: np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, np.uint64)
+        return TopResult(int(r.first_window), int(r.last_window), col(r.key_hash), col(r.errors),
+                         int(r.n_resident), int(r.n_matched), int(r.error_spans))
+    finally:
+        obj.lib.sa_top_result_free(out)
 
 
 def _ptr(x) -> int:
@@ -459,6 +490,13 @@ class Engine:
         finally:
             self.lib.sa_series_result_free(out)
 
+    def window_top(self, first: int, last: int, k: int = 10, min_count: int = 1) -> TopResult:
+        """sa_window_top: the k series with the largest estimate of the
+        count-min summed over windows first..last, among the series resident
+        in the key table (those seen since the last reclaim) with an estimate
+        >= min_count -- scanned, selected and sorted on the device."""
+        return _window_top(self, self.lib.sa_window_top, "sa_window_top", first, last, k, min_count)
+
     def flush_exp(self, allow_drops: bool = False) -> ExpoResult:
         out = C.POINTER(_lib.sa_exp_result)()
         rc = self.lib.sa_flush_exp(self._h, C.byref(out))
@@ -631,6 +669,11 @@ class Group:
         """sa_group_window_range: Engine.window_range over the members' merge."""
         return _window_range(self, self.lib.sa_group_window_range, "sa_group_window_range", first, last, keys,
                              registers, cells)
+
+    def window_top(self, first: int, last: int, k: int = 10, min_count: int = 1) -> TopResult:
+        """sa_group_window_top: Engine.window_top over the members' merge
+        (n_resident and n_matched summed over the members)."""
+        return _window_top(self, self.lib.sa_group_window_top, "sa_group_window_top", first, last, k, min_count)
 
     def window_advance(self, new_base: int):
         self._check(self.lib.sa_group_window_advance(self._h, int(new_base)), "sa_group_window_advance")
