@@ -70,7 +70,7 @@ int read_stats(sa_engine *e, uint64_t out[sa::kNumStats]) {
 }
 
 // Derive the count-min cells of window slot ws from its exact per-slot error
-// counts (see sketch_post in spanagg_kernels.hip).
+// counts (see sketch_post in sa_device.h).
 int fold_errslab(sa_engine *e, uint64_t ws, hipStream_t s) {
   if (!e->small.errslab) return SA_OK;
   SA_HIP(e, sa::launch_reduce_errslab(e->small.errslab, e->G * e->order.nsets, (uint64_t)e->cfg.n_windows * e->cap, ws,

@@ -1,7 +1,8 @@
 // sa_device.h -- device-side helpers shared by the gfx950 kernels of libspanagg
-// (spanagg_kernels.hip: small-table, HBM-table and round-1 partitioned paths;
-// spanagg_binned.hip, spanagg_dense.hip: the binned-table high-cardinality
-// path and its dense-index form).
+// (spanagg_kernels.hip: the small-table path; spanagg_part.hip: the HBM-table
+// and round-1 partitioned paths; spanagg_table.hip: the flush-time table
+// kernels; spanagg_binned.hip, spanagg_dense.hip: the binned-table
+// high-cardinality path and its dense-index form).
 #pragma once
 #include "sa_internal.h"
 

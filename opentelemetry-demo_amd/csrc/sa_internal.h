@@ -357,16 +357,13 @@ constexpr uint32_t kDbgPerWg = 136;  // diagnostic stamps per workgroup: 8 + 16 
 // the last slots of the wave rows
 constexpr uint32_t kXcStamp = 4, kXcStampSlab = kDbgPerWg - 1, kXcStampZeroed = kDbgPerWg - 9,
                    kXcStampSelected = kDbgPerWg - 17, kXcStampTail = kDbgPerWg - 25;
-// (kHllQueue, kErrTab, kLdsExtraBytes: sa_path.h)
+// (kHllQueue, kErrTab, small_lds_layout, kLdsExtraBytes: sa_path.h)
 
-// launchers (spanagg_kernels.hip).  Small tables: the engine's kernel k
-// (sa_path.h), block small_block(k); diag (laboratory build only): the
+// launchers of the small-table path (spanagg_kernels.hip): the engine's kernel
+// k (sa_path.h), block small_block(k); diag (laboratory build only): the
 // ablation instance in its place, which has Generic1024's geometry.
 hipError_t launch_ingest_small(const IngestParams &P, uint32_t grid, size_t lds_bytes, hipStream_t s, SmallKernel k,
                                bool diag);
-hipError_t launch_ingest_hbm(const IngestParams &P, uint32_t grid, hipStream_t s);
-hipError_t launch_ingest_part(const IngestParams &P, hipStream_t s);
-hipError_t prepare_ingest_part();
 hipError_t prepare_ingest_small(size_t lds_bytes);
 void ingest_small_node(uint32_t grid, size_t lds_bytes, SmallKernel k, void **args, hipKernelNodeParams *np);
 uint32_t ingest_small_blocks_per_cu(SmallKernel k, bool diag, size_t lds_bytes);
@@ -376,6 +373,15 @@ uint32_t ingest_small_blocks_per_cu(SmallKernel k, bool diag, size_t lds_bytes);
 hipError_t prepare_ingest_expo_small(size_t lds_bytes);
 hipError_t launch_ingest_expo_small(const IngestParams &P, uint32_t grid, size_t lds_bytes, hipStream_t s);
 uint32_t ingest_expo_blocks_per_cu(uint32_t log2cap, uint32_t p, size_t lds_bytes);
+// HBM-table paths (spanagg_part.hip): per-span atomics, round-1 partitioned
+hipError_t launch_ingest_hbm(const IngestParams &P, uint32_t grid, hipStream_t s);
+hipError_t launch_ingest_part(const IngestParams &P, hipStream_t s);
+hipError_t prepare_ingest_part();
+// flush-time table kernels (spanagg_table.hip)
+hipError_t launch_reduce_errslab(uint32_t *errslab, uint32_t G, uint64_t per_wg, uint64_t ws,
+                                 uint32_t log2cap, unsigned long long *errcnt_ws, hipStream_t s);
+hipError_t launch_count_keys(const unsigned long long *gkeys, uint64_t cap,
+                             unsigned long long *out, hipStream_t s);
 hipError_t launch_reduce_slabs(uint32_t *slab_cnt, unsigned long long *slab_sum,
                                unsigned long long *gcounts, uint32_t G, uint64_t cap,
                                uint32_t nbk, hipStream_t s);
@@ -404,10 +410,6 @@ hipError_t launch_dn_scatter(const IngestParams &P, hipStream_t s);
 hipError_t launch_dn_aggregate(const IngestParams &P, hipStream_t s);
 hipError_t launch_dn_bind(unsigned long long *gkeys, const uint64_t *index, const uint64_t *key_hash, uint64_t n,
                           uint32_t log2sb, hipStream_t s);
-hipError_t launch_reduce_errslab(uint32_t *errslab, uint32_t G, uint64_t per_wg, uint64_t ws,
-                                 uint32_t log2cap, unsigned long long *errcnt_ws, hipStream_t s);
-hipError_t launch_count_keys(const unsigned long long *gkeys, uint64_t cap,
-                             unsigned long long *out, hipStream_t s);
 // range queries over the window ring (spanagg_range.hip): windows first ..
 // first + n_win - 1 of a ring of n_windows slots (slot = window & (n_windows - 1)).
 // hist [n_services][SA_HLL_HIST_BINS] (zeroed by the caller; nullptr: none): the

@@ -38,11 +38,42 @@ constexpr uint32_t kPartMaxBk = 17;       // LDS counter row: nbk <= 17 (default
 
 constexpr uint32_t kHllQueue = 2048;  // deferred HLL raises per workgroup (8 B each)
 constexpr uint32_t kErrTab = 1024;    // LDS (window, slot) -> ERROR count table per workgroup (4 B each)
-// small-table kernels' LDS beyond the table: HLL queue + its count + bin table
-// (+ the ERROR table and HLL bounds of the v2 kernels)
-// (+ 64 B reserved: no kernel uses them, but the path decision's thresholds
-// and every recorded geometry count them)
-constexpr size_t kLdsExtraBytes = kHllQueue * 8 + 32 + kBins * sizeof(BinEntry) + kErrTab * 4 + kLbMaxSub + 64;
+// The small-table kernels' dynamic LDS: its regions in order, for a table of
+// `cap` slots with `nw` u32 counter words per slot (EXPO: nw = 6, so sums +
+// counters are the 32-B header partials of a slot).  The one list behind
+// decide_path's sizes and kLdsExtraBytes; the kernels' carve (small_lds_carve,
+// spanagg_kernels.hip) steps over the same regions by their element counts,
+// with pointer types whose sizes it asserts to be the `elem` given here.
+// ingest_lds_kernel uses the head, up to the control block's first word.
+struct LdsRegion {
+  size_t n, elem;  // n elements of elem bytes
+};
+enum { kLdsKeys, kLdsSums, kLdsCnt, kLdsHq, kLdsCtl, kLdsBins, kLdsErr, kLdsLb, kLdsScale, kLdsReserved, kLdsRegions };
+struct SmallLdsLayout {
+  LdsRegion r[kLdsRegions];
+  constexpr size_t end() const {
+    size_t e = 0;
+    for (const LdsRegion &x : r) e += x.n * x.elem;
+    return e;
+  }
+};
+constexpr SmallLdsLayout small_lds_layout(size_t cap, size_t nw, bool expo) {
+  return {{{cap, 8},                      // key mirror
+           {cap, 8},                      // ns sums
+           {cap * nw, 4},                 // counters
+           {kHllQueue, 8},                // HLL queue
+           {8, 4},                        // control block: hq_n[4] + lstat[4]
+           {kBins, sizeof(BinEntry)},     // bin table
+           {kErrTab, 4},                  // ERROR table
+           {kLbMaxSub, 1},                // HLL bounds
+           {expo ? cap : 0, 1},           // EXPO: the index records' per-slot scales
+           // no kernel uses these, but the path decision's thresholds and
+           // every recorded geometry count them
+           {64, 1}}};
+}
+constexpr size_t kExpoWords = 6;  // the EXPO kernel's nw
+// the LDS beyond the table (what the layout of an empty table holds)
+constexpr size_t kLdsExtraBytes = small_lds_layout(0, 0, false).end();
 constexpr size_t kLdsBudget = 144 * 1024;  // small-table path LDS ceiling per workgroup
 
 inline uint32_t log2u(uint64_t x) { return 63u - (uint32_t)__builtin_clzll(x); }
@@ -150,12 +181,10 @@ struct PathChoice {
 // The path of a validated config with `cap` table slots (config_table_slots).
 inline PathChoice decide_path(const sa_config &c, const Hist &h, uint64_t cap) {
   const bool expo = c.exp_max_size != 0;
-  // lkeys + lsum + lcnt + deferred-HLL queue (+ its counter), see ingest_lds_kernel
-  const size_t lds = (size_t)cap * 16 + (size_t)cap * ((h.nbk + 1) / 2) * 4 + kLdsExtraBytes;
+  const size_t lds = small_lds_layout(cap, (h.nbk + 1) / 2, false).end();
   if (lds <= kLdsBudget && !expo) return {Path::Small, lds};
-  if (expo) {  // key mirror + 32-B header partials per slot (nw = 6 counter words)
-    // (+ cap: the index records' per-slot scales)
-    const size_t xl = (size_t)cap * 8 + (size_t)cap * 32 + kLdsExtraBytes + (size_t)cap;
+  if (expo) {
+    const size_t xl = small_lds_layout(cap, kExpoWords, true).end();
     if (xl <= kLdsBudget && !(c.options & SA_OPT_EXPO_HBM)) return {Path::ExpoSmall, xl};
     return {Path::ExpoHbm, lds};
   }

@@ -16,18 +16,72 @@
 //   * HBM-table path (high cardinality): lock-free CAS insert + u64 atomics;
 //   * HLL: u8 registers in HBM, read-filtered, CAS-max only when rho grows;
 //   * count-min: u64 cells, atomic add per ERROR span per row.
-#include <algorithm>
-
+// (the HBM-table kernels: spanagg_part.hip; the flush-time table kernels:
+// spanagg_table.hip)
 #include "sa_device.h"
 
 namespace sa {
 namespace {
 
 // ---------------------------------------------------------------------------
-// Small-table path.  LDS layout (dynamic, 16-B aligned):
+// Small-table path.  LDS layout (dynamic, 16-B aligned; sa_path.h
+// small_lds_layout lists the regions and sizes the launch from them):
 //   lkeys [cap] u64   mirror of the HBM key table (same slot positions)
 //   lsum  [cap] u64   per-slot ns sum of this epoch
 //   lcnt  [cap][nw] u32, nw = ceil(nbk/2): two u16 bucket counters per word
+//   hq    [kHllQueue] (hoff, rho) deferred HLL raises
+//   hq_n  [4] the queue's fill, the next chunk claim, the filtered HLL updates
+//   lstat [4] LEAN event counts (zero key, bad service, out of ring, dropped)
+//   lbins [kBins] bucket bin table
+//   etab  [kErrTab] (key + 1) << 16 | count of the ERROR spans
+//   llb   [kLbMaxSub] HLL lower bounds
+//   lsc   [cap] EXPO with index records: each slot's scale at the kernel's start
+// (ingest_lds_kernel uses lkeys .. hq_n[0])
+struct SmallLds {
+  unsigned long long *lkeys, *lsum;
+  uint32_t *lcnt;
+  uint2 *hq;
+  uint32_t *hq_n, *lstat;
+  BinEntry *lbins;
+  uint32_t *etab;
+  uint8_t *llb;
+  int8_t *lsc;
+};
+// Each pointer starts where the one before ends: typed pointer arithmetic over
+// the host list's element counts (the compiler folds this form best).
+__device__ __forceinline__ SmallLds small_lds_carve(unsigned char *smem, uint32_t cap, uint32_t nw, bool expo) {
+  const SmallLdsLayout R = small_lds_layout(cap, nw, expo);
+  auto n = [&](int region) { return (uint32_t)R.r[region].n; };
+  SmallLds L;
+  L.lkeys = reinterpret_cast<unsigned long long *>(smem);
+  L.lsum = L.lkeys + n(kLdsKeys);
+  L.lcnt = reinterpret_cast<uint32_t *>(L.lsum + n(kLdsSums));
+  L.hq = reinterpret_cast<uint2 *>(L.lcnt + n(kLdsCnt));
+  L.hq_n = reinterpret_cast<uint32_t *>(L.hq + n(kLdsHq));
+  L.lstat = L.hq_n + 4;  // the control block's second half
+  L.lbins = reinterpret_cast<BinEntry *>(L.hq_n + n(kLdsCtl));
+  L.etab = reinterpret_cast<uint32_t *>(L.lbins + n(kLdsBins));
+  L.llb = reinterpret_cast<uint8_t *>(L.etab + n(kLdsErr));
+  L.lsc = reinterpret_cast<int8_t *>(L.llb + n(kLdsLb));
+  return L;
+}
+// The carve ends where the host's size does (SmallLdsLayout::end) when every
+// step is as wide as the list says: for any geometry, so for the compile-time
+// ones (LC 11 / NWC 9, the EXPO LC 11) too.  lsc + its count + the reserved
+// tail is the end; nothing is carved after it.
+constexpr bool small_lds_steps_match() {
+  constexpr SmallLdsLayout R = small_lds_layout(1u << 11, 9, true);
+  return sizeof(*SmallLds{}.lkeys) == R.r[kLdsKeys].elem && sizeof(*SmallLds{}.lsum) == R.r[kLdsSums].elem &&
+         sizeof(*SmallLds{}.lcnt) == R.r[kLdsCnt].elem && sizeof(*SmallLds{}.hq) == R.r[kLdsHq].elem &&
+         sizeof(*SmallLds{}.hq_n) == R.r[kLdsCtl].elem && sizeof(*SmallLds{}.lbins) == R.r[kLdsBins].elem &&
+         sizeof(*SmallLds{}.etab) == R.r[kLdsErr].elem && sizeof(*SmallLds{}.llb) == R.r[kLdsLb].elem &&
+         sizeof(*SmallLds{}.lsc) == R.r[kLdsScale].elem && kLdsScale + 2 == kLdsRegions;
+}
+static_assert(small_lds_steps_match(), "small_lds_carve's pointer types vs. sa_path.h small_lds_layout");
+static_assert(small_lds_layout(1u << 11, 9, false).end() == 2048 * 52 + kLdsExtraBytes &&
+                  small_lds_layout(1u << 11, kExpoWords, true).end() == 2048 * 41 + kLdsExtraBytes,
+              "the compile-time geometries' LDS");
+
 // The workgroup's HBM slab is [cap][2*nw] u32 (+ [cap] u64 sums): LDS word w
 // maps to slab cells 2w and 2w+1, so a pair of LDS words is one 16-B slab
 // vector and the flush is a vectorised read-modify-write of touched cells.
@@ -112,6 +166,22 @@ __device__ __forceinline__ void epi_raise_and_bound(const PT &P, const uint2 *hq
   hll_lb_finish<B>(P, lv);
 }
 
+// This workgroup's LDS ERROR table -> its private ERROR slab (kErrTab / B
+// entries per thread).  ATOMIC: no-return atomics, for the epilogues whose
+// other stores are already in flight; otherwise a plain read-modify-write.
+template <uint32_t B, bool ATOMIC, typename PT>
+__device__ __forceinline__ void errtab_to_slab(const PT &P, const uint32_t *etab, bool err_lds, uint32_t log2cap) {
+  if (!err_lds) return;
+  for (uint32_t t = threadIdx.x; t < kErrTab; t += B) {
+    const uint32_t e = etab[t];
+    if (e) {
+      uint32_t *cell = P.errslab + (uint64_t)blockIdx.x * ((uint64_t)P.n_windows << log2cap) + ((e >> 16) - 1);
+      if constexpr (ATOMIC) atomicAdd(cell, e & 0xFFFFu);
+      else *cell += e & 0xFFFFu;
+    }
+  }
+}
+
 template <int UPT, int SPT>
 struct EpiPre {
   uint4 g[UPT];
@@ -159,14 +229,7 @@ __device__ __forceinline__ void v2_epilogue(const PT &P, uint32_t cap, uint32_t 
     const ulonglong2 sv = slabs ? ls[tid + u * B] : make_ulonglong2(0, 0);
     if (sv.x | sv.y) ss[tid + u * B] = make_ulonglong2(x.sg[u].x + sv.x, x.sg[u].y + sv.y);
   }
-  constexpr uint32_t kE = kErrTab / B;  // ERROR table entries per thread
-#pragma unroll
-  for (uint32_t i = 0; i < kE; ++i) {
-    const uint32_t e = err_lds ? etab[tid + i * B] : 0u;
-    if (e)
-      atomicAdd(P.errslab + (uint64_t)blockIdx.x * ((uint64_t)P.n_windows << log2cap) + ((e >> 16) - 1),
-                e & 0xFFFFu);
-  }
+  errtab_to_slab<B, true>(P, etab, err_lds, log2cap);
   epi_raise_and_bound<B, Q>(P, hq, hqv, nq, x.lv);
 }
 
@@ -207,11 +270,10 @@ __global__ __launch_bounds__(kLdsBlock) void ingest_lds_kernel(IngestParams P) {
   const uint32_t cap = 1u << P.log2cap;
   const uint32_t nbk = P.nbk;
   const uint32_t nw = (nbk + 1) >> 1;
-  unsigned long long *lkeys = reinterpret_cast<unsigned long long *>(smem);
-  unsigned long long *lsum = lkeys + cap;
-  uint32_t *lcnt = reinterpret_cast<uint32_t *>(lsum + cap);
-  uint2 *hq = reinterpret_cast<uint2 *>(lcnt + cap * nw);
-  uint32_t *hq_n = reinterpret_cast<uint32_t *>(hq + kHllQueue);
+  const SmallLds L = small_lds_carve(smem, cap, nw, false);  // (the head: lkeys .. hq_n[0])
+  unsigned long long *const lkeys = L.lkeys, *const lsum = L.lsum;
+  uint32_t *const lcnt = L.lcnt, *const hq_n = L.hq_n;
+  uint2 *const hq = L.hq;
 
   uint64_t lo, hi;
   wg_range(P.n, lo, hi);
@@ -515,13 +577,182 @@ __device__ __forceinline__ uint32_t wave_claim(uint32_t *ctr) {
   return (uint32_t)__builtin_amdgcn_readfirstlane((int)atomicAdd(ctr, 1u)) >> 6;
 }
 
-// the scale read of the index records (the laboratory's SPANAGG_XIDX_OFF=3
-// ablation skips it; the product build always reads it)
+constexpr int kSpansPerLane = 2;   // one 16-B load per u64 column per lane and tile
+constexpr int kTilesInFlight = 2;  // a wave's register ring of tiles (= the tiles of one claim)
+
+// ---------------------------------------------------------------------------
+// The phases of ingest_v2_kernel's step, per span unless said otherwise.
+
+// Step 4: the key's two candidate 4-slot buckets in the LDS mirror (4 x 16-B
+// reads, fixed cost, no probe loop): its slot, or kNotFound.
+__device__ __forceinline__ uint32_t two_bucket_lookup(const unsigned long long *lkeys, unsigned long long k,
+                                                      uint32_t log2cap) {
+  const ProbeSeq pr = probe_seq(k, log2cap);
+  const ulonglong2 *b1 = reinterpret_cast<const ulonglong2 *>(lkeys + pr.b1 * 4);
+  const ulonglong2 *b2 = reinterpret_cast<const ulonglong2 *>(lkeys + pr.b2 * 4);
+  const ulonglong2 q1a = b1[0], q1b = b1[1], q2a = b2[0], q2b = b2[1];
+  uint32_t f = kNotFound;
+  f = q2b.y == k ? pr.b2 * 4 + 3 : f;
+  f = q2b.x == k ? pr.b2 * 4 + 2 : f;
+  f = q2a.y == k ? pr.b2 * 4 + 1 : f;
+  f = q2a.x == k ? pr.b2 * 4 + 0 : f;
+  f = q1b.y == k ? pr.b1 * 4 + 3 : f;
+  f = q1b.x == k ? pr.b1 * 4 + 2 : f;
+  f = q1a.y == k ? pr.b1 * 4 + 1 : f;
+  f = q1a.x == k ? pr.b1 * 4 + 0 : f;
+  return f;
+}
+
+// Step 6, an ERROR span: the exact per-(window, slot) counter -- the
+// workgroup's LDS table, else one no-return global atomic; a span without a
+// slot updates the count-min cells directly.
+__device__ __forceinline__ void error_add(uint32_t *etab, bool err_lds, uint32_t ws, uint32_t found, uint64_t key,
+                                          uint32_t log2cap) {
+  if (found == kNotFound) {
+    cold_cms_add(ws, key);
+  } else {
+    const uint32_t ek = (ws << log2cap) | found;
+    if (!(err_lds && lds_err_add(etab, ek)))
+      atomicAdd(cold_params().errcnt + ((uint64_t)ws << log2cap) + found, 1ULL);
+  }
+}
+
+// Step 7, the RED update of a span; the hot series' ns sum goes to the lane's
+// register (hot_sum), the others' to LDS.  (The LEAN form is in the kernel.)
+// Plain: LDS u16 bucket counter + u64 ns sum.
+template <bool DIAG>
+__device__ __forceinline__ void red_update_plain(const SmallLds &L, uint32_t nw, uint32_t cap, uint32_t diag,
+                                                 uint32_t found, uint32_t b, uint64_t dur, uint32_t hot_slot,
+                                                 unsigned long long &hot_sum) {
+  if (found != kNotFound) {
+    // diag 4096: spread the atomics over slots by lane (prices same-address
+    // serialisation of hot keys; counts are wrong)
+    const uint32_t fs = (DIAG && (diag & 4096u)) ? (found + (threadIdx.x & 63u) * 29u) & (cap - 1u) : found;
+    atomicAdd(&L.lcnt[fs * nw + (b >> 1)], 1u << ((b & 1) * 16));
+    if (found == hot_slot) hot_sum += dur;
+    else atomicAdd(&L.lsum[fs], (unsigned long long)dur);
+  }
+}
+// EXPO: per-slot LDS header partials -- count, zero count, ns sum, max of ~d
+// and max d over positive durations (XHdr) -- in the space of lsum + lcnt.
+struct XPartials {
+  unsigned long long *minx, *max;
+  uint32_t *cnt, *zero;
+};
+__device__ __forceinline__ XPartials expo_partials(const SmallLds &L, uint32_t cap) {
+  uint32_t *const cnt = reinterpret_cast<uint32_t *>(L.lsum + 3 * cap);
+  return {L.lsum + cap, L.lsum + 2 * cap, cnt, cnt + cap};
+}
+__device__ __forceinline__ void red_update_expo(const SmallLds &L, const XPartials &X, uint32_t f, unsigned long long d,
+                                                uint32_t hot_slot, unsigned long long &hot_sum) {
+  if (f != kNotFound) {
+    atomicAdd(&X.cnt[f], 1u);
+    if (f == hot_slot) hot_sum += d;
+    else atomicAdd(&L.lsum[f], d);
+    if (d == 0) {
+      atomicAdd(&X.zero[f], 1u);
+    } else {
+      atomicMax(&X.minx[f], ~d);
+      atomicMax(&X.max[f], d);
+    }
+  }
+}
+// The laboratory's SPANAGG_XIDX_OFF ablations of the EXPO index records
+// (P.xidx 2: wrong buckets without the index computation; 3: also without the
+// scale read); the product build has none.  A macro, so that the product's 0
+// is folded before code generation (a function of P, folded after inlining,
+// changed the EXPO instances' device code).  kLabBuild: whether the ablation
+// option set (O::DIAG) may be instantiated at all.
 #ifdef SPANAGG_AB
-#define SA_XIDX_SCALE(P) ((P).xidx != 3)
+#define SA_XIDX_ABLATION(P) ((P).xidx >= 2 ? (P).xidx : 0u)
+constexpr bool kLabBuild = true;
 #else
-#define SA_XIDX_SCALE(P) true
+#define SA_XIDX_ABLATION(P) 0u
+constexpr bool kLabBuild = false;
 #endif
+
+// The prologue's LDS setup, up to (not including) its barrier, from the
+// values its loads brought: the key table kv, the bin table bv, the HLL bounds
+// lbw.  (The loads themselves, and EXPO's scale bytes, stay in the kernel: as
+// functions they raised the generic EXPO instance's SGPR spills.)
+template <uint32_t BLK>
+__device__ __forceinline__ void lds_setup(const IngestParams &P, const SmallLds &L, uint32_t cap, uint32_t nw, bool lb_on,
+                                          const ulonglong2 (&kv)[4], uint4 bv, uint32_t lbw) {
+  const uint32_t per = (cap + 2 * BLK - 1) / (2 * BLK);
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const uint32_t i = 2 * (threadIdx.x + u * BLK);
+    if (u < (int)per && i < cap) {
+      reinterpret_cast<ulonglong2 *>(L.lkeys)[i / 2] = kv[u];
+      reinterpret_cast<ulonglong2 *>(L.lsum)[i / 2] = make_ulonglong2(0, 0);
+    }
+  }
+  if (threadIdx.x < kBins * 2) reinterpret_cast<uint4 *>(L.lbins)[threadIdx.x] = bv;
+  for (uint32_t i = threadIdx.x * 4; i < cap * nw; i += BLK * 4)
+    *reinterpret_cast<uint4 *>(L.lcnt + i) = make_uint4(0, 0, 0, 0);
+  if (threadIdx.x == 0) {
+    L.hq_n[0] = 0;
+    // the next unclaimed chunk of this workgroup's range, x 64 (see wave_claim)
+    L.hq_n[1] = (2u * (BLK / 64)) << 6;
+    L.hq_n[2] = 0;  // HLL updates the lower-bound filter skipped (summed over the waves)
+  }
+  if (threadIdx.x < 4) L.lstat[threadIdx.x] = 0;
+  for (uint32_t i = threadIdx.x; i < kErrTab; i += BLK) L.etab[i] = 0;
+  // (filter off: the first bound word stays 0, and every span's sub-block
+  // index is 0 or 1 below, so no rho can be at or below it)
+  if (threadIdx.x * 4 < (lb_on ? P.lb_n : 4u)) reinterpret_cast<uint32_t *>(L.llb)[threadIdx.x] = lbw;
+}
+
+// The event counts at the kernel's end (after the epilogue's barrier, so the
+// LDS counts are final).  LEAN's LDS counters: one global add per count.
+__device__ __forceinline__ void flush_lds_stats(const uint32_t *lstat) {
+  if (threadIdx.x < 4 && lstat[threadIdx.x]) {
+    constexpr uint32_t kIdx[4] = {kStatZeroKey, kStatInvalidService, kStatWindowOOR, kStatDropped};
+    atomicAdd(&cold_params().stats[kIdx[threadIdx.x]], (unsigned long long)lstat[threadIdx.x]);
+  }
+}
+// The filtered HLL updates (hq_n[2]), to a slot per workgroup: thousands of
+// same-address atomics at the end of every launch would serialise its tail.
+__device__ __forceinline__ void flush_filtered(const uint32_t *hq_n) {
+  if (threadIdx.x == 0 && hq_n[2])
+    atomicAdd(&cold_params().hll_filt[blockIdx.x & (kFiltSlots - 1)], (unsigned long long)hq_n[2]);
+}
+// The plain form's wave-uniform counts: one add per wave and count.
+__device__ __forceinline__ void flush_wave_stats(uint32_t n_zero, uint32_t n_badsvc, uint32_t n_oor, uint32_t n_drop) {
+  if ((threadIdx.x & 63) == 0) {
+    unsigned long long *const stats = cold_params().stats;
+    if (n_zero) atomicAdd(&stats[kStatZeroKey], (unsigned long long)n_zero);
+    if (n_badsvc) atomicAdd(&stats[kStatInvalidService], (unsigned long long)n_badsvc);
+    if (n_oor) atomicAdd(&stats[kStatWindowOOR], (unsigned long long)n_oor);
+    if (n_drop) atomicAdd(&stats[kStatDropped], (unsigned long long)n_drop);
+  }
+}
+
+// The kernel's epilogue (after the loop's workgroup barrier) in its three
+// forms: EXPO, the compile-time geometries' prefetched one (v2_epi_pre +
+// v2_epilogue above) and the generic one.
+// EXPO: this workgroup's header partials -> its slab, every slot (untouched
+// ones as zeros: the reduce pass reads the slab and leaves it as it is, no
+// zeroing stores behind its reads); the ERROR counts; the HLL raises and bound.
+template <uint32_t B, uint32_t Q>
+__device__ __forceinline__ void epilogue_expo(const IngestParams &P, const SmallLds &L, const XPartials &X, uint32_t cap,
+                                              uint32_t log2cap, bool err_lds, const uint32_t *hqv, uint32_t nq,
+                                              const uint4 (&lv)[4]) {
+  XHdr *xs = P.xslab + (uint64_t)blockIdx.x * cap;
+  for (uint32_t sl = threadIdx.x; sl < cap; sl += B) xs[sl] = XHdr{X.cnt[sl], X.zero[sl], L.lsum[sl], X.minx[sl], X.max[sl]};
+  errtab_to_slab<B, true>(P, L.etab, err_lds, log2cap);
+  epi_raise_and_bound<B, Q>(cold_params(), L.hq, hqv, nq, lv);
+}
+// Generic: the slab flush of ingest_lds_kernel, the ERROR counts, the queued
+// HLL raises and a refresh of the bounds, all read after the barrier.
+template <uint32_t B>
+__device__ __forceinline__ void epilogue_generic(const IngestParams &P, const SmallLds &L, uint32_t cap, uint32_t nw,
+                                                 uint32_t log2cap, bool err_lds, uint32_t nq) {
+  flush_lds(P, cap, nw, L.lsum, L.lcnt);
+  errtab_to_slab<B, false>(P, L.etab, err_lds, log2cap);
+  for (uint32_t i = threadIdx.x; i < nq; i += B) hll_raise(P.hll + L.hq[i].x, L.hq[i].y);
+  hll_lb_refresh(P, threadIdx.x >> 6, B / 64);
+}
 
 //
 // The kernel's template: its geometry (LC = log2 slots, NWC = counter words
@@ -537,46 +768,36 @@ struct V2Plain {
 struct V2Lean : V2Plain {
   static constexpr bool LEAN = true;
 };
-constexpr int kSpansPerLane = 2;   // one 16-B load per u64 column per lane and tile
-constexpr int kTilesInFlight = 2;  // a wave's register ring of tiles (= the tiles of one claim)
 template <int LC, int NWC, int PC, bool EXPO, uint32_t BLK, typename O>
 __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
   constexpr int S = kSpansPerLane, NBUF = kTilesInFlight, AUX = 2;  // (AUX 2: nt tile loads)
   constexpr bool LEAN = O::LEAN, DIAG = O::DIAG;
-#ifndef SPANAGG_AB
-  static_assert(!DIAG, "laboratory switch: libspanagg_ab.so only");
-#endif
+  static_assert(kLabBuild || !DIAG, "laboratory switch: libspanagg_ab.so only");
   static_assert(BLK % 64 == 0 && kErrTab % BLK == 0 && kHllQueue % BLK == 0 && BLK * 4 >= kLbMaxSub, "block size");
   static_assert(S == 2, "EXPO stores a lane's two spans as one vector");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   if (P.dbg && threadIdx.x == 0) P.dbg[blockIdx.x * kDbgPerWg + 0] = __builtin_amdgcn_s_memrealtime();
   const uint32_t log2cap = LC ? (uint32_t)LC : P.log2cap;
   const uint32_t cap = 1u << log2cap;
-  const uint32_t nw = EXPO ? 6u : NWC ? (uint32_t)NWC : (P.nbk + 1) >> 1;
+  const uint32_t nw = EXPO ? (uint32_t)kExpoWords : NWC ? (uint32_t)NWC : (P.nbk + 1) >> 1;
   const uint32_t hp = PC ? (uint32_t)PC : P.p;
   const uint32_t diag = DIAG ? P.diag : 0u;
-  unsigned long long *lkeys = reinterpret_cast<unsigned long long *>(smem);
-  unsigned long long *lsum = lkeys + cap;
-  uint32_t *lcnt = reinterpret_cast<uint32_t *>(lsum + cap);
-  uint2 *hq = reinterpret_cast<uint2 *>(lcnt + cap * nw);
-  uint32_t *hq_n = reinterpret_cast<uint32_t *>(hq + kHllQueue);
+  const SmallLds L = small_lds_carve(smem, cap, nw, EXPO);
+  unsigned long long *const lkeys = L.lkeys, *const lsum = L.lsum;
+  uint32_t *const lcnt = L.lcnt, *const hq_n = L.hq_n, *const lstat = L.lstat, *const etab = L.etab;
+  uint2 *const hq = L.hq;
+  BinEntry *const lbins = L.lbins;
+  uint8_t *const llb = L.llb;
+  int8_t *const lsc = L.lsc;
   // the compile-time-geometry epilogue (v2_epilogue) raises from the word each
   // span saw: the queue region holds kQcap (hoff, rho) pairs, then their words
   constexpr bool kObs = (LC != 0 && NWC != 0 && LEAN) || EXPO;
   constexpr uint32_t kQcap = kObs ? kHllQueue / 2 : kHllQueue;
   static_assert(!kObs || kQcap * 12 <= kHllQueue * 8, "queue region");
   uint32_t *hqv = reinterpret_cast<uint32_t *>(hq + kQcap);
-  uint32_t *lstat = hq_n + 4;  // LEAN: [4] event counts (zero key, bad service, out of ring, dropped)
-  BinEntry *lbins = reinterpret_cast<BinEntry *>(hq_n + 8);
-  uint32_t *etab = reinterpret_cast<uint32_t *>(lbins + kBins);  // [kErrTab]: (key+1) << 16 | count
-  uint8_t *llb = reinterpret_cast<uint8_t *>(etab + kErrTab);       // [kLbMaxSub] HLL lower bounds
-  // EXPO with index records: [cap] each slot's scale when the kernel started
-  int8_t *lsc = reinterpret_cast<int8_t *>(llb + kLbMaxSub);
   const bool err_lds = P.errslab != nullptr;
   const bool lb_on = P.lb_n != 0 && !(diag & 2u);
-  // EXPO header partials (zeroed with lsum / lcnt): lsum = ns sums
-  unsigned long long *xminx = lsum + cap, *xmax = lsum + 2 * cap;
-  uint32_t *xcnt = reinterpret_cast<uint32_t *>(lsum + 3 * cap), *xzero = xcnt + cap;
+  const XPartials X = expo_partials(L, cap);  // EXPO header partials (zeroed with lsum / lcnt)
 
   uint64_t lo, hi;
   wg_range_p(P, lo, hi);
@@ -593,24 +814,16 @@ __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   // the first two chunks of every wave are fixed; claims continue after them
   uint32_t c0 = wave, c1 = wave + kWaves;
-  // Unused, and kept on purpose: the retired tile-claim loop initialised such
-  // an array here, and without it the compiler orders ~20 scalar prologue
-  // instructions of the three generic instances differently (same
-  // instructions and registers).  It stayed so that the change which removed
-  // that loop left this kernel's device code identical (tools/isa_diff.py);
-  // drop it with the next change that alters the kernel's code anyway.
-  uint32_t cur[NBUF];
-#pragma unroll
-  for (int b = 0; b < NBUF; ++b) cur[b] = (uint32_t)b * kWaves + wave;
-  (void)cur;
   auto tstart = [&](uint32_t c, int b) -> uint32_t {  // step b's first span in chunk c, relative to lo
     return c * chunk + (uint32_t)b * tile;
   };
   auto tremain = [&](uint32_t t) -> uint32_t { return len > t ? len - t : 0u; };
 
   // Prologue: key-table loads (16 B per lane, <= 4 per lane for cap <= 8192)
-  // and the bin table first, then the first NBUF tiles; the LDS setup then
-  // waits only for the key-table loads (vmcnt counts in issue order).
+  // and the bin table first, then the first NBUF tiles; the LDS setup
+  // (lds_setup) then waits only for the key-table loads (vmcnt counts in
+  // issue order).  (The loads are inline: as a function returning their values
+  // they raised the generic EXPO instance's SGPR spills, 80 -> 82 or 84.)
   ulonglong2 kv[4];
   const uint32_t per = (cap + 2 * BLK - 1) / (2 * BLK);
 #pragma unroll
@@ -626,7 +839,7 @@ __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
   // them and not for the first tiles
   uint32_t xsc = 0;
   if constexpr (EXPO)
-    if (P.xidx && SA_XIDX_SCALE(P) && 2 * threadIdx.x < cap) xsc = *reinterpret_cast<const uint16_t *>(P.xscale + 2 * threadIdx.x);
+    if (P.xidx && SA_XIDX_ABLATION(P) != 3 && 2 * threadIdx.x < cap) xsc = *reinterpret_cast<const uint16_t *>(P.xscale + 2 * threadIdx.x);
   uint32_t lbw = 0;
   if (lb_on && threadIdx.x * 4 < P.lb_n) lbw = *reinterpret_cast<const uint32_t *>(P.hll_lb + threadIdx.x * 4);
   if constexpr (LEAN) {
@@ -651,30 +864,9 @@ __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
       for (int j = 0; j < S; ++j) pend.hv[j] = *reinterpret_cast<const uint32_t *>(P.hll + z);
     }
   }
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const uint32_t i = 2 * (threadIdx.x + u * BLK);
-    if (u < (int)per && i < cap) {
-      reinterpret_cast<ulonglong2 *>(lkeys)[i / 2] = kv[u];
-      reinterpret_cast<ulonglong2 *>(lsum)[i / 2] = make_ulonglong2(0, 0);
-    }
-  }
-  if (threadIdx.x < kBins * 2) reinterpret_cast<uint4 *>(lbins)[threadIdx.x] = bv;
-  for (uint32_t i = threadIdx.x * 4; i < cap * nw; i += BLK * 4)
-    *reinterpret_cast<uint4 *>(lcnt + i) = make_uint4(0, 0, 0, 0);
-  if (threadIdx.x == 0) {
-    hq_n[0] = 0;
-    // the next unclaimed chunk of this workgroup's range, x 64 (see wave_claim)
-    hq_n[1] = (2u * kWaves) << 6;
-    hq_n[2] = 0;  // HLL updates the lower-bound filter skipped (summed over the waves)
-  }
-  if (threadIdx.x < 4) lstat[threadIdx.x] = 0;
+  lds_setup<BLK>(P, L, cap, nw, lb_on, kv, bv, lbw);
   if constexpr (EXPO)
-    if (P.xidx && SA_XIDX_SCALE(P) && 2 * threadIdx.x < cap) *reinterpret_cast<uint16_t *>(lsc + 2 * threadIdx.x) = (uint16_t)xsc;
-  for (uint32_t i = threadIdx.x; i < kErrTab; i += BLK) etab[i] = 0;
-  // (filter off: the first bound word stays 0, and every span's sub-block
-  // index is 0 or 1 below, so no rho can be at or below it)
-  if (threadIdx.x * 4 < (lb_on ? P.lb_n : 4u)) reinterpret_cast<uint32_t *>(llb)[threadIdx.x] = lbw;
+    if (P.xidx && SA_XIDX_ABLATION(P) != 3 && 2 * threadIdx.x < cap) *reinterpret_cast<uint16_t *>(lsc + 2 * threadIdx.x) = (uint16_t)xsc;
   __syncthreads();
   if (P.dbg && threadIdx.x == 0) P.dbg[blockIdx.x * kDbgPerWg + 1] = __builtin_amdgcn_s_memrealtime();
 
@@ -768,6 +960,9 @@ __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
       rho[j] = 0;
       hoff[j] = 0;
       if (!(diag & 2u)) {
+        // rho, register index and row in the LEAN and the plain form (inline:
+        // as two functions returning the three values they cost every instance
+        // but the default one a VGPR and three of them SGPR spills)
         uint32_t r, idx, row;
         if constexpr (LEAN) {
           const H64 x = xxh64_16_h(T.a[j], T.b[j]);
@@ -818,20 +1013,8 @@ __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
       bool need[S];
 #pragma unroll
       for (int j = 0; j < S; ++j) {
-        const ProbeSeq pr = probe_seq(key[j], log2cap);
-        const ulonglong2 *b1 = reinterpret_cast<const ulonglong2 *>(lkeys + pr.b1 * 4);
-        const ulonglong2 *b2 = reinterpret_cast<const ulonglong2 *>(lkeys + pr.b2 * 4);
-        const ulonglong2 q1a = b1[0], q1b = b1[1], q2a = b2[0], q2b = b2[1];
         const unsigned long long k = key[j];
-        uint32_t f = kNotFound;
-        f = q2b.y == k ? pr.b2 * 4 + 3 : f;
-        f = q2b.x == k ? pr.b2 * 4 + 2 : f;
-        f = q2a.y == k ? pr.b2 * 4 + 1 : f;
-        f = q2a.x == k ? pr.b2 * 4 + 0 : f;
-        f = q1b.y == k ? pr.b1 * 4 + 3 : f;
-        f = q1b.x == k ? pr.b1 * 4 + 2 : f;
-        f = q1a.y == k ? pr.b1 * 4 + 1 : f;
-        f = q1a.x == k ? pr.b1 * 4 + 0 : f;
+        const uint32_t f = two_bucket_lookup(lkeys, k, log2cap);
         found[j] = k != 0 ? f : kNotFound;
         need[j] = k != 0 && f == kNotFound;
       }
@@ -860,6 +1043,7 @@ __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
     // most common slot among four candidate lanes (ballot); its ns sum then
     // accumulates in a lane register instead of the LDS atomic that every lane
     // of that series would otherwise serialise on (summed once at the end)
+    // (inline: as a function it inverted two branches of the timed instances)
     if (hot_slot == kHotUnset) {
       uint32_t best = kNotFound, nbest = 0;
 #pragma unroll
@@ -873,62 +1057,34 @@ __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
       }
       hot_slot = best;
     }
-    // 6. ERROR spans: exact per-(window, slot) counter (one no-return atomic);
-    //    spans without a slot update the count-min cells directly
+    // 6. ERROR spans
 #pragma unroll
-    for (int j = 0; j < S; ++j) {
-      if (err[j]) {
-        if (found[j] == kNotFound) {
-          cold_cms_add(ws[j], key[j]);
-        } else {
-          const uint32_t ek = (ws[j] << log2cap) | found[j];
-          if (!(err_lds && lds_err_add(etab, ek)))
-            atomicAdd(cold_params().errcnt + ((uint64_t)ws[j] << log2cap) + found[j], 1ULL);
-        }
-      }
-    }
-    // 7. RED update: LDS u16 bucket counter + u64 ns sum.  LEAN: wave-level
-    //    key dedup of the counter adds -- the lanes that hold the same
-    //    (slot, bucket) as the wave's first lane of its hot series (a ballot
-    //    on the readlane'd key) make one LDS add of their count, from the
-    //    first of them; the other lanes add their own span.
+    for (int j = 0; j < S; ++j)
+      if (err[j]) error_add(etab, err_lds, ws[j], found[j], key[j], log2cap);
+    // 7. RED update, in one of its three forms
     if constexpr (EXPO) {
+      // + the span's slot, or its index record (the bucket index at the
+      // slot's starting scale), or the span record, for the counting pass.
+      // (Inline: as functions the index record and the two stores changed the
+      // EXPO instances' registers and spills.)
       uint32_t xw[S] = {};
 #pragma unroll
       for (int j = 0; j < S; ++j) {
+        red_update_expo(L, X, found[j], dur[j], hot_slot, hot_sum);
         const uint32_t f = found[j];
-        if (f != kNotFound) {
-          const unsigned long long d = dur[j];
-          atomicAdd(&xcnt[f], 1u);
-          if (f == hot_slot) hot_sum += d;
-          else atomicAdd(&lsum[f], d);
-          if (d == 0) {
-            atomicAdd(&xzero[f], 1u);
-          } else {
-            atomicMax(&xminx[f], ~d);
-            atomicMax(&xmax[f], d);
-          }
-        }
         if (!P.span_rec) {
           uint32_t w = f;
-          if (P.xidx) {  // the index record: the bucket index at the slot's starting scale
+          if (P.xidx) {
             // (branch-free but for the rare long-duration store: every lane
             // computes the index, the record is picked by selects)
             const unsigned long long d = dur[j];
             const bool nf = f == kNotFound;
             const uint32_t fs = nf ? 0u : f;
-#ifdef SPANAGG_AB
-            const int32_t sc = P.xidx == 3 ? 0 : lsc[fs];
-#else
-            const int32_t sc = lsc[fs];
-#endif
+            const int32_t sc = SA_XIDX_ABLATION(P) == 3 ? 0 : lsc[fs];
             int32_t ix = 0;
             bool ok;
-#ifdef SPANAGG_AB
-            if (P.xidx >= 2) ok = true, ix = (int32_t)(d & 7u);  // ablation (SPANAGG_XIDX_OFF): wrong buckets
-            else
-#endif
-            ok = expo_index_fast(d ? d : 1u, P.l2d_q24, sc, ix) && ix >= kIxMin && ix <= kIxMax;
+            if (SA_XIDX_ABLATION(P) >= 2) ok = true, ix = (int32_t)(d & 7u);  // (wrong buckets)
+            else ok = expo_index_fast(d ? d : 1u, P.l2d_q24, sc, ix) && ix >= kIxMin && ix <= kIxMax;
             w = nf ? kSpanRecNoSlot << kIxSlotShift
                    : d == 0 ? (f << kIxSlotShift | kIxZero)
                             : ok ? ixrec_of(f, sc, ix) : (f << kIxSlotShift | kIxLong);
@@ -962,6 +1118,12 @@ __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
           if (dur[j] >= kSpanRecDurMask && i0 + (uint32_t)j < len) P.span_long[lo + i0 + j] = dur[j];
       }
     } else if constexpr (LEAN) {
+      // LDS u16 bucket counter + u64 ns sum with wave-level key dedup of the
+      // counter adds -- the lanes that hold the same (slot, bucket) as the
+      // wave's first lane of its hot series (a ballot on the readlane'd key)
+      // make one LDS add of their count, from the first of them; the other
+      // lanes add their own span.  (Inline: every function form tried changed
+      // ~870 lines of the default instance's loop.)
       const uint32_t lane = threadIdx.x & 63u;
 #pragma unroll
       for (int j = 0; j < S; ++j) {
@@ -981,19 +1143,10 @@ __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
         if (found[j] == hot_slot) hot_sum += dur[j];
         else if (found[j] != kNotFound) atomicAdd(&lsum[found[j]], (unsigned long long)dur[j]);
       }
-    }
+    } else {
 #pragma unroll
-    for (int j = 0; j < S && !LEAN && !EXPO; ++j) {
-      if (found[j] != kNotFound) {
-        const uint32_t b = bkt[j];
-        // diag 4096: spread the atomics over slots by lane (prices same-address
-        // serialisation of hot keys; counts are wrong)
-        const uint32_t fs = (DIAG && (diag & 4096u)) ? (found[j] + (threadIdx.x & 63u) * 29u) & (cap - 1u)
-                                                     : found[j];
-        atomicAdd(&lcnt[fs * nw + (b >> 1)], 1u << ((b & 1) * 16));
-        if (found[j] == hot_slot) hot_sum += dur[j];
-        else atomicAdd(&lsum[fs], (unsigned long long)dur[j]);
-      }
+      for (int j = 0; j < S; ++j)
+        red_update_plain<DIAG>(L, nw, cap, diag, found[j], bkt[j], dur[j], hot_slot, hot_sum);
     }
     stamp(3);
     // 8. settle the previous step's HLL reads, keep this step's for the next
@@ -1051,687 +1204,21 @@ __global__ __launch_bounds__(BLK) void ingest_v2_kernel(IngestParams P) {
   __syncthreads();
   const uint32_t nq = *hq_n < kQcap ? *hq_n : kQcap;
   if constexpr (EXPO) {
-    // this workgroup's header partials -> its slab, every slot (untouched ones
-    // as zeros: the reduce pass reads the slab and leaves it as it is, no
-    // zeroing stores behind its reads)
-    XHdr *xs = P.xslab + (uint64_t)blockIdx.x * cap;
-    for (uint32_t sl = threadIdx.x; sl < cap; sl += BLK) xs[sl] = XHdr{xcnt[sl], xzero[sl], lsum[sl], xminx[sl], xmax[sl]};
-    if (err_lds) {  // this workgroup's ERROR counts -> its private slab (no-return atomics)
-      for (uint32_t t = threadIdx.x; t < kErrTab; t += BLK) {
-        const uint32_t e = etab[t];
-        if (e) atomicAdd(P.errslab + (uint64_t)blockIdx.x * ((uint64_t)P.n_windows << log2cap) + ((e >> 16) - 1),
-                         e & 0xFFFFu);
-      }
-    }
-    epi_raise_and_bound<BLK, kQcap>(cold_params(), hq, hqv, nq, epre.lv);
+    epilogue_expo<BLK, kQcap>(P, L, X, cap, log2cap, err_lds, hqv, nq, epre.lv);
   } else if constexpr (kSlabPre) {
-    // compile-time geometry: the two-phase epilogue (words prefetched above)
     v2_epilogue<kUpt, kSpt, BLK, kQcap>(cold_params(), cap, nw, log2cap, lsum, lcnt, etab, err_lds, hq, hqv, nq,
                                         epre);
   } else {
-    flush_lds(P, cap, nw, lsum, lcnt);
-    if (err_lds) {  // this workgroup's ERROR counts -> its private slab (plain RMW)
-      for (uint32_t t = threadIdx.x; t < kErrTab; t += BLK) {
-        const uint32_t e = etab[t];
-        if (e) {
-          uint32_t *cell = P.errslab + (uint64_t)blockIdx.x * ((uint64_t)P.n_windows << log2cap) + ((e >> 16) - 1);
-          *cell += e & 0xFFFFu;
-        }
-      }
-    }
-    for (uint32_t i = threadIdx.x; i < nq; i += BLK) hll_raise(P.hll + hq[i].x, hq[i].y);
-    hll_lb_refresh(P, threadIdx.x >> 6, kWaves);
+    epilogue_generic<BLK>(P, L, cap, nw, log2cap, err_lds, nq);
   }
   if (dbg && threadIdx.x == 0) dbg[blockIdx.x * kDbgPerWg + 3] = __builtin_amdgcn_s_memrealtime();
   if (dbg && (threadIdx.x & 63) == 0) {
     for (int i = 0; i < 6 && DIAG; ++i) dbg[blockIdx.x * kDbgPerWg + 8 + (threadIdx.x >> 6) * 8 + i] = seg[i];
     dbg[blockIdx.x * kDbgPerWg + 8 + (threadIdx.x >> 6) * 8 + 6] = wave_loop_end;
   }
-  if constexpr (LEAN) {  // (lstat is final: the epilogue follows a workgroup barrier)
-    if (threadIdx.x < 4 && lstat[threadIdx.x]) {
-      constexpr uint32_t kIdx[4] = {kStatZeroKey, kStatInvalidService, kStatWindowOOR, kStatDropped};
-      atomicAdd(&cold_params().stats[kIdx[threadIdx.x]], (unsigned long long)lstat[threadIdx.x]);
-    }
-  }
-  // (hq_n[2] is final: the epilogue follows a workgroup barrier.  A slot per
-  // workgroup: thousands of same-address atomics at the end of every launch
-  // would serialise its tail)
-  if (threadIdx.x == 0 && hq_n[2])
-    atomicAdd(&cold_params().hll_filt[blockIdx.x & (kFiltSlots - 1)], (unsigned long long)hq_n[2]);
-  if ((threadIdx.x & 63) == 0) {
-    unsigned long long *const stats = cold_params().stats;
-    if (n_zero) atomicAdd(&stats[kStatZeroKey], (unsigned long long)n_zero);
-    if (n_badsvc) atomicAdd(&stats[kStatInvalidService], (unsigned long long)n_badsvc);
-    if (n_oor) atomicAdd(&stats[kStatWindowOOR], (unsigned long long)n_oor);
-    if (n_drop) atomicAdd(&stats[kStatDropped], (unsigned long long)n_drop);
-  }
-}
-
-// ---------------------------------------------------------------------------
-// HBM-table path (table larger than LDS): CAS insert + u64 atomics per span;
-// 256 threads, 4 spans per lane per tile, no prefetch.  NB >= 0: unrolled for
-// NB non-negative bounds; -1: any bounds.
-template <int NB>
-__global__ __launch_bounds__(kHbmBlock) void ingest_hbm_kernel(IngestParams P) {
-  constexpr int S = kHbmSpansPerLane;
-  LaneStats st{0, 0, 0, 0};
-  const uint32_t nbk = NB >= 0 ? (uint32_t)NB + 1 : P.nbk;
-  const uint32_t stride = row_stride(nbk);
-  uint64_t lo, hi;
-  wg_range(P.n, lo, hi);
-  const Cols c = make_cols(P, lo, hi);
-  const uint32_t len = (uint32_t)(hi - lo);
-  const uint32_t tile = kHbmBlock * S;
-  uint32_t off = threadIdx.x * S;
-  SpanTile<S> cur;
-  load_tile<S>(c, off, len, cur);
-  for (uint32_t t0 = 0; t0 < len; t0 += tile, off += tile) {
-    SketchPre<S> k;
-    sketch_pre<S>(P, cur, k, st);
-    uint32_t slot[S], bk[S];
-    uint64_t dd[S];
-#pragma unroll
-    for (int j = 0; j < S; ++j) {
-      slot[j] = kNotFound;
-      bk[j] = 0;
-      dd[j] = 0;
-      if (j < cur.cnt) {
-        const uint64_t key = cur.key[j];
-        const uint64_t d = cur.e[j] > cur.s[j] ? cur.e[j] - cur.s[j] : 0;
-        st.zero_key += key == 0 ? 1u : 0u;
-        if (key != 0 && !(P.diag & 1u)) {
-          bk[j] = bucket_of<NB>(d, P);
-          dd[j] = d;
-          const uint32_t found = g_find_insert(P.gkeys, key, P.log2cap, P.max_probe);
-          st.dropped += found == kNotFound ? 1u : 0u;
-          slot[j] = found;
-        }
-      }
-    }
-    // Counter atomics in lane pairs: lanes 2i and 2i+1 each add the count of
-    // one span and the sum of the other's, so one instruction carries both
-    // cells of a span -- one 64-B segment, one memory-side atomic request
-    // (the requests, not the bytes, bound this path: tools/atomic_probe.hip).
-    if (!(P.diag & 2048u)) {  // diag 2048: lookups only
-      const bool even = (threadIdx.x & 1u) == 0;
-#pragma unroll
-      for (int j = 0; j < S; ++j) {
-        const uint32_t os = (uint32_t)__shfl_xor((int)slot[j], 1);
-        const uint32_t ob = (uint32_t)__shfl_xor((int)bk[j], 1);
-        const uint64_t od = (uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)dd[j], 1) |
-                            ((uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(dd[j] >> 32), 1) << 32);
-        // instruction 1: even lane -> its count, odd lane -> the even lane's sum
-        const uint32_t s1 = even ? slot[j] : os, b1 = even ? bk[j] : ob;
-        if (s1 != kNotFound)
-          atomicAdd(P.gcounts + (uint64_t)s1 * stride + (even ? row_count_cell(b1) : row_sum_cell(b1)),
-                    even ? 1ULL : (unsigned long long)od);
-        // instruction 2: odd lane -> its count, even lane -> the odd lane's sum
-        const uint32_t s2 = even ? os : slot[j], b2 = even ? ob : bk[j];
-        if (s2 != kNotFound)
-          atomicAdd(P.gcounts + (uint64_t)s2 * stride + (even ? row_sum_cell(b2) : row_count_cell(b2)),
-                    even ? (unsigned long long)od : 1ULL);
-      }
-    }
-    sketch_post<S>(P, cur, k, slot);
-    load_tile<S>(c, off + tile, len, cur);
-  }
-  flush_stats(P, st);
-}
-
-// ---------------------------------------------------------------------------
-// Partitioned HBM-table path.  Random per-span lookups and counter atomics
-// into a table far larger than LDS bound ingest_hbm_kernel (10 M spans over
-// 1 M keys: 552 us).  Here every span is first written as a 16-B record into
-// the bin of its key (top 11 bits), then one workgroup per bin aggregates its
-// records in an LDS table (~490 keys per bin at 1 M keys) and adds each key's
-// row to the HBM counters once, with plain read-modify-write: a key belongs
-// to one bin, so its row has one writer per launch.  Records that do not fit
-// (a bin beyond its capacity, durations >= 2^57 ns, an LDS table past its
-// probe limit) take the direct path: lookup + counter atomics, as in
-// ingest_hbm_kernel.  Stats, HLL and ERROR spans are handled in the scatter.
-
-typedef unsigned long long nt_u64x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void direct_red(const IngestParams &P, uint64_t key, uint64_t d,
-                                           uint32_t bk, uint32_t stride, LaneStats &st) {
-  const uint32_t s = g_find_insert(P.gkeys, key, P.log2cap, P.max_probe);
-  if (s == kNotFound) {
-    st.dropped += 1u;
-    return;
-  }
-  atomicAdd(P.gcounts + (uint64_t)s * stride + row_count_cell(bk), 1ULL);
-  atomicAdd(P.gcounts + (uint64_t)s * stride + row_sum_cell(bk), (unsigned long long)d);
-}
-
-#ifndef PART_U
-#define PART_U 4
-#endif
-// Records go through a kPartStage-record LDS stage per bin and leave as whole
-// chunks (runs are reserved in multiples of kPartStage records, so chunks
-// stay aligned).
-#ifndef SA_PART_SKIP_USED
-#define SA_PART_SKIP_USED 1
-#endif
-#ifndef SA_PART_WAVES_EU
-#define SA_PART_WAVES_EU 1  // 8 caps VGPRs at 64: two 1,024-thread workgroups per CU
-#endif
-template <int NB>
-__global__ __launch_bounds__(kPartBlock, SA_PART_WAVES_EU) void part_scatter_kernel(IngestParams P) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  uint32_t *cur = reinterpret_cast<uint32_t *>(smem);  // phase 1: counts; then next record index
-  uint32_t *lim = cur + kPartBins;                      // end of this workgroup's run in the bin
-  uint32_t *scnt = lim + kPartBins;                     // records staged per bin
-  ulonglong2 *stage = reinterpret_cast<ulonglong2 *>(scnt + kPartBins);  // [kPartBins][kPartStage]
-  unsigned long long *hkey = reinterpret_cast<unsigned long long *>(stage + kPartBins * kPartStage);
-  unsigned long long *hsum = hkey + kPartHot;                           // overflow table
-  uint32_t *hcnt = reinterpret_cast<uint32_t *>(hsum + kPartHot);       // [kPartHot][kPartMaxBk]
-  LaneStats st{0, 0, 0, 0};
-  const uint32_t nbk = NB >= 0 ? (uint32_t)NB + 1 : P.nbk;
-  const uint32_t stride = row_stride(nbk);
-  uint64_t lo, hi;
-  wg_range(P.n, lo, hi);
-  for (uint32_t b = threadIdx.x; b < kPartBins; b += blockDim.x) cur[b] = scnt[b] = 0;
-  for (uint32_t h = threadIdx.x; h < kPartHot; h += blockDim.x) hkey[h] = hsum[h] = 0;
-  for (uint32_t h = threadIdx.x; h < kPartHot * kPartMaxBk; h += blockDim.x) hcnt[h] = 0;
-  __syncthreads();
-  // 1. records per bin in this workgroup's range (key column only; 8 loads
-  //    in flight per thread)
-  constexpr int U1 = 8;
-  for (uint64_t i0 = lo + threadIdx.x; i0 < hi; i0 += (uint64_t)U1 * blockDim.x) {
-    uint64_t k[U1];
-#pragma unroll
-    for (int u = 0; u < U1; ++u) {
-      const uint64_t i = i0 + (uint64_t)u * blockDim.x;
-      k[u] = i < hi ? P.key[i] : 0;
-    }
-#pragma unroll
-    for (int u = 0; u < U1; ++u)
-      if (k[u] != 0) atomicAdd(&cur[part_bin(k[u])], 1u);
-  }
-  __syncthreads();
-  // 2. reserve one contiguous run per bin (one returning atomic per bin)
-  for (uint32_t b = threadIdx.x; b < kPartBins; b += blockDim.x) {
-    const uint32_t c = (cur[b] + kPartStage - 1) & ~(kPartStage - 1);
-    uint32_t base = 0;
-    if (c) base = atomicAdd(&P.part_fill[b], c);
-    const uint64_t b0 = (uint64_t)b * P.part_cap;
-    cur[b] = (uint32_t)(b0 + min(base, P.part_cap));
-    lim[b] = (uint32_t)(b0 + min(base + c, P.part_cap));
-  }
-  __syncthreads();
-  // a span whose bin run is full: into the overflow table (hot keys of a
-  // skewed mix overfill their bins; per-span global atomics on one row would
-  // serialise), else the direct path
-  auto spill = [&](uint64_t key, uint64_t d, uint32_t bk) {
-    uint32_t h = ((uint32_t)key * 0x9E3779B1u) >> (32 - kPartHotBits);
-    for (int pr = 0; pr < 8; ++pr, h = (h + 1) & (kPartHot - 1)) {
-      unsigned long long k = hkey[h];
-      if (k == 0) k = atomicCAS(&hkey[h], 0ULL, (unsigned long long)key);
-      if (k == 0 || k == key) {
-        atomicAdd(&hcnt[h * kPartMaxBk + bk], 1u);
-        atomicAdd(&hsum[h], (unsigned long long)d);
-        return;
-      }
-    }
-    direct_red(P, key, d, bk, stride, st);
-  };
-  auto put = [&](uint32_t b, const ulonglong2 &rec, uint64_t d, uint32_t bk) {  // one record, now
-    const uint32_t r = atomicAdd(&cur[b], 1u);
-    if (r < lim[b]) P.part_rec[r] = rec;  // write-back: partial lines merge in L2
-    else spill(rec.x, d, bk);
-  };
-  // 3. every span: stats, sketches, and its record (or the direct path);
-  //    U spans per thread with all their loads issued first; rounds are
-  //    workgroup-uniform (the stages are flushed between them)
-  constexpr int U = PART_U;
-  for (uint64_t r0 = lo; r0 < hi; r0 += (uint64_t)U * blockDim.x) {
-   const uint64_t i0 = r0 + threadIdx.x;
-   uint64_t K[U], S0[U], E0[U], A[U], B[U];
-   uint32_t M[U];
-#pragma unroll
-   for (int u = 0; u < U; ++u) {
-     const uint64_t i = i0 + (uint64_t)u * blockDim.x;
-     const bool ok = i < hi;
-     K[u] = ok ? P.key[i] : 0;
-     S0[u] = ok ? P.start[i] : 0;
-     E0[u] = ok ? P.end[i] : 0;
-     A[u] = ok ? P.w0[i] : 0;
-     B[u] = ok ? P.w1[i] : 0;
-     M[u] = ok ? P.meta[i] : 0xFFFFu;  // padding lanes are skipped below
-   }
-   // sketch phase A for all U spans: the HLL register reads are issued
-   // together (unconditional: a skipped span reads the first byte)
-   uint32_t WS[U], RHO[U], CUR[U];
-   uint8_t *REG[U];
-#pragma unroll
-   for (int u = 0; u < U; ++u) {
-    const bool in = i0 + (uint64_t)u * blockDim.x < hi;
-    const uint32_t svc = M[u] & 0xFFFFu;
-    const bool svc_ok = svc < P.n_services;
-    const uint64_t win = fast_div(E0[u], P.window_ns, P.win_magic);
-    const bool win_ok = win - P.win_base < (uint64_t)P.n_windows;
-    if (in) {
-      st.zero_key += K[u] == 0 ? 1u : 0u;
-      st.bad_svc += svc_ok ? 0u : 1u;
-      st.oor += (svc_ok && !win_ok) ? 1u : 0u;
-    }
-    WS[u] = in && svc_ok && win_ok ? (uint32_t)(win & P.win_mask) : 0xFFFFFFFFu;
-    RHO[u] = 0;
-    REG[u] = P.hll;
-    if (WS[u] != 0xFFFFFFFFu && !(P.diag & 2u)) {
-      const uint64_t x = xxh64_16(A[u], B[u]);
-      RHO[u] = (uint32_t)__clzll((long long)((x << P.p) | (1ULL << (P.p - 1)))) + 1;
-      REG[u] = P.hll + ((((uint64_t)WS[u] * P.n_services + svc) << P.p) + (x >> (64 - P.p)));
-    }
-   }
-#pragma unroll
-   for (int u = 0; u < U; ++u) CUR[u] = *REG[u];
-#pragma unroll
-   for (int u = 0; u < U; ++u) {
-    if (i0 + (uint64_t)u * blockDim.x >= hi) continue;
-    const uint64_t key = K[u], s0 = S0[u], e0 = E0[u];
-    const uint32_t meta = M[u];
-    const uint64_t d = e0 > s0 ? e0 - s0 : 0;
-    const uint32_t bk = bucket_of<NB>(d, P);
-    const uint32_t ws = WS[u];
-    if (key != 0 && !(P.diag & 1u)) {
-      const uint32_t b = part_bin(key);
-      const ulonglong2 rec = make_ulonglong2(key, (d << 7) | bk);
-      if (d >= (1ULL << 57)) {
-        direct_red(P, key, d, bk, stride, st);
-      } else if (SA_PART_SKIP_USED && cur[b] >= lim[b]) {  // run used up (stays so): no stage, no cur atomic
-        spill(key, d, bk);
-      } else {
-        const uint32_t slot = atomicAdd(&scnt[b], 1u);
-        if (slot < kPartStage) stage[b * kPartStage + slot] = rec;
-        else put(b, rec, d, bk);
-      }
-    }
-    // ERROR spans: the exact per-(window, slot) counter (count-min cells are
-    // folded from it); no slot (key 0, table full): the cells directly
-    if (ws != 0xFFFFFFFFu && ((meta >> 19) & 3u) == 2u && !(P.diag & 4u)) {
-      const uint32_t slot = key != 0 ? g_find_insert(P.gkeys, key, P.log2cap, P.max_probe) : kNotFound;
-      if (slot != kNotFound) atomicAdd(P.errcnt + ((uint64_t)ws << P.log2cap) + slot, 1ULL);
-      else cms_add(P, ws, key, 1ULL);
-    }
-   }
-#pragma unroll
-   for (int u = 0; u < U; ++u)
-     if ((CUR[u] & 0xFFu) < RHO[u]) hll_raise(REG[u], RHO[u]);
-   // full stages leave as one chunk
-   __syncthreads();
-   for (uint32_t b = threadIdx.x; b < kPartBins; b += blockDim.x) {
-     if (scnt[b] < kPartStage) continue;
-     const uint32_t r = cur[b];
-     cur[b] = r + kPartStage;
-     scnt[b] = 0;
-#pragma unroll
-     for (int j = 0; j < (int)kPartStage; ++j) {
-       const ulonglong2 rec = stage[b * kPartStage + j];
-       if (r + j < lim[b]) P.part_rec[r + j] = rec;
-       else spill(rec.x, rec.y >> 7, (uint32_t)(rec.y & 127u));
-     }
-   }
-   __syncthreads();
-  }
-  // partial stages, then zero records over the run's unused tail (the
-  // padding, and the slots of spans that took the direct path)
-  __syncthreads();
-  for (uint32_t b = threadIdx.x; b < kPartBins; b += blockDim.x) {
-    for (uint32_t j = 0; j < scnt[b]; ++j) {
-      const ulonglong2 rec = stage[b * kPartStage + j];
-      put(b, rec, rec.y >> 7, (uint32_t)(rec.y & 127u));
-    }
-    for (uint32_t r = cur[b]; r < lim[b]; ++r) P.part_rec[r] = make_ulonglong2(0, 0);
-  }
-  // the overflow table: one atomic per non-zero cell per key (the aggregate
-  // kernel's plain row updates come after this kernel)
-  __syncthreads();
-  for (uint32_t h = threadIdx.x; h < kPartHot; h += blockDim.x) {
-    const unsigned long long key = hkey[h];
-    if (key == 0) continue;
-    const uint32_t g = g_find_insert(P.gkeys, key, P.log2cap, P.max_probe);
-    if (g == kNotFound) {
-      for (uint32_t b = 0; b < nbk; ++b) st.dropped += hcnt[h * kPartMaxBk + b];
-      continue;
-    }
-    unsigned long long *row = P.gcounts + (uint64_t)g * stride;
-    for (uint32_t b = 0; b < nbk; ++b)
-      if (const uint32_t c = hcnt[h * kPartMaxBk + b]) atomicAdd(row + row_count_cell(b), (unsigned long long)c);
-    atomicAdd(row + row_sum_cell(0), hsum[h]);
-  }
-  flush_stats(P, st);
-}
-
-// One workgroup per bin: LDS table of kPartSlots keys (linear probing from a
-// hash of the key's low bits; the bin fixes its top bits), u16 bucket-count
-// pairs (a bin holds < 2^16 records) and u64 ns sums -- 52 KiB, three
-// workgroups per CU -- then one read-modify-write of each key's HBM row.
-__global__ __launch_bounds__(kPartAggBlock) void part_aggregate_kernel(IngestParams P) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unsigned long long *lkeys = reinterpret_cast<unsigned long long *>(smem);
-  unsigned long long *lsum = lkeys + kPartSlots;
-  uint32_t *lcnt = reinterpret_cast<uint32_t *>(lsum + kPartSlots);  // [kPartSlots][kPartWords]
-  const uint32_t nbk = P.nbk, stride = row_stride(nbk);
-  auto cnt = [&](uint32_t s, uint32_t b) -> uint32_t {
-    return (lcnt[s * kPartWords + (b >> 1)] >> ((b & 1u) * 16)) & 0xFFFFu;
-  };
-  LaneStats st{0, 0, 0, 0};
-  __shared__ uint32_t spilled;  // direct-path atomics from this workgroup
-  if (threadIdx.x == 0) spilled = 0;
-  const uint32_t bin = blockIdx.x;
-  const uint32_t n = (P.diag & 1u) ? 0u : min(P.part_fill[bin], P.part_cap);  // diag 1: no records
-  for (uint32_t i = threadIdx.x; i < kPartSlots; i += blockDim.x) lkeys[i] = lsum[i] = 0;
-  for (uint32_t i = threadIdx.x; i < kPartSlots * kPartWords; i += blockDim.x) lcnt[i] = 0;
-  __syncthreads();
-  const ulonglong2 *rec = P.part_rec + (uint64_t)bin * P.part_cap;
-  constexpr int R = 8;  // records in flight per thread
-  for (uint32_t i0 = 0; i0 < n; i0 += R * blockDim.x) {
-    ulonglong2 v[R];
-#pragma unroll
-    for (int u = 0; u < R; ++u) {
-      const uint32_t i = i0 + u * blockDim.x + threadIdx.x;
-      v[u] = i < n ? rec[i] : make_ulonglong2(0, 0);
-    }
-#pragma unroll
-    for (int u = 0; u < R; ++u) {
-      const unsigned long long key = v[u].x;
-      if (key == 0) continue;
-      const uint64_t d = v[u].y >> 7;
-      const uint32_t bk = (uint32_t)(v[u].y & 127u);
-      uint32_t s = ((uint32_t)key * 0x9E3779B1u) >> (32 - kPartSlotBits), found = kNotFound;
-      for (int pr = 0; pr < 64; ++pr, s = (s + 1) & (kPartSlots - 1)) {
-        unsigned long long k = lkeys[s];
-        if (k == 0) k = atomicCAS(&lkeys[s], 0ULL, key);
-        if (k == 0 || k == key) {
-          found = s;
-          break;
-        }
-      }
-      if (found != kNotFound) {
-        atomicAdd(&lcnt[found * kPartWords + (bk >> 1)], 1u << ((bk & 1u) * 16));
-        atomicAdd(&lsum[found], (unsigned long long)d);
-      } else {
-        direct_red(P, key, d, bk, stride, st);
-        spilled = 1;
-      }
-    }
-  }
-  __syncthreads();
-  // Row updates below use plain loads: a row belongs to this workgroup's bin,
-  // so in this launch only this workgroup writes it (earlier launches' writes
-  // are visible at the kernel boundary).  After a direct-path spill the
-  // row may also hold this launch's atomics, which are performed beyond the
-  // XCD's L2: then fence and read at agent scope.
-  const bool coherent = spilled != 0;
-  if (coherent) {
-    __threadfence();
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) P.part_fill[bin] = 0;  // ready for the next launch
-  for (uint32_t s = threadIdx.x; s < kPartSlots && !(P.diag & 8u); s += blockDim.x) {
-    const unsigned long long key = lkeys[s];
-    if (key == 0) continue;
-    // the key's first-choice bucket in four independent loads (most keys sit
-    // there); the full probe sequence only for the rest
-    const ProbeSeq pr = probe_seq(key, P.log2cap);
-    const ulonglong2 *bq = reinterpret_cast<const ulonglong2 *>(P.gkeys + pr.b1 * 4);
-    const ulonglong2 qa = bq[0], qb = bq[1];  // stale reads just miss: see g_find_insert
-    const unsigned long long q[4] = {qa.x, qa.y, qb.x, qb.y};
-    uint32_t g = kNotFound;
-#pragma unroll
-    for (int j = 3; j >= 0; --j) g = q[j] == key ? pr.b1 * 4 + j : g;
-    if (g == kNotFound) g = g_find_insert(P.gkeys, key, P.log2cap, P.max_probe);
-    if (g == kNotFound) {
-      uint32_t calls = 0;
-      for (uint32_t b = 0; b < nbk; ++b) calls += cnt(s, b);
-      st.dropped += calls;
-      continue;
-    }
-    unsigned long long *row = P.gcounts + (uint64_t)g * stride;
-    // every load issued before any store (no wait per cell)
-    unsigned long long old[kPartMaxBk + 1];
-    if (coherent) {
-#pragma unroll
-      for (uint32_t b = 0; b < kPartMaxBk; ++b)  // unconditional (in-row address), no branch per load
-        old[b] = __hip_atomic_load(row + (b < nbk ? row_count_cell(b) : 0u), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-      old[kPartMaxBk] = __hip_atomic_load(row + row_sum_cell(0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-      // the row's (<= 3) 64-B segments as 16-B loads
-      constexpr uint32_t kSeg = (kPartMaxBk + kSegBuckets - 1) / kSegBuckets;
-      const uint32_t nseg = stride / 8;
-      ulonglong2 v[kSeg * 4];
-#pragma unroll
-      for (uint32_t k = 0; k < kSeg * 4; ++k)
-        v[k] = reinterpret_cast<const ulonglong2 *>(row)[(k / 4 < nseg ? k : k % 4)];
-      auto cell = [&](uint32_t c) -> unsigned long long { return (c & 1u) ? v[c / 2].y : v[c / 2].x; };
-#pragma unroll
-      for (uint32_t b = 0; b < kPartMaxBk; ++b) old[b] = b < nbk ? cell(row_count_cell(b)) : 0ULL;
-      old[kPartMaxBk] = cell(row_sum_cell(0));
-    }
-#pragma unroll
-    for (uint32_t b = 0; b < kPartMaxBk; ++b)
-      if (b < nbk && cnt(s, b)) row[row_count_cell(b)] = old[b] + cnt(s, b);
-    row[row_sum_cell(0)] = old[kPartMaxBk] + lsum[s];
-  }
-  flush_stats(P, st);
-}
-
-// ---------------------------------------------------------------------------
-// Flush-time kernels.
-// slabs -> counters.  blockIdx.y takes a group of kSlabGroup workgroup slabs;
-// each thread sums one 4-cell quad of them and adds the partial into the u64
-// counters (coalesced no-return atomics, G / kSlabGroup per cell).  The slabs
-// are cleared by a memset afterwards.
-constexpr uint32_t kSlabGroup = 16;
-__global__ void reduce_slabs_kernel(const uint32_t *slab_cnt, const unsigned long long *slab_sum,
-                                    unsigned long long *gcounts, uint32_t G, uint64_t cap,
-                                    uint32_t nbk) {
-  const uint32_t srow = (nbk + 1) & ~1u;  // 2 * ceil(nbk / 2)
-  const uint64_t cells = cap * srow, quads = cells / 4;
-  const uint32_t stride = row_stride(nbk);
-  const uint32_t g0 = blockIdx.y * kSlabGroup, g1 = min(G, g0 + kSlabGroup);
-  const uint64_t q = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-  if (q < quads) {
-    unsigned long long acc[4] = {0, 0, 0, 0};
-    for (uint32_t g = g0; g < g1; ++g) {
-      const uint4 v = reinterpret_cast<const uint4 *>(slab_cnt + (uint64_t)g * cells)[q];
-      acc[0] += v.x;
-      acc[1] += v.y;
-      acc[2] += v.z;
-      acc[3] += v.w;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const uint64_t c = q * 4 + i, slot = c / srow, b = c - slot * srow;
-      if (acc[i] && b < nbk) atomicAdd(gcounts + slot * stride + row_count_cell((uint32_t)b), acc[i]);
-    }
-  } else if (q < quads + cap) {
-    const uint64_t slot = q - quads;
-    unsigned long long acc = 0;
-    for (uint32_t g = g0; g < g1; ++g) acc += slab_sum[(uint64_t)g * cap + slot];
-    if (acc) atomicAdd(gcounts + slot * stride + row_sum_cell(0), acc);
-  }
-}
-
-// One counter row in the external layout [nbk bucket counts, ns sum] (u64),
-// from either row layout (u64 segment rows, or the binned path's 32-B u8 rows
-// + the u64 spill array).
-__device__ __forceinline__ bool row_nonzero(const unsigned long long *gcounts, uint64_t s, const RowGeom &g) {
-  if (g.row8) {
-    const uint4 *row = reinterpret_cast<const uint4 *>(gcounts) + s * (kRowBytes / 16);
-    const uint4 a = row[0], b = row[1];
-    if (a.x | a.y | a.z | a.w | b.x | b.y | b.z | b.w) return true;
-    for (uint32_t c = 0; c <= g.nbk; ++c)
-      if (g.base64[s * (g.nbk + 1) + c]) return true;
-    return false;
-  }
-  const uint32_t stride = row_stride(g.nbk);
-  const unsigned long long *row = gcounts + s * stride;
-  for (uint32_t c = 0; c < stride; ++c)
-    if (row[c]) return true;
-  return false;
-}
-
-__device__ __forceinline__ void row_emit(const unsigned long long *gcounts, uint64_t s, const RowGeom &g,
-                                         unsigned long long *out) {
-  const uint32_t nbk = g.nbk;
-  if (g.row8) {
-    const unsigned long long *row = gcounts + s * (kRowBytes / 8);
-    const uint8_t *cnt = reinterpret_cast<const uint8_t *>(row + 1);
-    const unsigned long long *b64 = g.base64 + s * (nbk + 1);
-    for (uint32_t b = 0; b < nbk; ++b) out[b] = cnt[b] + b64[b];
-    out[nbk] = row[0] + b64[nbk];
-    return;
-  }
-  const uint32_t stride = row_stride(nbk);
-  const unsigned long long *row = gcounts + s * stride;
-  unsigned long long sum = 0;
-  for (uint32_t c = 0; c < stride; c += 8) sum += row[c];
-  for (uint32_t b = 0; b < nbk; ++b) out[b] = row[row_count_cell(b)];
-  out[nbk] = sum;
-}
-
-__device__ __forceinline__ void row_zero(unsigned long long *gcounts, uint64_t s, const RowGeom &g) {
-  if (g.row8) {
-    uint4 *row = reinterpret_cast<uint4 *>(gcounts) + s * (kRowBytes / 16);
-    row[0] = row[1] = make_uint4(0, 0, 0, 0);
-    for (uint32_t c = 0; c <= g.nbk; ++c) g.base64[s * (g.nbk + 1) + c] = 0;
-    return;
-  }
-  const uint32_t stride = row_stride(g.nbk);
-  for (uint32_t c = 0; c < stride; ++c) gcounts[s * stride + c] = 0;
-}
-
-// Compacts occupied slots with a non-zero row into (out_keys, out_rows); order
-// is arrival order of the atomic ticket (the host sorts by key).  Keys leave
-// as the host's series ids (stored id * kinv), rows in the external layout.
-__global__ void compact_kernel(const unsigned long long *gkeys, unsigned long long *gcounts,
-                               uint64_t cap, RowGeom g, unsigned long long *out_keys,
-                               unsigned long long *out_rows, unsigned long long *out_n,
-                               uint64_t out_cap, int reset) {
-  const uint32_t ostride = g.nbk + 1;
-  for (uint64_t s = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; s < cap;
-       s += (uint64_t)gridDim.x * blockDim.x) {
-    const unsigned long long k = gkeys[s];
-    if (!k) {
-      // dense-index engines: spans on an index that was never bound -- no
-      // row is reported; a resetting pass counts them dropped and clears them
-      if (g.dense && reset && row_nonzero(gcounts, s, g)) {
-        const uint8_t *cnt = reinterpret_cast<const uint8_t *>(gcounts + s * (kRowBytes / 8) + 1);  // (row8)
-        unsigned long long calls = 0;
-        for (uint32_t b = 0; b < g.nbk; ++b) calls += cnt[b] + g.base64[s * (g.nbk + 1) + b];
-        atomicAdd(g.dropped, calls);
-        row_zero(gcounts, s, g);
-      }
-      continue;
-    }
-    if (!row_nonzero(gcounts, s, g)) continue;
-    // one returning atomic per wave for its emitting lanes (a million lanes
-    // on one counter serialised the compaction of a 1 M-series table)
-    const uint64_t m = __ballot(true);
-    const int leader = __builtin_ctzll(m);
-    unsigned long long base = 0;
-    if ((int)(threadIdx.x & 63u) == leader) base = atomicAdd(out_n, (unsigned long long)__popcll(m));
-    base = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(base >> 32), leader) << 32) |
-           (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)base, leader);
-    const unsigned long long pos =
-        base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-    if (pos < out_cap) {
-      if (out_keys) out_keys[pos] = k * g.kinv;
-      if (out_rows) row_emit(gcounts, s, g, out_rows + pos * ostride);
-    }
-    if (reset) row_zero(gcounts, s, g);
-  }
-}
-
-__device__ __forceinline__ uint32_t geom_find(const unsigned long long *gkeys, uint64_t m, const RowGeom &g) {
-  if (g.binned) {
-    const BtSeq q = bt_seq(m, g.log2sb);
-    const uint32_t base = (uint32_t)(m >> kBinShift) << g.log2sb;
-    for (uint32_t i = 0; i < bt_probe_max(g.log2sb); ++i) {
-      const uint32_t s = base | bt_pos(q, i);
-      const unsigned long long k = gkeys[s];
-      if (k == m) return s;
-      if (k == 0) return kNotFound;
-    }
-    return kNotFound;
-  }
-  return g_find(gkeys, m, g.log2cap, g.max_probe);
-}
-
-// rows[i] = [nbk bucket counts, ns sum] of keys[i] (zeros if absent).  One
-// 32-lane half wave per key: every lane probes the same key (one broadcast
-// load per probe), then lane c moves cells c, c + 32, ... so a row's reads
-// and its dense output row are contiguous across the lanes.
-__global__ void gather_dense_kernel(const unsigned long long *gkeys, const unsigned long long *gcounts,
-                                    RowGeom g, const uint64_t *keys, uint64_t n, uint64_t *rows) {
-  const uint32_t nbk = g.nbk, ostride = nbk + 1, c0 = threadIdx.x & 31u;
-  for (uint64_t i = (blockIdx.x * (uint64_t)blockDim.x + threadIdx.x) >> 5; i < n;
-       i += ((uint64_t)gridDim.x * blockDim.x) >> 5) {
-    const uint64_t k = keys[i];
-    const uint32_t s = k ? geom_find(gkeys, k * g.kmul, g) : kNotFound;
-    unsigned long long *out = reinterpret_cast<unsigned long long *>(rows) + i * ostride;
-    for (uint32_t c = c0; c < ostride; c += 32) {
-      unsigned long long v = 0;
-      if (s != kNotFound) {
-        if (g.row8) {
-          const unsigned long long *row = gcounts + (uint64_t)s * (kRowBytes / 8);
-          v = g.base64[(uint64_t)s * ostride + c] +
-              (c < nbk ? (unsigned long long)reinterpret_cast<const uint8_t *>(row + 1)[c] : row[0]);
-        } else {
-          const uint32_t stride = row_stride(nbk);
-          const unsigned long long *row = gcounts + (uint64_t)s * stride;
-          if (c < nbk) {
-            v = row[row_count_cell(c)];
-          } else {
-            for (uint32_t q = 0; q < stride; q += 8) v += row[q];
-          }
-        }
-      }
-      out[c] = v;
-    }
-  }
-}
-
-// errcnt[ws][slot] += sum over workgroups of errslab[g][ws << log2cap | slot]
-// (blockIdx.y = a group of kSlabGroup workgroups; no-return u64 atomics).
-__global__ void reduce_errslab_kernel(const uint32_t *errslab, uint32_t G, uint64_t per_wg,
-                                      uint64_t ws, uint32_t log2cap,
-                                      unsigned long long *errcnt_ws) {
-  const uint64_t cap = 1ULL << log2cap;
-  const uint64_t s = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-  if (s >= cap) return;
-  const uint32_t g0 = blockIdx.y * kSlabGroup, g1 = min(G, g0 + kSlabGroup);
-  unsigned long long acc = 0;
-  for (uint32_t g = g0; g < g1; ++g) acc += errslab[g * per_wg + (ws << log2cap) + s];
-  if (acc) atomicAdd(errcnt_ws + s, acc);
-}
-
-__global__ void count_keys_kernel(const unsigned long long *gkeys, uint64_t cap,
-                                  unsigned long long *out) {
-  uint32_t c = 0;
-  for (uint64_t s = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; s < cap;
-       s += (uint64_t)gridDim.x * blockDim.x)
-    c += gkeys[s] != 0;
-  c = wave_sum(c);
-  if ((threadIdx.x & 63) == 0 && c) atomicAdd(out, (unsigned long long)c);
-}
-
-// Window read: add the exact per-slot error counts of window slot `ws` into
-// its count-min cells, then clear them (so reads are idempotent).
-__global__ void fold_errcnt_kernel(const unsigned long long *gkeys, unsigned long long *errcnt,
-                                   uint64_t cap, unsigned long long *cms, uint32_t d, uint32_t w,
-                                   uint32_t shift, const uint64_t *seeds, uint64_t kinv, uint32_t dense) {
-  fold_errcnt_slots(gkeys, errcnt, cap, cms, d, w, shift, seeds, kinv, dense);
-}
-
-uint32_t grid_for(uint64_t work, uint32_t block, uint32_t cap_blocks) {
-  uint64_t g = (work + block - 1) / block;
-  if (g < 1) g = 1;
-  if (g > cap_blocks) g = cap_blocks;
-  return (uint32_t)g;
+  if constexpr (LEAN) flush_lds_stats(lstat);
+  flush_filtered(hq_n);
+  flush_wave_stats(n_zero, n_badsvc, n_oor, n_drop);
 }
 
 // The small-table kernels by name (sa_path.h SmallKernel): the v2 kernel
@@ -1826,96 +1313,6 @@ hipError_t launch_ingest_expo_small(const IngestParams &P, uint32_t grid, size_t
   void *args[] = {const_cast<IngestParams *>(&P)};
   const void *fn = expo_small_fn(expo_kernel(P.log2cap, P.p) == ExpoKernel::Specialised);
   return hipLaunchKernel(fn, dim3(grid), dim3(kLdsBlock), args, lds_bytes, s);
-}
-
-hipError_t launch_ingest_part(const IngestParams &P, hipStream_t s) {
-  const uint32_t grid = (uint32_t)std::min<uint64_t>(kPartMaxGrid, (P.n + kPartBlock - 1) / kPartBlock);
-  const void *fn = bounds16(P.nneg, P.npos) ? (const void *)&part_scatter_kernel<16> : (const void *)&part_scatter_kernel<-1>;
-  void *args[] = {const_cast<IngestParams *>(&P)};
-  if (hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(kPartBlock), args, kPartScatterLds, s); e != hipSuccess)
-    return e;
-  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-  hipLaunchKernelGGL(part_aggregate_kernel, dim3(kPartBins), dim3(kPartAggBlock), kPartLdsBytes, s, P);
-  return hipGetLastError();
-}
-
-hipError_t prepare_ingest_part() {
-  for (const void *fn : {(const void *)&part_scatter_kernel<16>, (const void *)&part_scatter_kernel<-1>})
-    if (hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPartScatterLds);
-        e != hipSuccess)
-      return e;
-  return hipFuncSetAttribute((const void *)&part_aggregate_kernel,
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPartLdsBytes);
-}
-
-hipError_t launch_ingest_hbm(const IngestParams &P, uint32_t grid, hipStream_t s) {
-  if (bounds16(P.nneg, P.npos)) hipLaunchKernelGGL(ingest_hbm_kernel<16>, dim3(grid), dim3(kHbmBlock), 0, s, P);
-  else hipLaunchKernelGGL(ingest_hbm_kernel<-1>, dim3(grid), dim3(kHbmBlock), 0, s, P);
-  return hipGetLastError();
-}
-
-hipError_t launch_reduce_slabs(uint32_t *slab_cnt, unsigned long long *slab_sum,
-                               unsigned long long *gcounts, uint32_t G, uint64_t cap,
-                               uint32_t nbk, hipStream_t s) {
-  const uint32_t block = 256;
-  const uint64_t srow = (nbk + 1) & ~1u, work = cap * srow / 4 + cap;
-  const dim3 grid((uint32_t)((work + block - 1) / block), (G + kSlabGroup - 1) / kSlabGroup);
-  hipLaunchKernelGGL(reduce_slabs_kernel, grid, dim3(block), 0, s, slab_cnt, slab_sum, gcounts, G,
-                     cap, nbk);
-  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-  if (hipError_t e = hipMemsetAsync(slab_cnt, 0, (size_t)G * cap * srow * 4, s); e != hipSuccess)
-    return e;
-  return hipMemsetAsync(slab_sum, 0, (size_t)G * cap * 8, s);
-}
-
-hipError_t launch_compact(const unsigned long long *gkeys, unsigned long long *gcounts,
-                          uint64_t cap, const RowGeom &g, unsigned long long *out_keys,
-                          unsigned long long *out_rows, unsigned long long *out_n,
-                          uint64_t out_cap, int reset, hipStream_t s) {
-  const uint32_t block = 256;
-  hipLaunchKernelGGL(compact_kernel, dim3(grid_for(cap, block, 4096)), dim3(block), 0, s, gkeys,
-                     gcounts, cap, g, out_keys, out_rows, out_n, out_cap, reset);
-  return hipGetLastError();
-}
-
-hipError_t launch_gather_dense(const unsigned long long *gkeys, const unsigned long long *gcounts,
-                               const RowGeom &g, const uint64_t *keys, uint64_t n, uint64_t *rows,
-                               hipStream_t s) {
-  if (n == 0) return hipSuccess;
-  const uint32_t block = 256;
-  hipLaunchKernelGGL(gather_dense_kernel, dim3(grid_for(n * 32, block, 8192)), dim3(block), 0, s,  // (32 lanes a key)
-                     gkeys, gcounts, g, keys, n, rows);
-  return hipGetLastError();
-}
-
-hipError_t launch_fold_errcnt(const unsigned long long *gkeys, unsigned long long *errcnt,
-                              uint64_t cap, unsigned long long *cms, uint32_t d, uint32_t w,
-                              uint32_t shift, const uint64_t *seeds, uint64_t kinv, uint32_t dense,
-                              hipStream_t s) {
-  const uint32_t block = 256;
-  hipLaunchKernelGGL(fold_errcnt_kernel, dim3(grid_for(cap, block, 2048)), dim3(block), 0, s, gkeys,
-                     errcnt, cap, cms, d, w, shift, seeds, kinv, dense);
-  return hipGetLastError();
-}
-
-hipError_t launch_reduce_errslab(uint32_t *errslab, uint32_t G, uint64_t per_wg, uint64_t ws,
-                                 uint32_t log2cap, unsigned long long *errcnt_ws, hipStream_t s) {
-  const uint32_t block = 256;
-  const uint64_t cap = 1ULL << log2cap;
-  const dim3 grid((uint32_t)((cap + block - 1) / block), (G + kSlabGroup - 1) / kSlabGroup);
-  hipLaunchKernelGGL(reduce_errslab_kernel, grid, dim3(block), 0, s, errslab, G, per_wg, ws, log2cap,
-                     errcnt_ws);
-  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-  // clear window ws's cells of every workgroup slab (a strided 2-D memset)
-  return hipMemset2DAsync(errslab + (ws << log2cap), per_wg * 4, 0, cap * 4, G, s);
-}
-
-hipError_t launch_count_keys(const unsigned long long *gkeys, uint64_t cap,
-                             unsigned long long *out, hipStream_t s) {
-  const uint32_t block = 256;
-  hipLaunchKernelGGL(count_keys_kernel, dim3(grid_for(cap, block, 2048)), dim3(block), 0, s,
-                     gkeys, cap, out);
-  return hipGetLastError();
 }
 
 }  // namespace sa

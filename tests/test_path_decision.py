@@ -24,12 +24,16 @@ Default bounds: nbk = 17, so Small needs cap*52 + 24,704 <= 147,456: cap <=
 The program also prints the remaining geometry decisions of sa_path.h: the
 small-table kernel (small_kernel), the small exponential table's kernel
 (expo_kernel), whether the HBM kernels' 16-bound instance applies (bounds16),
-the HLL filter's sub-blocks (hll_filter_geometry) and the small tables' ERROR
-table rule (error_table).  tests/geometry_util.py states those rules and works
-every row of its matrix out by hand; the rows are checked here on the CPU and
-run on the GPU by tests/test_gpu_geometry.py.  The rows of the moving-ring
-matrix (RING_ROWS, run by tests/test_gpu_ring.py) go through the same program
-and the same assertions.
+the HLL filter's sub-blocks (hll_filter_geometry), the small tables' ERROR
+table rule (error_table) and, for an LDS table, where the kernels' LDS layout
+(small_lds_layout) ends, which must be the launch's lds_bytes (the list
+summed here against the list summed by decide_path: it shows that decide_path
+passes the kernel's counter words and EXPO flag, no more).
+tests/geometry_util.py states those rules and works every row of its matrix
+out by hand; the rows are checked here on the CPU and run on the GPU by
+tests/test_gpu_geometry.py.  The rows of the moving-ring matrix (RING_ROWS,
+run by tests/test_gpu_ring.py) go through the same program and the same
+assertions.
 
 The same program also runs built with -fsanitize=address,undefined (plain
 host code; nothing is preloaded).
@@ -123,8 +127,15 @@ int main() {
       spl = sa::small_spans_per_lane(k);
       v2 = sa::small_is_v2(k);
     }
-    std::printf("%s %u %zu %s %u %u %d %u %u %u %u\n", names[(int)pc.path], log2cap, pc.lds_bytes, kernel, lb.shift, lb.n,
-                (int)(sa::lds_table(pc.path) && sa::error_table(c.n_windows, cap)), h.nneg, block, spl, v2);
+    // where the kernel's LDS layout ends, walked region by region (0: no LDS table)
+    size_t lds_end = 0;
+    if (sa::lds_table(pc.path)) {
+      const bool x = pc.path == sa::Path::ExpoSmall;
+      const sa::SmallLdsLayout layout = sa::small_lds_layout(cap, x ? sa::kExpoWords : (h.nbk + 1) / 2, x);
+      for (const sa::LdsRegion &r : layout.r) lds_end += r.n * r.elem;
+    }
+    std::printf("%s %u %zu %s %u %u %d %u %u %u %u %zu\n", names[(int)pc.path], log2cap, pc.lds_bytes, kernel, lb.shift,
+                lb.n, (int)(sa::lds_table(pc.path) && sa::error_table(c.n_windows, cap)), h.nneg, block, spl, v2, lds_end);
   }
   return 0;
 }
@@ -165,6 +176,7 @@ def test_path_table(tmp_path, flags):
         assert (g[0], int(g[1])) == (path, log2cap), (cfg[:4], g)
         if i in LDS:
             assert int(g[2]) == LDS[i], (cfg[:4], g)
+        _assert_layout_end(g, cfg[:4])
     # the default table is the default geometry: the specialised kernels, the 16-bound instances
     assert [g[3] for g in got[:3]] == ["small_default", "expo_specialised", "bounds16"]
     assert got[7][3] == "small_linear"  # CROWDED on a small table
@@ -177,8 +189,17 @@ def test_path_table(tmp_path, flags):
     _assert_rows(RING_ROWS, ring)
 
 
+def _assert_layout_end(g, what):
+    """An LDS table's launch size is where the kernels' layout ends (sa_path.h small_lds_layout)."""
+    if g[0] in ("Small", "ExpoSmall"):
+        assert int(g[11]) == int(g[2]) > 0, (what, g)
+    else:
+        assert int(g[11]) == 0, (what, g)
+
+
 def _assert_rows(rows, got):
     for (name, r), g in zip(rows.items(), got):
+        _assert_layout_end(g, name)
         assert (g[0], int(g[1]), g[3]) == (r["path"], r["log2cap"], r["kernel"]), (name, g)
         assert (int(g[4]), int(g[5])) == r["lb"], (name, g)
         assert bool(int(g[6])) == r["error_table"], (name, g)
