@@ -4,7 +4,8 @@ config, and the comparison with the CPU oracle.
 ROWS is shared by tests/test_path_decision.py (the decisions on the CPU) and
 tests/test_gpu_geometry.py (the kernels on the GPU); RING_ROWS, the small rings
 of the moving-ring walk (tests/ring_util.py), by tests/test_path_decision.py,
-tests/test_ring_walk.py and tests/test_gpu_ring.py.  Each row's expectation is
+tests/test_ring_walk.py and tests/test_gpu_ring.py (tests/hll_util.py adds six
+rows of the same form for hll_p 4 and 18).  Each row's expectation is
 written from the rules, not read from the code:
 
   cap   = next power of two >= 1.25 x key_capacity (>= 16; SA_OPT_DENSE_IDS: >= 2^19)
@@ -175,9 +176,10 @@ def config_of(row) -> Config:
     return Config(**(RING_ROWS.get(row) or ROWS[row])["cfg"])
 
 
-def assert_geometry(e, row):
-    """Engine.debug_geometry() against the row's expectation (ROWS or RING_ROWS)."""
-    r, g = RING_ROWS.get(row) or ROWS[row], e.debug_geometry()
+def assert_geometry(e, row, rows=None):
+    """Engine.debug_geometry() against the row's expectation (ROWS or RING_ROWS,
+    or another matrix `rows` of the same form)."""
+    r, g = (rows or {}).get(row) or RING_ROWS.get(row) or ROWS[row], e.debug_geometry()
     assert (g["path"], g["kernel"], g["log2cap"]) == (r["path"], r["kernel"], r["log2cap"]), g
     assert (g["lb_shift"], g["lb_n"]) == r["lb"], g
     assert g["error_table"] == r["error_table"], g

@@ -20,7 +20,7 @@ moved rings, p4 and p18) and one more:
          reach, and the earlier of two windows that share a register holds the
          larger value, so in every span the first window holds a strict
          maximum and the window before the span exceeds it.  The marker's
-         trace id is built from the wanted hash (trace_with_hash: the 16-byte
+         trace id is built from the wanted hash (hll_util.trace_with_hash: the 16-byte
          xxh64 run backwards).
 
   wide512  Config(key_capacity=800, hll_p=5, n_services=20, n_windows=512): one
@@ -49,6 +49,7 @@ import numpy as np
 
 import range_util
 from geometry_util import RING_ROWS, key_pool, make_batch, ring_start
+from hll_util import trace_with_hash
 from spanagg import Config
 from spanagg.sketch import CMS_SEEDS
 
@@ -65,34 +66,6 @@ LONG_WIDTHS = (1, 7, 32, 33, 64, 100, 128, 129, 255, 256)
 WIDE_CFG = Config(key_capacity=800, hll_p=5, n_services=20, n_windows=512)
 WIDE_FILL, WIDE_WIDTHS = 4, (256, 257, 512)
 NOERR_WIDTHS = (1, 2, 3, 5, 8, 16, 31, 32)
-
-
-_M64 = (1 << 64) - 1
-_P1, _P2, _P3, _P4, _P5 = (0x9E3779B185EBCA87, 0xC2B2AE3D27D4EB4F, 0x165667B19E3779F9, 0x85EBCA77C2B2AE63,
-                           0x27D4EB2F165667C5)  # xxh64's primes
-
-
-def _rotl(v, r):
-    return ((v << r) | (v >> (64 - r))) & _M64
-
-
-def _inv(a):
-    return pow(a, -1, 1 << 64)
-
-
-def trace_with_hash(x, w0):
-    """trace_w1 such that xxh64 of the 16 trace-id bytes (w0, w1 little-endian,
-    seed 0) is x: the avalanche and the second lane's round undone."""
-    h = x
-    h ^= h >> 32
-    h = h * _inv(_P3) & _M64
-    h ^= h >> 29
-    h ^= h >> 58
-    h = h * _inv(_P2) & _M64
-    h ^= h >> 33
-    h1 = (_rotl(((_P5 + 16) & _M64) ^ (_rotl(w0 * _P2 & _M64, 31) * _P1 & _M64), 27) * _P1 + _P4) & _M64
-    r = _rotl((h - _P4) * _inv(_P1) & _M64, 64 - 27) ^ h1
-    return _rotl(r * _inv(_P1) & _M64, 64 - 31) * _inv(_P2) & _M64
 
 
 def long_markers(cfg, base):

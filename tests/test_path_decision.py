@@ -32,8 +32,9 @@ passes the kernel's counter words and EXPO flag, no more).
 tests/geometry_util.py states those rules and works every row of its matrix
 out by hand; the rows are checked here on the CPU and run on the GPU by
 tests/test_gpu_geometry.py.  The rows of the moving-ring matrix (RING_ROWS,
-run by tests/test_gpu_ring.py) go through the same program and the same
-assertions.
+run by tests/test_gpu_ring.py) and the rows for the ends of hll_p
+(hll_util.HLL_ROWS, run by tests/test_gpu_hll_ids.py) go through the same
+program and the same assertions.
 
 The same program also runs built with -fsanitize=address,undefined (plain
 host code; nothing is preloaded).
@@ -45,6 +46,7 @@ import subprocess
 import pytest
 
 from geometry_util import RING_ROWS, ROWS
+from hll_util import HLL_ROWS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "opentelemetry-demo_amd", "csrc")
@@ -187,6 +189,11 @@ def test_path_table(tmp_path, flags):
     ring = [tuple(ln.split()) for ln in ring if ln]
     assert len(ring) == len(RING_ROWS)
     _assert_rows(RING_ROWS, ring)
+    ends = subprocess.run([str(exe)], input="".join(_line(**r["cfg"]) for r in HLL_ROWS.values()),
+                          capture_output=True, text=True, check=True).stdout.split("\n")
+    ends = [tuple(ln.split()) for ln in ends if ln]
+    assert len(ends) == len(HLL_ROWS) == 6
+    _assert_rows(HLL_ROWS, ends)
 
 
 def _assert_layout_end(g, what):
