@@ -20,6 +20,7 @@
  *   (new) the same over a span of windows           sa_window_range (merged on the device)
  *   (new) every trailing span of a window series    sa_window_series (one pass over the ring)
  *   (new) heavy hitters over a span of windows      sa_window_top (key table scanned on the device)
+ *   (new) traces shared by pairs of services        sa_window_overlap (pairwise register maxima on the device)
  *
  * Boundary rules (mirroring the connector's contracts):
  *  - Ownership: batches are borrowed for the duration of the call (page-locked
@@ -411,6 +412,59 @@ int sa_window_top(sa_engine *e, uint64_t first, uint64_t last, uint32_t k, uint6
                   uint32_t flags, sa_top_result **out);
 void sa_top_result_free(sa_top_result *r);
 
+/* ---- service overlap over the window ring ----
+ * "How many traces do two services share over these windows": every service's
+ * registers are filled from the same hash of the trace id, so the register-wise
+ * maximum of two services' arrays is the HLL of the union of their trace sets,
+ * and inclusion-exclusion gives the intersection.  The pairwise maxima and
+ * their histograms are taken on the device; only the histograms cross the bus. */
+#define SA_OVERLAP_MAX_SERVICES 64u
+typedef struct {
+    uint64_t first_window, last_window;  /* inclusive */
+    uint32_t n_sel, n_pairs;             /* n_pairs = n_sel * (n_sel - 1) / 2 */
+    uint32_t hll_p, pad;
+    const uint32_t *services;   /* [n_sel] service ids, in the caller's order */
+    const uint32_t *hll_hist;   /* [n_sel][SA_HLL_HIST_BINS]: as sa_range_result.hll_hist rows */
+    const double   *distinct;   /* [n_sel] sa_hll_estimate_hist(hll_hist row, hll_p) */
+    const uint32_t *pair_hist;  /* [n_pairs][SA_HLL_HIST_BINS]: value histogram of
+                                   max(merged regs of services[i], of services[j]), i < j,
+                                   pair index i*n_sel - i*(i+1)/2 + (j-i-1); every row sums to 2^hll_p */
+    const double   *union_est;  /* [n_pairs] sa_hll_estimate_hist(pair_hist row, hll_p) */
+    const double   *shared;     /* [n_pairs] fmax(0.0, (distinct[i] + distinct[j]) - union_est[pair]) */
+} sa_overlap_result;
+
+/* Merge first, then pair: the windows first..last are max-merged per selected
+ * service -- exactly the registers sa_window_range returns with
+ * SA_RANGE_REGISTERS -- and the pairs are taken on the merged arrays (pairing
+ * per window and adding would be wrong: a trace that meets service a in one
+ * window and service b in the next is shared).
+ * hll_hist / distinct: row i is bit for bit what sa_window_range returns for
+ * service services[i].  pair_hist is integer counts; union_est and shared are
+ * computed on the host from the histograms in exactly the arithmetic written
+ * above, so two calls give equal bits, and an engine and a group give equal
+ * bits.
+ * Selection: services == NULL with n_sel == 0 selects every service in id
+ * order, allowed only when n_services <= SA_OVERLAP_MAX_SERVICES.  n_sel == 1
+ * is valid: zero pairs and the one histogram.
+ * SA_EINVAL for services == NULL with n_sel == 0 on an engine with more than
+ * SA_OVERLAP_MAX_SERVICES services, services == NULL with n_sel != 0, n_sel
+ * == 0 with services given, n_sel > SA_OVERLAP_MAX_SERVICES, an id >= n_services, a repeated id, flags != 0
+ * (reserved), a null `out`; SA_ERANGE as sa_window_range; SA_ENOMEM when the
+ * device scratch (at most n_sel x 2^hll_p bytes plus the histograms, allocated
+ * by the first call) or the result cannot be allocated.  The engine stays
+ * usable after any error.
+ * Ordering and waiting as sa_window_range: joins every launch in flight, runs
+ * on the engine stream, waits once, clears nothing.  Works on every ingest
+ * path, SA_OPT_DENSE_IDS included: only the registers are read.
+ * Accuracy: each of the three estimates (distinct[i], distinct[j], union_est)
+ * carries about 1.04 / sqrt(2^hll_p) relative error of its own size, so shared
+ * is meaningful only where it is not small against union_est x 1.04 /
+ * sqrt(2^hll_p).  The call is exact with respect to the sketches, like
+ * sa_window_top.  Free the result with sa_overlap_result_free. */
+int sa_window_overlap(sa_engine *e, uint64_t first, uint64_t last, const uint32_t *services,
+                      uint32_t n_sel, uint32_t flags, sa_overlap_result **out);
+void sa_overlap_result_free(sa_overlap_result *r);
+
 int sa_get_stats(sa_engine *e, sa_stats *out);
 
 /* ---- multi-GPU merge hooks (device pointers on this engine's device) ----
@@ -507,6 +561,13 @@ int sa_group_window_range(sa_group *g, uint64_t first, uint64_t last, const uint
  * sa_group_get_stats does). */
 int sa_group_window_top(sa_group *g, uint64_t first, uint64_t last, uint32_t k, uint64_t min_count,
                         uint32_t flags, sa_top_result **out);
+/* sa_window_overlap of a group: every member max-merges its own windows on
+ * its device, the group's transport merges the members' registers (max, every
+ * service's rows as for sa_group_window_range), and member 0's device gathers
+ * the selected rows and takes the pairwise maxima.  Results equal those of one
+ * engine fed every span, bit for bit. */
+int sa_group_window_overlap(sa_group *g, uint64_t first, uint64_t last, const uint32_t *services,
+                            uint32_t n_sel, uint32_t flags, sa_overlap_result **out);
 /* Counters summed over members (n_keys and table_capacity too; window_base and
  * small_table from member 0). */
 int sa_group_get_stats(sa_group *g, sa_stats *out);

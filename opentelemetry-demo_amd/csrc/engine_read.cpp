@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <new>
@@ -311,9 +312,113 @@ int top_on(sa_engine *e, const unsigned long long *d_cells, uint32_t k, uint64_t
   (void)hipStreamSynchronize(s);  // (a copy into h may be in flight)
   return fail(e, SA_EDEVICE, std::string("window top: ") + hipGetErrorString(st));
 }
+
+// ---- service overlap (sa_window_overlap; kernels in spanagg_range.hip and spanagg_overlap.hip) ----
+// The counting form of the pair kernel: the laboratory build reads
+// SPANAGG_OVERLAP (0, 1, 2) at every call, the product holds variant 0 alone.
+uint32_t overlap_variant() {
+#ifdef SPANAGG_AB
+  if (const char *v = ab_env("SPANAGG_OVERLAP")) return (uint32_t)std::atoi(v);
+#endif
+  return 0;
+}
+
+int overlap_buffers(sa_engine *e) {
+  sa_engine::Overlap &O = e->overlap;
+  const size_t cap = std::min<size_t>(e->cfg.n_services, SA_OVERLAP_MAX_SERVICES);
+  if (!O.map)
+    if (int rc = dalloc(e, O.map, cap, false, "window overlap: selection hipMalloc failed")) return rc;
+  if (!O.hist)
+    if (int rc = dalloc(e, O.hist, cap * SA_HLL_HIST_BINS, false, "window overlap: histogram hipMalloc failed")) return rc;
+  if (!O.pair_hist)
+    if (int rc = dalloc(e, O.pair_hist, cap * (cap - 1) / 2 * SA_HLL_HIST_BINS, false,
+                        "window overlap: pair histogram hipMalloc failed"))
+      return rc;
+  if (!O.regs)
+    if (int rc = dalloc(e, O.regs, cap << e->cfg.hll_p, false, "window overlap: register buffer hipMalloc failed"))
+      return rc;
+  return SA_OK;
+}
+
+// On `s` (waited for): the registers regs [n_win slots of n_services][2^p] of
+// windows first .. first + n_win - 1 (ring of n_windows slots) max-merged for
+// the services of sel, their histograms, the pairs' histograms, the copies
+// into the result and the estimates.
+int overlap_on(sa_engine *e, uint64_t first, uint64_t last, const uint8_t *regs, uint32_t n_windows, uint64_t from,
+               uint32_t n_win, const std::vector<uint32_t> &sel, hipStream_t s, sa_overlap_result **out) {
+  std::unique_ptr<overlap_holder> h;
+  try {
+    h.reset(new overlap_holder());
+    h->shape(first, last, sel, e->cfg.hll_p);
+  } catch (const std::bad_alloc &) {
+    return fail(e, SA_ENOMEM, "window overlap: the result does not fit in host memory");
+  }
+  if (int rc = overlap_buffers(e)) return rc;
+  const sa_engine::Overlap &O = e->overlap;
+  const uint32_t n = (uint32_t)sel.size(), p = e->cfg.hll_p;
+  hipError_t st = hipMemcpyAsync(O.map, sel.data(), (size_t)n * 4, hipMemcpyHostToDevice, s);
+  if (st == hipSuccess) st = hipMemsetAsync(O.hist, 0, h->hist.size() * 4, s);
+  if (st == hipSuccess && h->r.n_pairs) st = hipMemsetAsync(O.pair_hist, 0, h->pair_hist.size() * 4, s);
+  if (st == hipSuccess)
+    st = sa::launch_range_merge_sel(regs, n_windows, e->cfg.n_services, p, from, n_win, O.map, n, O.hist, O.regs, s);
+  if (st == hipSuccess) st = sa::launch_overlap_pairs(O.regs, n, p, O.pair_hist, overlap_variant(), s);
+  if (st == hipSuccess) st = hipMemcpyAsync(h->hist.data(), O.hist, h->hist.size() * 4, hipMemcpyDeviceToHost, s);
+  if (st == hipSuccess && h->r.n_pairs)
+    st = hipMemcpyAsync(h->pair_hist.data(), O.pair_hist, h->pair_hist.size() * 4, hipMemcpyDeviceToHost, s);
+  const hipError_t waited = hipStreamSynchronize(s);  // the call's one wait (also after a failure: copies may be in flight)
+  if (st != hipSuccess || waited != hipSuccess)
+    return fail(e, SA_EDEVICE, std::string("window overlap: ") + hipGetErrorString(st != hipSuccess ? st : waited));
+  for (uint32_t i = 0; i < n; ++i)
+    h->distinct[i] = sa_hll_estimate_hist(h->hist.data() + (size_t)i * SA_HLL_HIST_BINS, p);
+  size_t pair = 0;
+  for (uint32_t i = 0; i < n; ++i)
+    for (uint32_t j = i + 1; j < n; ++j, ++pair) {
+      h->union_est[pair] = sa_hll_estimate_hist(h->pair_hist.data() + pair * SA_HLL_HIST_BINS, p);
+      h->shared[pair] = std::fmax(0.0, (h->distinct[i] + h->distinct[j]) - h->union_est[pair]);
+    }
+  *out = &h.release()->r;
+  return SA_OK;
+}
 }  // namespace
 
 namespace sa_grp {
+const char *overlap_select(uint32_t n_services, const uint32_t *services, uint32_t n_sel, std::vector<uint32_t> *sel) {
+  sel->clear();
+  if (!services) {
+    if (n_sel) return "window overlap: n_sel != 0 with null services";
+    if (n_services > SA_OVERLAP_MAX_SERVICES)
+      return "window overlap: every service asked for on an engine with more than SA_OVERLAP_MAX_SERVICES";
+    for (uint32_t i = 0; i < n_services; ++i) sel->push_back(i);
+    return nullptr;
+  }
+  if (n_sel == 0) return "window overlap: an empty selection";
+  if (n_sel > SA_OVERLAP_MAX_SERVICES) return "window overlap: more than SA_OVERLAP_MAX_SERVICES services";
+  for (uint32_t i = 0; i < n_sel; ++i) {
+    if (services[i] >= n_services) return "window overlap: a service id at or past n_services";
+    if (std::find(sel->begin(), sel->end(), services[i]) != sel->end()) return "window overlap: a repeated service id";
+    sel->push_back(services[i]);
+  }
+  return nullptr;
+}
+
+int window_overlap_export_async(sa_engine *e, uint64_t first, uint64_t last, uint8_t *d_hll, hipStream_t s) {
+  if (!e || !d_hll) return SA_EINVAL;
+  if (int rc = range_args(e, first, last, nullptr, 0, 0)) return rc;
+  if (int rc = begin_read(e)) return rc;
+  if (int rc = hop_to(e, s)) return rc;
+  SA_HIP(e, sa::launch_range_merge(e->hll, e->cfg.n_windows, e->cfg.n_services, e->cfg.hll_p, first,
+                                   (uint32_t)(last - first + 1), nullptr, d_hll, s));
+  return hop_back(e, s);
+}
+
+int window_overlap_finish(sa_engine *e, uint64_t first, uint64_t last, const uint8_t *d_hll,
+                          const std::vector<uint32_t> &sel, hipStream_t s, sa_overlap_result **out) {
+  if (!e || !out || !d_hll || sel.empty()) return SA_EINVAL;
+  if (int rc = set_dev(e)) return rc;
+  // (the merged array as a ring of one window: the gather of the selected rows)
+  return overlap_on(e, first, last, d_hll, 1, 0, 1, sel, s, out);
+}
+
 bool over_reclaim_threshold(const sa_engine *e, uint64_t nk) {
   return sa::binned_like(e->path) ? 20 * nk > 7 * (uint64_t)e->cap : 2 * nk > e->cap;
 }
@@ -718,6 +823,25 @@ int sa_window_top(sa_engine *e, uint64_t first, uint64_t last, uint32_t k, uint6
 }
 
 void sa_top_result_free(sa_top_result *r) { delete reinterpret_cast<top_holder *>(r); }
+
+int sa_window_overlap(sa_engine *e, uint64_t first, uint64_t last, const uint32_t *services, uint32_t n_sel,
+                      uint32_t flags, sa_overlap_result **out) {
+  if (!e || !out) return SA_EINVAL;
+  *out = nullptr;
+  if (flags) return fail(e, SA_EINVAL, "window overlap: flags are reserved (0)");
+  std::vector<uint32_t> sel;
+  try {
+    if (const char *bad = sa_grp::overlap_select(e->cfg.n_services, services, n_sel, &sel)) return fail(e, SA_EINVAL, bad);
+  } catch (const std::bad_alloc &) {
+    return fail(e, SA_ENOMEM, "window overlap: the selection does not fit in host memory");
+  }
+  if (int rc = range_args(e, first, last, nullptr, 0, 0)) return rc;
+  if (int rc = begin_read(e)) return rc;
+  // (only the registers are read: no window's ERROR counts are folded)
+  return overlap_on(e, first, last, e->hll, e->cfg.n_windows, first, (uint32_t)(last - first + 1), sel, e->stream, out);
+}
+
+void sa_overlap_result_free(sa_overlap_result *r) { delete reinterpret_cast<overlap_holder *>(r); }
 
 int sa_window_advance(sa_engine *e, uint64_t new_base) {
   if (!e) return SA_EINVAL;

@@ -215,6 +215,17 @@ struct LaneStats {
   uint32_t zero_key, bad_svc, oor, dropped;
 };
 
+// max of four u8 lanes, each below 128 (an HLL register is at most 65 - p):
+// (a | 0x80) - b keeps bit 7 exactly where a >= b and borrows from no neighbour
+__device__ __forceinline__ uint32_t max_u8x4(uint32_t a, uint32_t b) {
+  const uint32_t ge = (((a | 0x80808080u) - b) >> 7) & 0x01010101u;
+  const uint32_t m = ge * 0xFFu;
+  return (a & m) | (b & ~m);
+}
+__device__ __forceinline__ uint4 max_u8x16(uint4 a, uint4 b) {
+  return uint4{max_u8x4(a.x, b.x), max_u8x4(a.y, b.y), max_u8x4(a.z, b.z), max_u8x4(a.w, b.w)};
+}
+
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

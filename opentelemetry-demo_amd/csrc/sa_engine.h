@@ -215,6 +215,14 @@ struct sa_engine {
     ulonglong2 *cand = nullptr;
     sa::TopCtl *ctl = nullptr;
   } top;
+  // sa_window_overlap (allocated by its first call, for min(n_services,
+  // SA_OVERLAP_MAX_SERVICES) = cap services): the selected ids [cap], their
+  // merged registers [cap][2^p] and histograms [cap][SA_HLL_HIST_BINS], and
+  // the pairs' histograms [cap (cap - 1) / 2][SA_HLL_HIST_BINS]
+  struct Overlap {
+    uint32_t *map = nullptr, *hist = nullptr, *pair_hist = nullptr;
+    uint8_t *regs = nullptr;
+  } overlap;
   // sa_ingest: two pinned host slots and their HBM copies; a slot is refilled
   // once its event (H2D copy + aggregation of the previous use) has passed
   struct HostStage {

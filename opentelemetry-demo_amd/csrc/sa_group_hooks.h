@@ -42,6 +42,21 @@ int window_range_export_async(sa_engine *e, uint64_t first, uint64_t last, uint8
 // sa_window_range.
 int window_range_finish(sa_engine *e, uint64_t first, uint64_t last, const uint8_t *d_hll, const uint64_t *d_cms,
                         const uint64_t *keys, uint64_t n_keys, uint32_t flags, hipStream_t s, sa_range_result **out);
+// sa_window_overlap's selection rules for an engine of n_services services:
+// *sel = the ids in the caller's order (services == nullptr with n_sel == 0:
+// every id).  nullptr when valid, else what is wrong (SA_EINVAL).
+const char *overlap_select(uint32_t n_services, const uint32_t *services, uint32_t n_sel, std::vector<uint32_t> *sel);
+// sa_window_overlap's merge for one member, without the wait: d_hll
+// [n_services][2^p] = the registers of windows first..last max-merged, on `s`
+// (no cell is folded or summed: only the registers are read).  SA_ERANGE as
+// sa_window_range.
+int window_overlap_export_async(sa_engine *e, uint64_t first, uint64_t last, uint8_t *d_hll, hipStream_t s);
+// the rest of a group's overlap query, on member 0 (`e`, whose device holds
+// the members' merged d_hll [n_services][2^p]) and on `s`: the selected rows
+// gathered with their histograms, the pairs' histograms, the copies, the wait
+// and the estimates.  sel: overlap_select's.
+int window_overlap_finish(sa_engine *e, uint64_t first, uint64_t last, const uint8_t *d_hll,
+                          const std::vector<uint32_t> &sel, hipStream_t s, sa_overlap_result **out);
 // What one engine's heavy-hitter scan leaves on the host once its stream
 // passes the copies: head = the matches, the resident keys, the largest
 // estimate, error_spans; rows [k] = (estimate, key) pairs, the first

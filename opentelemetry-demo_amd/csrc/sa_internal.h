@@ -417,6 +417,20 @@ hipError_t launch_dn_bind(unsigned long long *gkeys, const uint64_t *index, cons
 // none): the merged registers themselves
 hipError_t launch_range_merge(const uint8_t *hll, uint32_t n_windows, uint32_t n_services, uint32_t p, uint64_t first,
                               uint32_t n_win, uint32_t *hist, uint8_t *out, hipStream_t s);
+// the same for the n_sel services svc_map[0 .. n_sel) (device; nullptr: every
+// service in id order, n_sel = n_services): row i of hist [n_sel][..] and out
+// [n_sel][2^p] is service svc_map[i]; no other service's registers are read
+hipError_t launch_range_merge_sel(const uint8_t *hll, uint32_t n_windows, uint32_t n_services, uint32_t p,
+                                  uint64_t first, uint32_t n_win, const uint32_t *svc_map, uint32_t n_sel,
+                                  uint32_t *hist, uint8_t *out, hipStream_t s);
+// sa_window_overlap's pair stage (spanagg_overlap.hip): pair_hist [n_sel (n_sel
+// - 1) / 2][SA_HLL_HIST_BINS] (zeroed by the caller) = the value histogram of
+// max(regs[i], regs[j]) for every i < j of regs [n_sel][2^p], pair index i *
+// n_sel - i (i + 1) / 2 + (j - i - 1).  n_sel <= SA_OVERLAP_MAX_SERVICES.
+// variant: 0, the product's counting; 1 and 2: the laboratory build's
+// column-wise forms ("Service overlap over the window ring")
+hipError_t launch_overlap_pairs(const uint8_t *regs, uint32_t n_sel, uint32_t p, uint32_t *pair_hist, uint32_t variant,
+                                hipStream_t s);
 // launch_fold_errcnt for the n_win windows from `first` in one launch
 // (errcnt [n_windows][cap], cms [n_windows][slot_elems])
 hipError_t launch_range_fold(const unsigned long long *gkeys, unsigned long long *errcnt, uint64_t cap,

@@ -154,6 +154,24 @@ struct top_holder {
   }
 };
 
+struct overlap_holder {
+  sa_overlap_result r;
+  std::vector<uint32_t> services, hist, pair_hist;
+  std::vector<double> distinct, union_est, shared;
+  // the columns sized for the selection sel of an engine of precision p, and r pointing at them
+  __attribute__((visibility("hidden"))) void shape(uint64_t first, uint64_t last, const std::vector<uint32_t> &sel,
+                                                   uint32_t p) {
+    const size_t n = sel.size(), np = n * (n - 1) / 2;
+    services = sel;
+    hist.resize(n * SA_HLL_HIST_BINS), distinct.resize(n);
+    pair_hist.resize(np * SA_HLL_HIST_BINS), union_est.resize(np), shared.resize(np);
+    r.first_window = first, r.last_window = last, r.n_sel = (uint32_t)n, r.n_pairs = (uint32_t)np;
+    r.hll_p = p, r.pad = 0;
+    r.services = services.data(), r.hll_hist = hist.data(), r.distinct = distinct.data();
+    r.pair_hist = pair_hist.data(), r.union_est = union_est.data(), r.shared = shared.data();
+  }
+};
+
 struct sketch_holder {
   sa_sketch_result r;
   std::vector<uint8_t> hll;

@@ -1181,6 +1181,47 @@ int sa_group_window_top(sa_group *g, uint64_t first, uint64_t last, uint32_t k, 
   return SA_OK;
 }
 
+// Each member max-merges its own windows first..last (registers only), the
+// transport merges the members' arrays -- every service's rows, as
+// sa_group_window_range moves them -- and member 0's device gathers the
+// selected rows and takes the pairs.
+int sa_group_window_overlap(sa_group *g, uint64_t first, uint64_t last, const uint32_t *services, uint32_t n_sel,
+                            uint32_t flags, sa_overlap_result **out) {
+  if (!g || !out) return SA_EINVAL;
+  *out = nullptr;
+  if (flags) return gfail(g, SA_EINVAL, "window overlap: flags are reserved (0)");
+  std::vector<uint32_t> sel;
+  if (const char *bad = sa_grp::overlap_select(g->cfg.n_services, services, n_sel, &sel)) return gfail(g, SA_EINVAL, bad);
+  const uint32_t n = (uint32_t)g->eng.size();
+  for (uint32_t i = 0; i < n; ++i) {
+    if (int rc = ensure(g, g->dev[i], g->hll[i], g->hll_bytes)) return rc;
+    if (int rc = sa_grp::window_overlap_export_async(g->eng[i], first, last, static_cast<uint8_t *>(g->hll[i].p), g->st[i]))
+      return member_error(g, i, rc, "window overlap");
+  }
+  if (g->rccl) {
+    SG_NCCL(g, ncclGroupStart());
+    for (uint32_t i = 0; i < n; ++i)
+      SG_NCCL(g, ncclAllReduce(g->hll[i].p, g->hll[i].p, g->hll_bytes, ncclUint8, ncclMax, g->comm[i], g->st[i]));
+    SG_NCCL(g, ncclGroupEnd());
+  } else {
+    if (int rc = copy_reduce(g, g->hll, g->hll_bytes, true)) return rc;
+  }
+  const int rc = sa_grp::window_overlap_finish(g->eng[0], first, last, static_cast<const uint8_t *>(g->hll[0].p), sel,
+                                               g->st[0], out);
+  hipError_t st = hipSuccess;
+  for (uint32_t i = 1; i < n && st == hipSuccess; ++i) {  // (an all-reduce ends on every member's stream)
+    st = hipSetDevice(g->dev[i]);
+    if (st == hipSuccess) st = hipStreamSynchronize(g->st[i]);
+  }
+  if (rc) return member_error(g, 0, rc, "window overlap");
+  if (st != hipSuccess) {
+    sa_overlap_result_free(*out);
+    *out = nullptr;
+    return gfail(g, SA_EDEVICE, std::string("window overlap: ") + hipGetErrorString(st));
+  }
+  return SA_OK;
+}
+
 int sa_group_window_advance(sa_group *g, uint64_t new_base) {
   if (!g) return SA_EINVAL;
   for (uint32_t i = 0; i < g->eng.size(); ++i)

@@ -11,6 +11,8 @@
 //                        stored only when a caller wants them.  Over one
 //                        "window" it is the histogram of an already merged
 //                        array (the group, after its all-reduce).
+//                        With a service map it merges the selected services
+//                        only (sa_window_overlap; the pairs: spanagg_overlap.hip).
 //   range_cells_kernel   count-min cells summed over the windows (u64).
 //   range_query_kernel   point queries on the summed cells, one thread a key.
 //
@@ -58,17 +60,6 @@ constexpr uint32_t kRangeInFlight = SA_RANGE_IN_FLIGHT;
 constexpr uint32_t kCellsInFlight = 4;
 constexpr uint32_t kCellChunks = 16;  // the cell sum's window chunks (blockIdx.y)
 
-// max of four u8 lanes, each below 128 (an HLL register is at most 65 - p):
-// (a | 0x80) - b keeps bit 7 exactly where a >= b and borrows from no neighbour
-__device__ __forceinline__ uint32_t max_u8x4(uint32_t a, uint32_t b) {
-  const uint32_t ge = (((a | 0x80808080u) - b) >> 7) & 0x01010101u;
-  const uint32_t m = ge * 0xFFu;
-  return (a & m) | (b & ~m);
-}
-__device__ __forceinline__ uint4 max_u8x16(uint4 a, uint4 b) {
-  return uint4{max_u8x4(a.x, b.x), max_u8x4(a.y, b.y), max_u8x4(a.z, b.z), max_u8x4(a.w, b.w)};
-}
-
 // Workgroup b serves service b / wgs and strides the service's tiles of 64
 // threads; a thread owns 16 consecutive registers (tps = 2^log2tps threads a
 // service, 2^p = 16 tps).  The workgroup's four waves each walk a quarter of
@@ -76,20 +67,24 @@ __device__ __forceinline__ uint4 max_u8x16(uint4 a, uint4 b) {
 // two waves a CU if a tile were one wave's -- and their partial maxima meet
 // in LDS; wave 0 stores and counts.  regs: [win_mask + 1][n_services][2^p].
 // hist (nullptr: none) [n_services][64] must be zero; out (nullptr: none)
-// [n_services][2^p].
+// [n_services][2^p].  svc_map (nullptr: every service, in id order): row b /
+// wgs of hist and out is service svc_map[b / wgs] of the ring -- the selected
+// services of sa_window_overlap, in the caller's order; the others are not read.
 __global__ __launch_bounds__(kRangeBlock) void range_merge_kernel(const uint4 *regs, uint64_t slot16, uint32_t win_mask,
                                                                   uint64_t first, uint32_t n_win, uint32_t log2tps,
-                                                                  uint32_t wgs, uint32_t *hist, uint4 *out) {
+                                                                  uint32_t wgs, const uint32_t *svc_map, uint32_t *hist,
+                                                                  uint4 *out) {
   __shared__ uint32_t h[kRangeBins];  // wave 0's histogram
   __shared__ uint4 part[kRangeWaves - 1][64];
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   if (threadIdx.x < kRangeBins) h[threadIdx.x] = 0;  // (ordered before the first count by the loop's barrier)
   const uint32_t svc = blockIdx.x / wgs, wg = blockIdx.x % wgs, tps = 1u << log2tps;
+  const uint32_t src = svc_map ? svc_map[svc] : svc;  // the ring's row; svc: the output's
   const uint32_t per = (n_win + kRangeWaves - 1) / kRangeWaves;
   const uint32_t k0 = min(n_win, wave * per), k1 = min(n_win, k0 + per);
   for (uint32_t t = wg; t < (tps + 63) / 64; t += wgs) {  // (the same trips for every thread)
     const uint32_t c = t * 64 + lane;
-    const uint64_t at = ((uint64_t)svc << log2tps) + c;
+    const uint64_t at = ((uint64_t)src << log2tps) + c;
     uint4 acc{0, 0, 0, 0};
     if (c < tps) {
       uint32_t k = k0;
@@ -107,7 +102,7 @@ __global__ __launch_bounds__(kRangeBlock) void range_merge_kernel(const uint4 *r
     if (wave == 0 && c < tps) {
 #pragma unroll
       for (uint32_t w = 0; w < kRangeWaves - 1; ++w) acc = max_u8x16(acc, part[w][lane]);
-      if (out) out[at] = acc;
+      if (out) out[((uint64_t)svc << log2tps) + c] = acc;
       if (hist) {
         const uint32_t w4[4] = {acc.x, acc.y, acc.z, acc.w};
 #pragma unroll
@@ -743,12 +738,18 @@ hipError_t launch_series_row0(const unsigned long long *cms, uint64_t slot_elems
 
 hipError_t launch_range_merge(const uint8_t *hll, uint32_t n_windows, uint32_t n_services, uint32_t p, uint64_t first,
                               uint32_t n_win, uint32_t *hist, uint8_t *out, hipStream_t s) {
+  return launch_range_merge_sel(hll, n_windows, n_services, p, first, n_win, nullptr, n_services, hist, out, s);
+}
+
+hipError_t launch_range_merge_sel(const uint8_t *hll, uint32_t n_windows, uint32_t n_services, uint32_t p,
+                                  uint64_t first, uint32_t n_win, const uint32_t *svc_map, uint32_t n_sel,
+                                  uint32_t *hist, uint8_t *out, hipStream_t s) {
   const uint32_t log2tps = p - 4, tiles = ((1u << log2tps) + 63) / 64;
   // workgroups a service: its tiles of 64 threads, fewer once the grid passes ~4,096 (they stride)
-  const uint32_t wgs = std::max(1u, std::min(tiles, 4096u / std::min(n_services, 4096u)));
-  hipLaunchKernelGGL(range_merge_kernel, dim3(n_services * wgs), dim3(kRangeBlock), 0, s,
+  const uint32_t wgs = std::max(1u, std::min(tiles, 4096u / std::min(n_sel, 4096u)));
+  hipLaunchKernelGGL(range_merge_kernel, dim3(n_sel * wgs), dim3(kRangeBlock), 0, s,
                      reinterpret_cast<const uint4 *>(hll), (uint64_t)n_services << log2tps, n_windows - 1, first, n_win,
-                     log2tps, wgs, hist, reinterpret_cast<uint4 *>(out));
+                     log2tps, wgs, svc_map, hist, reinterpret_cast<uint4 *>(out));
   return hipGetLastError();
 }
 

@@ -108,6 +108,17 @@ class sa_top_result(C.Structure):
     ]
 
 
+SA_OVERLAP_MAX_SERVICES = OVERLAP_MAX_SERVICES = 64
+
+
+class sa_overlap_result(C.Structure):
+    _fields_ = [
+        ("first_window", C.c_uint64), ("last_window", C.c_uint64), ("n_sel", C.c_uint32), ("n_pairs", C.c_uint32),
+        ("hll_p", C.c_uint32), ("pad", C.c_uint32), ("services", u32p), ("hll_hist", u32p), ("distinct", f64p),
+        ("pair_hist", u32p), ("union_est", f64p), ("shared", f64p),
+    ]
+
+
 class sa_stats(C.Structure):
     _fields_ = [
         ("spans", C.c_uint64), ("zero_key", C.c_uint64), ("invalid_service", C.c_uint64),
@@ -175,6 +186,11 @@ SIGNATURES = [
     ("sa_group_window_top", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32,
                                       C.POINTER(C.POINTER(sa_top_result))]),
     ("sa_top_result_free", None, [C.POINTER(sa_top_result)]),
+    ("sa_window_overlap", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, u32p, C.c_uint32, C.c_uint32,
+                                    C.POINTER(C.POINTER(sa_overlap_result))]),
+    ("sa_group_window_overlap", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, u32p, C.c_uint32, C.c_uint32,
+                                          C.POINTER(C.POINTER(sa_overlap_result))]),
+    ("sa_overlap_result_free", None, [C.POINTER(sa_overlap_result)]),
     ("sa_hll_estimate_hist", C.c_double, [u32p, C.c_uint32]),
     ("sa_get_stats", C.c_int, [C.c_void_p, C.POINTER(sa_stats)]),
     ("sa_bind_ids", C.c_int, [C.c_void_p, u64p, u64p, C.c_uint64]),

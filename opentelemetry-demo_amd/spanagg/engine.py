@@ -195,6 +195,41 @@ class TopResult:
         return [(int(k), int(e)) for k, e in zip(self.keys, self.errors)]
 
 
+@dataclass
+class OverlapResult:
+    """sa_overlap_result: for every pair of the selected services the traces
+    both saw over windows first..last, by inclusion-exclusion on the merged
+    HyperLogLog registers (the register-wise maximum of two services' arrays is
+    the sketch of the union of their trace sets).  Each estimate carries about
+    1.04 / sqrt(2^p) relative error of its own size: `shared` means something
+    only where it is not small against union x 1.04 / sqrt(2^p)."""
+    first: int
+    last: int
+    services: np.ndarray          # [n] u32 service ids, in the caller's order
+    hist: np.ndarray              # [n, 64] u32: window_range(first, last).hist[services]
+    distinct: np.ndarray          # [n] f64: window_range(first, last).distinct[services]
+    pair_hist: np.ndarray         # [n_pairs, 64] u32: histogram of max(regs[i], regs[j]), row pair_index(i, j)
+    union: np.ndarray             # [n, n] f64, symmetric, diagonal = distinct
+    shared: np.ndarray            # [n, n] f64, symmetric, diagonal = distinct
+    p: int = 14
+
+    def pair_index(self, i: int, j: int) -> int:
+        """Row of pair_hist for positions i != j of `services`."""
+        n = len(self.services)
+        i, j = (i, j) if i < j else (j, i)
+        if not 0 <= i < j < n:
+            raise IndexError("pair_index: two different positions of the selection")
+        return i * n - i * (i + 1) // 2 + (j - i - 1)
+
+    def strongest(self, k: int = 10):
+        """The k pairs with the largest `shared`, ties by (i, j):
+        [(services[i], services[j], shared)] with i < j."""
+        n = len(self.services)
+        pairs = [(i, j) for i in range(n) for j in range(i + 1, n)]
+        pairs.sort(key=lambda ij: (-float(self.shared[ij]), ij))
+        return [(int(self.services[i]), int(self.services[j]), float(self.shared[i, j])) for i, j in pairs[:k]]
+
+
 def hll_estimate(regs: np.ndarray, p: int) -> float:
     lib = _lib.load()
     r = np.ascontiguousarray(regs, dtype=np.uint8)
@@ -305,6 +340,31 @@ def _window_top(obj, fn, what, first, last, k, min_count) -> TopResult:
                          int(r.n_resident), int(r.n_matched), int(r.error_spans))
     finally:
         obj.lib.sa_top_result_free(out)
+
+
+def _window_overlap(obj, fn, what, first, last, services) -> OverlapResult:
+    """sa_window_overlap / sa_group_window_overlap -> OverlapResult (copies), freeing the library's result."""
+    sv = None if services is None else np.ascontiguousarray(services, dtype=np.uint32).reshape(-1)
+    out = C.POINTER(_lib.sa_overlap_result)()
+    obj._check(fn(obj._h, int(first), int(last), None if sv is None else sv.ctypes.data_as(_lib.u32p),
+                  0 if sv is None else len(sv), 0, C.byref(out)), what)
+    try:
+        r = out.contents
+        n, npairs, B = int(r.n_sel), int(r.n_pairs), _lib.SA_HLL_HIST_BINS
+        distinct = np.ctypeslib.as_array(r.distinct, shape=(n,)).copy()
+        union, shared = np.diag(distinct), np.diag(distinct)
+        if npairs:
+            iu = np.triu_indices(n, 1)  # (row-major i < j: the pair index's order)
+            for m, col in ((union, r.union_est), (shared, r.shared)):
+                m[iu] = np.ctypeslib.as_array(col, shape=(npairs,))
+                m.T[iu] = m[iu]
+        return OverlapResult(
+            int(r.first_window), int(r.last_window), np.ctypeslib.as_array(r.services, shape=(n,)).copy(),
+            np.ctypeslib.as_array(r.hll_hist, shape=(n, B)).copy(), distinct,
+            np.ctypeslib.as_array(r.pair_hist, shape=(npairs, B)).copy() if npairs else np.zeros((0, B), np.uint32),
+            union, shared, int(r.hll_p))
+    finally:
+        obj.lib.sa_overlap_result_free(out)
 
 
 def _ptr(x) -> int:
@@ -497,6 +557,14 @@ class Engine:
         >= min_count -- scanned, selected and sorted on the device."""
         return _window_top(self, self.lib.sa_window_top, "sa_window_top", first, last, k, min_count)
 
+    def window_overlap(self, first: int, last: int, services=None) -> OverlapResult:
+        """sa_window_overlap: the traces every pair of `services` (ids, at most
+        OVERLAP_MAX_SERVICES; None: every service of an engine with no more
+        than that) shares over windows first..last -- registers max-merged
+        per service, then the pairwise maxima and their histograms, on the
+        device."""
+        return _window_overlap(self, self.lib.sa_window_overlap, "sa_window_overlap", first, last, services)
+
     def flush_exp(self, allow_drops: bool = False) -> ExpoResult:
         out = C.POINTER(_lib.sa_exp_result)()
         rc = self.lib.sa_flush_exp(self._h, C.byref(out))
@@ -674,6 +742,11 @@ class Group:
         """sa_group_window_top: Engine.window_top over the members' merge
         (n_resident and n_matched summed over the members)."""
         return _window_top(self, self.lib.sa_group_window_top, "sa_group_window_top", first, last, k, min_count)
+
+    def window_overlap(self, first: int, last: int, services=None) -> OverlapResult:
+        """sa_group_window_overlap: Engine.window_overlap over the members' merge."""
+        return _window_overlap(self, self.lib.sa_group_window_overlap, "sa_group_window_overlap", first, last,
+                               services)
 
     def window_advance(self, new_base: int):
         self._check(self.lib.sa_group_window_advance(self._h, int(new_base)), "sa_group_window_advance")
