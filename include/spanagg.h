@@ -21,6 +21,7 @@
  *   (new) every trailing span of a window series    sa_window_series (one pass over the ring)
  *   (new) heavy hitters over a span of windows      sa_window_top (key table scanned on the device)
  *   (new) traces shared by pairs of services        sa_window_overlap (pairwise register maxima on the device)
+ *   (new) series whose ERROR rate changed most      sa_window_movers (key table against two ranges' cells on the device)
  *
  * Boundary rules (mirroring the connector's contracts):
  *  - Ownership: batches are borrowed for the duration of the call (page-locked
@@ -412,6 +413,59 @@ int sa_window_top(sa_engine *e, uint64_t first, uint64_t last, uint32_t k, uint6
                   uint32_t flags, sa_top_result **out);
 void sa_top_result_free(sa_top_result *r);
 
+/* ---- movers over the window ring ----
+ * "Which series fail more now than they did before": the key table is the
+ * candidate list, as for sa_window_top, and every candidate is held against
+ * the summed cells of two ranges -- a baseline and a current one -- in one
+ * pass over the table. */
+#define SA_MOVERS_FALL 1u   /* rank by the fall instead of the rise */
+typedef struct {
+    uint64_t base_first, base_last, cur_first, cur_last;   /* inclusive */
+    uint32_t k, n;                  /* asked for; returned (n <= k) */
+    uint32_t flags, pad;
+    uint64_t n_resident;            /* candidates, as sa_top_result */
+    uint64_t n_matched;             /* candidates with score >= max(min_score, 1) */
+    uint64_t error_spans_base, error_spans_cur;  /* row 0 of each range's summed cells, exact */
+    const uint64_t *key_hash;       /* [n] */
+    const int64_t  *score;          /* [n] */
+    const uint64_t *baseline;       /* [n] */
+    const uint64_t *current;        /* [n] */
+} sa_movers_result;
+
+/* Candidates: exactly sa_window_top's -- every non-zero key resident in the
+ * key table when the call runs, on every ingest path; on an SA_OPT_DENSE_IDS
+ * engine the bound hash, unbound indices not being candidates.  Key 0 and
+ * series that got no slot are never candidates.  A reclaim empties the
+ * candidates and keeps the cells.
+ * Estimates: baseline[i] is bit for bit what sa_window_range(e, base_first,
+ * base_last, &key_hash[i], 1, 0, ..) returns in errors[0], current[i] the same
+ * for cur_first..cur_last.  Both ranges' windows are folded before any cell is
+ * summed.
+ * Score: with nb = base_last - base_first + 1 and nc = cur_last - cur_first + 1,
+ *   score = current * nb - baseline * nc
+ * as a signed 64-bit integer, negated under SA_MOVERS_FALL: the difference of
+ * the per-window means, cross-multiplied so that no division or rounding
+ * enters (score / (nb * nc) is ERROR spans per window).  Exact while each
+ * estimate is below 2^50 -- the largest ring has 4,096 windows, so the
+ * products stay below 2^62; beyond that the score is unspecified.
+ * Order: the n_matched candidates with score >= max(min_score, 1), sorted by
+ * score descending, then key_hash ascending (a total order); the first n =
+ * min(k, n_matched) of them are returned, in that order.  min_score >= 2^63
+ * matches nothing.
+ * Ranges: independent -- each must be resident; they may overlap or be equal.
+ * Equal ranges give n_matched == 0 with both counters filled and equal.
+ * Ordering and waiting as sa_window_top: joins every launch in flight, runs on
+ * the engine stream, waits once, clears nothing (two calls give equal bits).
+ * SA_EINVAL for a null `out`, k == 0, k > SA_TOP_MAX_K, flag bits other than
+ * SA_MOVERS_FALL; SA_ERANGE for either range as sa_window_range; SA_ENOMEM
+ * when the device scratch (sa_window_top's, a second cell array and the rows'
+ * estimates, allocated by the first call) or the result cannot be allocated.
+ * The engine stays usable after any error.  Free with sa_movers_result_free. */
+int sa_window_movers(sa_engine *e, uint64_t base_first, uint64_t base_last, uint64_t cur_first,
+                     uint64_t cur_last, uint32_t k, uint64_t min_score, uint32_t flags,
+                     sa_movers_result **out);
+void sa_movers_result_free(sa_movers_result *r);
+
 /* ---- service overlap over the window ring ----
  * "How many traces do two services share over these windows": every service's
  * registers are filled from the same hash of the trace id, so the register-wise
@@ -561,6 +615,17 @@ int sa_group_window_range(sa_group *g, uint64_t first, uint64_t last, const uint
  * sa_group_get_stats does). */
 int sa_group_window_top(sa_group *g, uint64_t first, uint64_t last, uint32_t k, uint64_t min_count,
                         uint32_t flags, sa_top_result **out);
+/* sa_window_movers of a group: every member sums both ranges on its device,
+ * the transport sums both cell arrays across members and leaves the sums on
+ * every member, every member scans its own key table against the merged
+ * arrays (a score depends on the key and the merged cells only, so the
+ * group's first k are among the members' first k), and the host drops the
+ * repeats and cuts to k in the same order.  The rows and both error_spans_*
+ * equal those of one engine fed every span; n_resident and n_matched are
+ * summed over members, as in sa_group_window_top. */
+int sa_group_window_movers(sa_group *g, uint64_t base_first, uint64_t base_last, uint64_t cur_first,
+                           uint64_t cur_last, uint32_t k, uint64_t min_score, uint32_t flags,
+                           sa_movers_result **out);
 /* sa_window_overlap of a group: every member max-merges its own windows on
  * its device, the group's transport merges the members' registers (max, every
  * service's rows as for sa_group_window_range), and member 0's device gathers

@@ -11,6 +11,7 @@
 #include <new>
 #include <numeric>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "sa_engine.h"
@@ -313,6 +314,39 @@ int top_on(sa_engine *e, const unsigned long long *d_cells, uint32_t k, uint64_t
   return fail(e, SA_EDEVICE, std::string("window top: ") + hipGetErrorString(st));
 }
 
+// ---- movers (sa_window_movers; kernels in spanagg_range.hip) ----
+int movers_buffers(sa_engine *e) {
+  if (int rc = top_buffers(e)) return rc;  // (the candidates and the select's state: calls are serialised)
+  if (!e->movers.out)
+    if (int rc = dalloc(e, e->movers.out, 1, false, "window movers: estimate buffer hipMalloc failed")) return rc;
+  return SA_OK;
+}
+
+// On `s`, not waited for: e's key table scanned against d_base and d_cur
+// [d][w] (the sums of nb and nc windows), the first k matches selected and
+// sorted, the counters, the k rows and their estimates copied into *h.
+int movers_on(sa_engine *e, const unsigned long long *d_base, const unsigned long long *d_cur, uint64_t nb, uint64_t nc,
+              uint32_t k, uint64_t min_score, uint32_t flags, hipStream_t s, sa_grp::MoversHost *h) {
+  const sa_engine::Top &T = e->top;
+  sa::MoversOut *O = e->movers.out;
+  try {
+    h->top.rows.resize(k);
+    h->out.resize((size_t)k + 1);
+  } catch (const std::bad_alloc &) {
+    return fail(e, SA_ENOMEM, "window movers: the rows do not fit in host memory");
+  }
+  hipError_t st = sa::launch_movers(e->gkeys, e->cap, e->binned.kinv, d_base, d_cur, e->cfg.cms_d, e->cfg.cms_w,
+                                    64 - sa::log2u(e->cfg.cms_w), e->d_seeds, nb, nc, flags & SA_MOVERS_FALL ? 1u : 0u, k,
+                                    std::max<uint64_t>(min_score, 1), T.cand, T.ctl, O, s);
+  if (st == hipSuccess) st = hipMemcpyAsync(h->top.head, T.ctl, sizeof h->top.head, hipMemcpyDeviceToHost, s);
+  if (st == hipSuccess) st = hipMemcpyAsync(h->top.rows.data(), T.ctl->sel, (size_t)k * 16, hipMemcpyDeviceToHost, s);
+  // (MoversOut: the 16-byte head, then the rows)
+  if (st == hipSuccess) st = hipMemcpyAsync(h->out.data(), O, ((size_t)k + 1) * 16, hipMemcpyDeviceToHost, s);
+  if (st == hipSuccess) return SA_OK;
+  (void)hipStreamSynchronize(s);  // (a copy into h may be in flight)
+  return fail(e, SA_EDEVICE, std::string("window movers: ") + hipGetErrorString(st));
+}
+
 // ---- service overlap (sa_window_overlap; kernels in spanagg_range.hip and spanagg_overlap.hip) ----
 // The counting form of the pair kernel: the laboratory build reads
 // SPANAGG_OVERLAP (0, 1, 2) at every call, the product holds variant 0 alone.
@@ -490,30 +524,84 @@ int window_top_async(sa_engine *e, const uint64_t *d_cms, uint32_t k, uint64_t m
   return hop_back(e, s);
 }
 
+int window_movers_async(sa_engine *e, const uint64_t *d_base, const uint64_t *d_cur, uint64_t nb, uint64_t nc,
+                        uint32_t k, uint64_t min_score, uint32_t flags, hipStream_t s, MoversHost *out) {
+  if (!e || !d_base || !d_cur || !out) return SA_EINVAL;
+  if (int rc = set_dev(e)) return rc;
+  if (int rc = movers_buffers(e)) return rc;
+  // (the scratch is the engine's: after its own earlier use, before its next)
+  if (int rc = hop_to(e, s)) return rc;
+  if (int rc = movers_on(e, reinterpret_cast<const unsigned long long *>(d_base),
+                         reinterpret_cast<const unsigned long long *>(d_cur), nb, nc, k, min_score, flags, s, out))
+    return rc;
+  return hop_back(e, s);
+}
+
+namespace {
+// A row of a ranked answer: its key, what it is ranked by, and what travels
+// with it (sa_window_movers: the two estimates).
+struct Ranked {
+  uint64_t key, rank, a, b;
+  bool operator<(const Ranked &o) const { return std::tie(key, rank, a, b) < std::tie(o.key, o.rank, o.a, o.b); }
+  bool operator==(const Ranked &o) const { return std::tie(key, rank, a, b) == std::tie(o.key, o.rank, o.a, o.b); }
+};
+
+// The answer of n scans (each waited for; member j's first min(k, head[0])
+// rows, extra[j] the values that travel with them or nullptr): one member's
+// rows as they are, the device's order; several members' merged -- a series on
+// several members has the same row on each: once -- by (rank descending, key
+// ascending), cut to k.
+std::vector<Ranked> ranked_rows(uint32_t k, const TopHost *const *m, const ulonglong2 *const *extra, uint32_t n) {
+  std::vector<Ranked> all;
+  for (uint32_t j = 0; j < n; ++j) {
+    const size_t rows = (size_t)std::min<uint64_t>(k, m[j]->head[0]);
+    for (size_t i = 0; i < rows; ++i)
+      all.push_back(Ranked{m[j]->rows[i].y, m[j]->rows[i].x, extra[j] ? extra[j][i].x : 0, extra[j] ? extra[j][i].y : 0});
+  }
+  if (n == 1) return all;
+  std::sort(all.begin(), all.end());
+  all.erase(std::unique(all.begin(), all.end()), all.end());
+  std::sort(all.begin(), all.end(),
+            [](const Ranked &a, const Ranked &b) { return a.rank != b.rank ? a.rank > b.rank : a.key < b.key; });
+  if (all.size() > k) all.resize(k);
+  return all;
+}
+}  // namespace
+
 int top_result(uint64_t first, uint64_t last, uint32_t k, const TopHost *m, uint32_t n_members, sa_top_result **out) {
   try {
     std::unique_ptr<top_holder> h(new top_holder());
-    auto rows_of = [&](const TopHost &t) { return (size_t)std::min<uint64_t>(k, t.head[0]); };
-    if (n_members == 1) {  // the device's order, as it is
-      const size_t n = rows_of(m[0]);
-      h->shape(first, last, k, (uint32_t)n);
-      for (size_t i = 0; i < n; ++i) h->errors[i] = m[0].rows[i].x, h->keys[i] = m[0].rows[i].y;
-    } else {
-      // a series on several members has the same estimate on each: once
-      std::vector<std::pair<uint64_t, uint64_t>> all;  // (key, estimate)
-      for (uint32_t j = 0; j < n_members; ++j)
-        for (size_t i = 0; i < rows_of(m[j]); ++i) all.emplace_back(m[j].rows[i].y, m[j].rows[i].x);
-      std::sort(all.begin(), all.end());
-      all.erase(std::unique(all.begin(), all.end()), all.end());
-      std::sort(all.begin(), all.end(), [](const auto &a, const auto &b) {
-        return a.second != b.second ? a.second > b.second : a.first < b.first;
-      });
-      const size_t n = std::min<size_t>(k, all.size());
-      h->shape(first, last, k, (uint32_t)n);
-      for (size_t i = 0; i < n; ++i) h->keys[i] = all[i].first, h->errors[i] = all[i].second;
-    }
+    std::vector<const TopHost *> tops(n_members);
+    for (uint32_t j = 0; j < n_members; ++j) tops[j] = &m[j];
+    const std::vector<const ulonglong2 *> none(n_members, nullptr);
+    const std::vector<Ranked> rows = ranked_rows(k, tops.data(), none.data(), n_members);
+    h->shape(first, last, k, (uint32_t)rows.size());
+    for (size_t i = 0; i < rows.size(); ++i) h->keys[i] = rows[i].key, h->errors[i] = rows[i].rank;
     for (uint32_t j = 0; j < n_members; ++j) h->r.n_matched += m[j].head[0], h->r.n_resident += m[j].head[1];
     h->r.error_spans = m[0].head[3];  // (the merged cells are the same on every member)
+    *out = &h.release()->r;
+    return SA_OK;
+  } catch (const std::bad_alloc &) {
+    return SA_ENOMEM;
+  }
+}
+
+int movers_result(const uint64_t range[4], uint32_t k, uint32_t flags, const MoversHost *m, uint32_t n_members,
+                  sa_movers_result **out) {
+  try {
+    std::unique_ptr<movers_holder> h(new movers_holder());
+    std::vector<const TopHost *> tops(n_members);
+    std::vector<const ulonglong2 *> est(n_members);
+    for (uint32_t j = 0; j < n_members; ++j) tops[j] = &m[j].top, est[j] = m[j].out.data() + 1;
+    const std::vector<Ranked> rows = ranked_rows(k, tops.data(), est.data(), n_members);
+    h->shape(range, k, (uint32_t)rows.size(), flags);
+    for (size_t i = 0; i < rows.size(); ++i) {
+      h->keys[i] = rows[i].key, h->score[i] = (int64_t)rows[i].rank;  // (a match's score is >= 1)
+      h->baseline[i] = rows[i].a, h->current[i] = rows[i].b;
+    }
+    for (uint32_t j = 0; j < n_members; ++j) h->r.n_matched += m[j].top.head[0], h->r.n_resident += m[j].top.head[1];
+    // (the merged cells are the same on every member)
+    h->r.error_spans_base = m[0].out[0].x, h->r.error_spans_cur = m[0].top.head[3];
     *out = &h.release()->r;
     return SA_OK;
   } catch (const std::bad_alloc &) {
@@ -823,6 +911,35 @@ int sa_window_top(sa_engine *e, uint64_t first, uint64_t last, uint32_t k, uint6
 }
 
 void sa_top_result_free(sa_top_result *r) { delete reinterpret_cast<top_holder *>(r); }
+
+int sa_window_movers(sa_engine *e, uint64_t base_first, uint64_t base_last, uint64_t cur_first, uint64_t cur_last,
+                     uint32_t k, uint64_t min_score, uint32_t flags, sa_movers_result **out) {
+  if (!e || !out) return SA_EINVAL;
+  *out = nullptr;
+  if (k == 0 || k > SA_TOP_MAX_K) return fail(e, SA_EINVAL, "window movers: k outside 1..SA_TOP_MAX_K");
+  if (flags & ~SA_MOVERS_FALL) return fail(e, SA_EINVAL, "window movers: unknown flag bits");
+  if (int rc = range_args(e, base_first, base_last, nullptr, 0, 0)) return rc;
+  if (int rc = range_args(e, cur_first, cur_last, nullptr, 0, 0)) return rc;
+  if (int rc = begin_read(e)) return rc;
+  if (int rc = range_buffers(e, 0, false, true)) return rc;
+  sa_engine::Range &R = e->range;
+  if (!R.cells_base)
+    if (int rc = dalloc(e, R.cells_base, e->cms_slot_elems, false, "window movers: cell buffer hipMalloc failed")) return rc;
+  if (int rc = movers_buffers(e)) return rc;
+  if (int rc = range_merge_on(e, base_first, base_last, nullptr, nullptr, R.cells_base, e->stream)) return rc;
+  if (int rc = range_merge_on(e, cur_first, cur_last, nullptr, nullptr, R.cells, e->stream)) return rc;
+  sa_grp::MoversHost mh;
+  if (int rc = movers_on(e, R.cells_base, R.cells, base_last - base_first + 1, cur_last - cur_first + 1, k, min_score,
+                         flags, e->stream, &mh))
+    return rc;
+  SA_HIP(e, hipStreamSynchronize(e->stream));  // the call's one wait
+  const uint64_t range[4] = {base_first, base_last, cur_first, cur_last};
+  if (int rc = sa_grp::movers_result(range, k, flags, &mh, 1, out))
+    return fail(e, rc, "window movers: the result does not fit in host memory");
+  return SA_OK;
+}
+
+void sa_movers_result_free(sa_movers_result *r) { delete reinterpret_cast<movers_holder *>(r); }
 
 int sa_window_overlap(sa_engine *e, uint64_t first, uint64_t last, const uint32_t *services, uint32_t n_sel,
                       uint32_t flags, sa_overlap_result **out) {

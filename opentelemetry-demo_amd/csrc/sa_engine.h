@@ -190,11 +190,12 @@ struct sa_engine {
   size_t hll_slot_bytes = 0, cms_slot_elems = 0;
   // sa_window_range (allocated by its first call): the histogram
   // [n_services][SA_HLL_HIST_BINS], the merged registers (SA_RANGE_REGISTERS
-  // only), the summed cells, and the keys with their answers [2][key_cap]
+  // only), the summed cells, and the keys with their answers [2][key_cap];
+  // cells_base: a second [d][w], the baseline range's sum (sa_window_movers only)
   struct Range {
     uint32_t *hist = nullptr;
     uint8_t *regs = nullptr;
-    unsigned long long *cells = nullptr;
+    unsigned long long *cells = nullptr, *cells_base = nullptr;
     uint64_t *keys = nullptr;
     uint64_t key_cap = 0;
   } range;
@@ -215,6 +216,12 @@ struct sa_engine {
     ulonglong2 *cand = nullptr;
     sa::TopCtl *ctl = nullptr;
   } top;
+  // sa_window_movers (allocated by its first call) works in sa_window_top's
+  // scratch -- calls are serialised -- and leaves the baseline's error_spans
+  // and the rows' estimates here (sa::MoversOut, 64 KiB)
+  struct Movers {
+    sa::MoversOut *out = nullptr;
+  } movers;
   // sa_window_overlap (allocated by its first call, for min(n_services,
   // SA_OVERLAP_MAX_SERVICES) = cap services): the selected ids [cap], their
   // merged registers [cap][2^p] and histograms [cap][SA_HLL_HIST_BINS], and

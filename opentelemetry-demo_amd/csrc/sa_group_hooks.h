@@ -75,4 +75,23 @@ int window_top_async(sa_engine *e, const uint64_t *d_cms, uint32_t k, uint64_t m
 // n_matched summed.  SA_ENOMEM when the result cannot be allocated.
 int top_result(uint64_t first, uint64_t last, uint32_t k, const TopHost *members, uint32_t n_members,
                sa_top_result **out);
+// What one engine's movers scan leaves on the host: top as TopHost with the
+// score for the estimate (head[2] the largest score, head[3] the current
+// range's error_spans); out [k + 1] = {the baseline's error_spans, -}, then the
+// rows' (baseline, current) estimates in top.rows' order.
+struct MoversHost {
+  TopHost top;
+  std::vector<ulonglong2> out;
+};
+// sa_window_movers' device part for one member against the merged cells
+// d_base and d_cur [d][w] on its device (the sums of nb and nc windows), on
+// `s`, without the wait: fills *out (which must stay until `s` has been waited
+// for).  k, min_score and flags as sa_window_movers.
+int window_movers_async(sa_engine *e, const uint64_t *d_base, const uint64_t *d_cur, uint64_t nb, uint64_t nc,
+                        uint32_t k, uint64_t min_score, uint32_t flags, hipStream_t s, MoversHost *out);
+// The sa_movers_result of n_members scans (each waited for), merged as
+// top_result merges; range: base first, base last, current first, current
+// last.  SA_ENOMEM when the result cannot be allocated.
+int movers_result(const uint64_t range[4], uint32_t k, uint32_t flags, const MoversHost *members, uint32_t n_members,
+                  sa_movers_result **out);
 }  // namespace sa_grp

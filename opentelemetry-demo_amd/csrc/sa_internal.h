@@ -482,6 +482,32 @@ struct TopCtl {
 hipError_t launch_top(const unsigned long long *gkeys, uint64_t cap, uint64_t kinv, const unsigned long long *cells,
                       uint32_t d, uint32_t w, uint32_t shift, const uint64_t *seeds, uint32_t k,
                       unsigned long long min_count, ulonglong2 *cand, TopCtl *T, hipStream_t s);
+// movers between two ranges' summed cells (sa_window_movers; DESIGN.md section
+// 4, "Movers between two ranges").  kMoversCellsLds: the scan stages both
+// arrays in LDS while together they fit this size -- 128 KiB, two default
+// sketches, one workgroup in a CU's 160 KiB -- and reads larger ones through
+// global memory.
+// (SA_MOVERS_CELLS_LDS: for A/B builds -- DESIGN.md has the measurement)
+#ifndef SA_MOVERS_CELLS_LDS
+#define SA_MOVERS_CELLS_LDS 131072
+#endif
+constexpr uint32_t kMoversCellsLds = SA_MOVERS_CELLS_LDS;
+// What the call leaves beside TopCtl: the baseline range's row-0 sum and the
+// selected rows' (baseline, current) estimates, in T->sel's order.
+struct MoversOut {
+  unsigned long long error_spans_base, pad;
+  ulonglong2 est[kTopSel];
+};
+// The whole query on `s`: gkeys [cap] scanned against base and cur [d][w] with
+// score = cur's estimate * nb - base's * nc (negated when fall != 0) into cand
+// [cap], then T->sel[0 .. min(k, T->n_matched)) = the first k of the keys with
+// score >= min_score as (score, key), by (score descending, key ascending),
+// and O->est their estimates.  T->error_spans is cur's row-0 sum, T->max_est
+// the largest score.  k <= kTopSel, 1 <= min_score.
+hipError_t launch_movers(const unsigned long long *gkeys, uint64_t cap, uint64_t kinv, const unsigned long long *base,
+                         const unsigned long long *cur, uint32_t d, uint32_t w, uint32_t shift, const uint64_t *seeds,
+                         uint64_t nb, uint64_t nc, uint32_t fall, uint32_t k, unsigned long long min_score,
+                         ulonglong2 *cand, TopCtl *T, MoversOut *O, hipStream_t s);
 // sorted union of series ids on the device (spanagg_union.hip): out = the
 // distinct non-zero ids of in[0..n) ascending, *d_total (device u32) their
 // count; scratch >= key_union_scratch_bytes(n); big_scratch / big_bytes: a

@@ -154,6 +154,20 @@ struct top_holder {
   }
 };
 
+struct movers_holder {
+  sa_movers_result r;
+  std::vector<uint64_t> keys, baseline, current;
+  std::vector<int64_t> score;
+  // the columns sized for n rows, and r pointing at them; range: base first, base last, current first, current last
+  __attribute__((visibility("hidden"))) void shape(const uint64_t range[4], uint32_t k, uint32_t n, uint32_t flags) {
+    keys.resize(n), score.resize(n), baseline.resize(n), current.resize(n);
+    r.base_first = range[0], r.base_last = range[1], r.cur_first = range[2], r.cur_last = range[3];
+    r.k = k, r.n = n, r.flags = flags, r.pad = 0;
+    r.n_resident = r.n_matched = r.error_spans_base = r.error_spans_cur = 0;
+    r.key_hash = keys.data(), r.score = score.data(), r.baseline = baseline.data(), r.current = current.data();
+  }
+};
+
 struct overlap_holder {
   sa_overlap_result r;
   std::vector<uint32_t> services, hist, pair_hist;

@@ -14,6 +14,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <initializer_list>
 #include <map>
 #include <memory>
 #include <cstdlib>
@@ -311,6 +312,7 @@ struct sa_group {
   bool rccl = false;
   std::vector<ncclComm_t> comm;
   std::vector<Buf> keys, gath, uni, rows, hll, cms;
+  std::vector<Buf> cms_base;  // sa_group_window_movers: the baseline range's cells beside cms (the current range's)
   std::vector<Buf> srt, ucnt;  // device key union (sa::key_union): its scratch and the distinct count
   std::vector<uint64_t *> big;  // key_union's scratch for oversized buckets (per member)
   std::vector<size_t> big_bytes;
@@ -533,6 +535,7 @@ int sa_group_create(const sa_config *cfg, const int32_t *devices, uint32_t n, sa
   g->rows.resize(n);
   g->hll.resize(n);
   g->cms.resize(n);
+  g->cms_base.resize(n);
   g->dropped_seen.assign(n, 0);
   g->pcnt.resize(2 * n);
   g->hcol.resize(n);
@@ -584,7 +587,7 @@ void sa_group_destroy(sa_group *g) {
       (void)hipStreamSynchronize(g->st[i]);
       (void)hipStreamDestroy(g->st[i]);
     }
-    for (std::vector<Buf> *v : {&g->keys, &g->gath, &g->uni, &g->rows, &g->hll, &g->cms, &g->srt, &g->ucnt})
+    for (std::vector<Buf> *v : {&g->keys, &g->gath, &g->uni, &g->rows, &g->hll, &g->cms, &g->cms_base, &g->srt, &g->ucnt})
       if (i < v->size() && (*v)[i].p) (void)hipFree((*v)[i].p);
     if (i < g->big.size() && g->big[i]) (void)hipFree(g->big[i]);
     for (size_t k = 0; k < 2; ++k)
@@ -1127,11 +1130,49 @@ int sa_group_window_range(sa_group *g, uint64_t first, uint64_t last, const uint
   return SA_OK;
 }
 
+// The members' cell arrays of every `which` (on their streams) summed, the sums
+// left on every member's device before its stream goes on: RCCL's all-reduce
+// leaves them there; the copy transport copies member 0's sums back.
+static int sum_cells_everywhere(sa_group *g, std::initializer_list<std::vector<Buf> *> which) {
+  const uint32_t n = (uint32_t)g->eng.size();
+  if (g->rccl) {
+    SG_NCCL(g, ncclGroupStart());
+    for (std::vector<Buf> *b : which)
+      for (uint32_t i = 0; i < n; ++i)
+        SG_NCCL(g, ncclAllReduce((*b)[i].p, (*b)[i].p, g->cms_elems, ncclUint64, ncclSum, g->comm[i], g->st[i]));
+    SG_NCCL(g, ncclGroupEnd());
+  } else if (n > 1) {
+    for (std::vector<Buf> *b : which) {
+      if (int rc = copy_reduce(g, *b, g->cms_elems, false)) return rc;  // (the members' streams are drained)
+      SG_HIP(g, hipSetDevice(g->dev[0]));
+      for (uint32_t i = 1; i < n; ++i) {
+        if (g->dev[i] == g->dev[0])
+          SG_HIP(g, hipMemcpyAsync((*b)[i].p, (*b)[0].p, g->cms_elems * 8, hipMemcpyDeviceToDevice, g->st[0]));
+        else
+          SG_HIP(g, hipMemcpyPeerAsync((*b)[i].p, g->dev[i], (*b)[0].p, g->dev[0], g->cms_elems * 8, g->st[0]));
+      }
+    }
+    SG_HIP(g, hipStreamSynchronize(g->st[0]));  // the sums are on every member before its scan starts
+  }
+  return SA_OK;
+}
+
+// Waits for every member's stream (also after a failure: copies into host
+// results may be in flight); the first error met.
+static hipError_t wait_members(sa_group *g) {
+  hipError_t st = hipSuccess;
+  for (uint32_t i = 0; i < g->eng.size(); ++i) {
+    hipError_t a = hipSetDevice(g->dev[i]);
+    if (a == hipSuccess) a = hipStreamSynchronize(g->st[i]);
+    if (st == hipSuccess) st = a;
+  }
+  return st;
+}
+
 // The members' cells merged as for sa_group_window_range and left on every
-// member's device (RCCL's all-reduce leaves them there; the copy transport
-// copies member 0's sum back), then every member's scan and select against
-// them over its own key table, one wait per member, and the host's merge of
-// the members' rows.
+// member's device, then every member's scan and select against them over its
+// own key table, one wait per member, and the host's merge of the members'
+// rows.
 int sa_group_window_top(sa_group *g, uint64_t first, uint64_t last, uint32_t k, uint64_t min_count, uint32_t flags,
                         sa_top_result **out) {
   if (!g || !out) return SA_EINVAL;
@@ -1145,22 +1186,7 @@ int sa_group_window_top(sa_group *g, uint64_t first, uint64_t last, uint32_t k, 
                                                    g->st[i]))
       return member_error(g, i, rc, "window top");
   }
-  if (g->rccl) {
-    SG_NCCL(g, ncclGroupStart());
-    for (uint32_t i = 0; i < n; ++i)
-      SG_NCCL(g, ncclAllReduce(g->cms[i].p, g->cms[i].p, g->cms_elems, ncclUint64, ncclSum, g->comm[i], g->st[i]));
-    SG_NCCL(g, ncclGroupEnd());
-  } else if (n > 1) {
-    if (int rc = copy_reduce(g, g->cms, g->cms_elems, false)) return rc;  // (the members' streams are drained)
-    SG_HIP(g, hipSetDevice(g->dev[0]));
-    for (uint32_t i = 1; i < n; ++i) {
-      if (g->dev[i] == g->dev[0])
-        SG_HIP(g, hipMemcpyAsync(g->cms[i].p, g->cms[0].p, g->cms_elems * 8, hipMemcpyDeviceToDevice, g->st[0]));
-      else
-        SG_HIP(g, hipMemcpyPeerAsync(g->cms[i].p, g->dev[i], g->cms[0].p, g->dev[0], g->cms_elems * 8, g->st[0]));
-    }
-    SG_HIP(g, hipStreamSynchronize(g->st[0]));  // the sum is on every member before its scan starts
-  }
+  if (int rc = sum_cells_everywhere(g, {&g->cms})) return rc;
   std::vector<sa_grp::TopHost> th(n);
   int rc = SA_OK;
   uint32_t started = 0;
@@ -1168,16 +1194,49 @@ int sa_group_window_top(sa_group *g, uint64_t first, uint64_t last, uint32_t k, 
     rc = sa_grp::window_top_async(g->eng[started], static_cast<const uint64_t *>(g->cms[started].p), k, min_count,
                                   g->st[started], &th[started]);
   const uint32_t failed = started - 1;  // (when rc != SA_OK)
-  hipError_t st = hipSuccess;
-  for (uint32_t i = 0; i < n; ++i) {  // (also after a failure: copies into th may be in flight)
-    hipError_t a = hipSetDevice(g->dev[i]);
-    if (a == hipSuccess) a = hipStreamSynchronize(g->st[i]);
-    if (st == hipSuccess) st = a;
-  }
+  const hipError_t st = wait_members(g);
   if (rc) return member_error(g, failed, rc, "window top");
   if (st != hipSuccess) return gfail(g, SA_EDEVICE, std::string("window top: ") + hipGetErrorString(st));
   if (int rc2 = sa_grp::top_result(first, last, k, th.data(), n, out))
     return gfail(g, rc2, "window top: the result does not fit in host memory");
+  return SA_OK;
+}
+
+// As sa_group_window_top with two cell arrays: every member sums the baseline
+// range into cms_base and the current range into cms, both are merged and left
+// on every member, and every member scans its table against the pair.
+int sa_group_window_movers(sa_group *g, uint64_t base_first, uint64_t base_last, uint64_t cur_first, uint64_t cur_last,
+                           uint32_t k, uint64_t min_score, uint32_t flags, sa_movers_result **out) {
+  if (!g || !out) return SA_EINVAL;
+  *out = nullptr;
+  if (k == 0 || k > SA_TOP_MAX_K) return gfail(g, SA_EINVAL, "window movers: k outside 1..SA_TOP_MAX_K");
+  if (flags & ~SA_MOVERS_FALL) return gfail(g, SA_EINVAL, "window movers: unknown flag bits");
+  const uint32_t n = (uint32_t)g->eng.size();
+  for (uint32_t i = 0; i < n; ++i) {
+    if (int rc = ensure(g, g->dev[i], g->cms_base[i], g->cms_elems * 8)) return rc;
+    if (int rc = ensure(g, g->dev[i], g->cms[i], g->cms_elems * 8)) return rc;
+    if (int rc = sa_grp::window_range_export_async(g->eng[i], base_first, base_last, nullptr,
+                                                   static_cast<uint64_t *>(g->cms_base[i].p), g->st[i]))
+      return member_error(g, i, rc, "window movers");
+    if (int rc = sa_grp::window_range_export_async(g->eng[i], cur_first, cur_last, nullptr,
+                                                   static_cast<uint64_t *>(g->cms[i].p), g->st[i]))
+      return member_error(g, i, rc, "window movers");
+  }
+  if (int rc = sum_cells_everywhere(g, {&g->cms_base, &g->cms})) return rc;
+  std::vector<sa_grp::MoversHost> mh(n);
+  int rc = SA_OK;
+  uint32_t started = 0;
+  for (; started < n && rc == SA_OK; ++started)
+    rc = sa_grp::window_movers_async(g->eng[started], static_cast<const uint64_t *>(g->cms_base[started].p),
+                                     static_cast<const uint64_t *>(g->cms[started].p), base_last - base_first + 1,
+                                     cur_last - cur_first + 1, k, min_score, flags, g->st[started], &mh[started]);
+  const uint32_t failed = started - 1;  // (when rc != SA_OK)
+  const hipError_t st = wait_members(g);
+  if (rc) return member_error(g, failed, rc, "window movers");
+  if (st != hipSuccess) return gfail(g, SA_EDEVICE, std::string("window movers: ") + hipGetErrorString(st));
+  const uint64_t range[4] = {base_first, base_last, cur_first, cur_last};
+  if (int rc2 = sa_grp::movers_result(range, k, flags, mh.data(), n, out))
+    return gfail(g, rc2, "window movers: the result does not fit in host memory");
   return SA_OK;
 }
 

@@ -35,6 +35,14 @@
 //   top_gather_kernel    the selected pairs and the threshold's class.
 //   top_sort_kernel      their order, in one workgroup's LDS.
 //
+// and for sa_window_movers / sa_group_window_movers, the series whose ERROR
+// rate changed most between two ranges, with the same select and sort:
+//
+//   movers_scan_kernel   the key table against both ranges' cells: (score,
+//                        key) of every match, the resident keys, the largest score.
+//   movers_rows_kernel   the selected keys' estimates in both ranges, and the
+//                        baseline's error_spans.
+//
 // Every result is an integer maximum or an integer sum, so the order of the
 // atomics does not show: two calls, and one engine against a group, give the
 // same bits.
@@ -405,6 +413,7 @@ constexpr uint32_t kTopScanBlock = 1024;  // 16 waves: two workgroups of 64 KiB 
 constexpr uint32_t kTopBlock = 256;       // the select's digit and gather kernels
 constexpr uint32_t kTopSortBlock = 1024;
 static_assert(kTopSel == SA_TOP_MAX_K, "the sort holds the largest k");
+static_assert(kMoversCellsLds <= 160 * 1024, "a workgroup's LDS");
 
 // A candidate is the pair (estimate, key), ordered by estimate descending then
 // key ascending: as a 128-bit number (estimate, ~key) the largest comes first.
@@ -633,11 +642,136 @@ __global__ __launch_bounds__(kTopSortBlock) void top_sort_kernel(TopCtl *T) {
   for (uint32_t i = threadIdx.x; i < want; i += kTopSortBlock) T->sel[i] = top_sel[i];
 }
 
+// ---- movers (sa_window_movers): the key table scanned against two ranges'
+// summed cells at once, ranked by the change; the select and the sort are the
+// heavy hitters' ----
+// The key's estimates in base and cur [d][w]: its d columns are computed once
+// and read in both (range_query_kernel's arithmetic, twice).
+__device__ __forceinline__ void movers_estimates(const unsigned long long *base, const unsigned long long *cur,
+                                                 uint32_t d, uint32_t w, uint32_t shift, const uint64_t (&sd)[8],
+                                                 uint64_t key, unsigned long long &eb, unsigned long long &ec) {
+  eb = ~0ULL, ec = ~0ULL;
+#pragma unroll
+  for (uint32_t r = 0; r < 8; ++r) {  // (cms_d <= 8)
+    if (r < d) {
+      const uint64_t at = (uint64_t)r * w + (splitmix64(key ^ sd[r]) >> shift);  // col < w: shift = 64 - log2 w, w >= 2
+      const unsigned long long vb = base[at], vc = cur[at];
+      eb = vb < eb ? vb : eb;
+      ec = vc < ec ? vc : ec;
+    }
+  }
+}
+
+// top_scan_kernel over two arrays: a slot's key recovered the same way, its
+// estimates eb and ec taken from base and cur -- both staged in LDS (LDS = 1:
+// 2 * d * w * 8 <= kMoversCellsLds dynamic bytes, base first) or both read
+// through global memory -- and score = ec * nb - eb * nc as a signed number,
+// negated when `fall`.  Keys with score >= min_score (>= 1, so the score
+// orders as an unsigned number) leave as (score, key) into cand [cap]; T
+// counts the resident keys, the matches and the largest score (max_est).
+template <int LDS>
+__global__ __launch_bounds__(kTopScanBlock) void movers_scan_kernel(const unsigned long long *gkeys, uint64_t cap,
+                                                                    uint64_t kinv, const unsigned long long *base,
+                                                                    const unsigned long long *cur, uint32_t d,
+                                                                    uint32_t w, uint32_t shift, const uint64_t *seeds,
+                                                                    unsigned long long nb, unsigned long long nc,
+                                                                    uint32_t fall, unsigned long long min_score,
+                                                                    ulonglong2 *cand, TopCtl *T) {
+  extern __shared__ unsigned long long movers_cells[];  // [2][d][w]
+  const unsigned long long *b = base, *c = cur;
+  if constexpr (LDS) {
+    const uint32_t n = d * w;
+    for (uint32_t i = threadIdx.x; i < n; i += kTopScanBlock) movers_cells[i] = base[i], movers_cells[n + i] = cur[i];
+    __syncthreads();
+    b = movers_cells, c = movers_cells + n;
+  }
+  uint64_t sd[8];  // (cms_d <= 8)
+#pragma unroll
+  for (uint32_t r = 0; r < 8; ++r) sd[r] = r < d ? seeds[r] : 0;
+  uint32_t resident = 0;
+  unsigned long long largest = 0;
+  for (uint64_t s = blockIdx.x * (uint64_t)kTopScanBlock + threadIdx.x; s < cap;
+       s += (uint64_t)gridDim.x * kTopScanBlock) {
+    const uint64_t key = gkeys[s] * kinv;
+    if (!key) continue;
+    ++resident;
+    unsigned long long eb, ec;
+    movers_estimates(b, c, d, w, shift, sd, key, eb, ec);
+    unsigned long long score = ec * nb - eb * nc;  // (two's complement: the signed difference)
+    if (fall) score = 0ULL - score;
+    if ((long long)score < 1 || score < min_score) continue;
+    largest = score > largest ? score : largest;
+    const unsigned long long pos = wave_ticket(&T->n_matched, __ballot(true));
+    if (pos < cap) cand[pos] = ulonglong2{score, key};  // (a table holds a key once: at most cap matches)
+  }
+  resident = wave_sum(resident);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long other = ((unsigned long long)(uint32_t)__shfl_xor((int)(uint32_t)(largest >> 32), o, 64) << 32) |
+                                     (uint32_t)__shfl_xor((int)(uint32_t)largest, o, 64);
+    largest = other > largest ? other : largest;
+  }
+  if ((threadIdx.x & 63u) == 0) {
+    if (resident) atomicAdd(&T->n_resident, (unsigned long long)resident);
+    if (largest) atomicMax(&T->max_est, largest);
+  }
+}
+
+// After the sort: O->est[i] = the (baseline, current) estimates of row i of
+// T->sel, i < T->want (<= kTopSel), from the same arrays the scan read; and,
+// by workgroup 0, O->error_spans_base = the sum of row 0 of base (cur's is
+// top_prepare_kernel's T->error_spans).
+__global__ __launch_bounds__(kTopBlock) void movers_rows_kernel(const unsigned long long *base,
+                                                                const unsigned long long *cur, uint32_t d, uint32_t w,
+                                                                uint32_t shift, const uint64_t *seeds, const TopCtl *T,
+                                                                MoversOut *O) {
+  __shared__ unsigned long long part[kTopBlock];
+  const uint32_t i = blockIdx.x * kTopBlock + threadIdx.x;
+  if (i < T->want && i < kTopSel) {
+    uint64_t sd[8];
+#pragma unroll
+    for (uint32_t r = 0; r < 8; ++r) sd[r] = r < d ? seeds[r] : 0;
+    unsigned long long eb, ec;
+    movers_estimates(base, cur, d, w, shift, sd, T->sel[i].y, eb, ec);
+    O->est[i] = ulonglong2{eb, ec};
+  }
+  if (blockIdx.x) return;
+  unsigned long long acc = 0;
+  for (uint32_t j = threadIdx.x; j < w; j += kTopBlock) acc += base[j];
+  part[threadIdx.x] = acc;
+  __syncthreads();
+  for (uint32_t s = kTopBlock / 2; s > 0; s >>= 1) {
+    if (threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) O->error_spans_base = part[0], O->pad = 0;
+}
+
 }  // namespace
 
 // The scan's grid: 4 slots a thread, at most two workgroups a CU's worth (they stride)
 static uint32_t top_scan_grid(uint64_t cap) {
   return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, (cap + 4 * kTopScanBlock - 1) / (4 * kTopScanBlock)), 512);
+}
+
+// After a scan left its matches in cand [cap] and its counters in T: the row-0
+// sum of cells [..][w] into T->error_spans, then the select and the sort.
+static hipError_t launch_top_select(const unsigned long long *cells, uint32_t w, uint32_t k, uint64_t cap,
+                                    const ulonglong2 *cand, TopCtl *T, hipStream_t s) {
+  hipLaunchKernelGGL(top_prepare_kernel, dim3(1), dim3(kTopBlock), 0, s, cells, w, k, T);
+  // the select's workgroups stride the matches (at most cap); every digit's
+  // launch is enqueued, the device decides which ones work
+  const uint32_t grid = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, (cap + 8 * kTopBlock - 1) / (8 * kTopBlock)), 1024);
+  for (uint32_t digit = 0; digit < kTopDigits; ++digit)
+    hipLaunchKernelGGL(top_digit_kernel, dim3(grid), dim3(kTopBlock), 0, s, cand, T);
+  hipLaunchKernelGGL(top_gather_kernel, dim3(grid), dim3(kTopBlock), 0, s, cand, T);
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  if (hipError_t e = hipFuncSetAttribute((const void *)&top_sort_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int)(kTopSel * sizeof(ulonglong2)));
+      e != hipSuccess)
+    return e;
+  hipLaunchKernelGGL(top_sort_kernel, dim3(1), dim3(kTopSortBlock), kTopSel * sizeof(ulonglong2), s, T);
+  return hipGetLastError();
 }
 
 hipError_t launch_top(const unsigned long long *gkeys, uint64_t cap, uint64_t kinv, const unsigned long long *cells,
@@ -657,19 +791,32 @@ hipError_t launch_top(const unsigned long long *gkeys, uint64_t cap, uint64_t ki
                        d, w, shift, seeds, min_count, cand, T);
   }
   if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-  hipLaunchKernelGGL(top_prepare_kernel, dim3(1), dim3(kTopBlock), 0, s, cells, w, k, T);
-  // the select's workgroups stride the matches (at most cap); every digit's
-  // launch is enqueued, the device decides which ones work
-  const uint32_t grid = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, (cap + 8 * kTopBlock - 1) / (8 * kTopBlock)), 1024);
-  for (uint32_t digit = 0; digit < kTopDigits; ++digit)
-    hipLaunchKernelGGL(top_digit_kernel, dim3(grid), dim3(kTopBlock), 0, s, cand, T);
-  hipLaunchKernelGGL(top_gather_kernel, dim3(grid), dim3(kTopBlock), 0, s, cand, T);
+  return launch_top_select(cells, w, k, cap, cand, T, s);
+}
+
+hipError_t launch_movers(const unsigned long long *gkeys, uint64_t cap, uint64_t kinv, const unsigned long long *base,
+                         const unsigned long long *cur, uint32_t d, uint32_t w, uint32_t shift, const uint64_t *seeds,
+                         uint64_t nb, uint64_t nc, uint32_t fall, uint32_t k, unsigned long long min_score,
+                         ulonglong2 *cand, TopCtl *T, MoversOut *O, hipStream_t s) {
+  if (hipError_t e = hipMemsetAsync(T, 0, offsetof(TopCtl, sel), s); e != hipSuccess) return e;
+  const size_t both_bytes = 2 * (size_t)d * w * 8;
+  // the heavy hitters' grid; staged, both arrays are one workgroup a CU: at most 256 (they stride)
+  const uint32_t grid = top_scan_grid(cap);
+  if (both_bytes <= kMoversCellsLds) {
+    if (hipError_t e = hipFuncSetAttribute((const void *)&movers_scan_kernel<1>,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMoversCellsLds);
+        e != hipSuccess)
+      return e;
+    hipLaunchKernelGGL(movers_scan_kernel<1>, dim3(std::min(grid, 256u)), dim3(kTopScanBlock), both_bytes, s, gkeys,
+                       cap, kinv, base, cur, d, w, shift, seeds, nb, nc, fall, min_score, cand, T);
+  } else {
+    hipLaunchKernelGGL(movers_scan_kernel<0>, dim3(grid), dim3(kTopScanBlock), 0, s, gkeys, cap, kinv, base, cur, d, w,
+                       shift, seeds, nb, nc, fall, min_score, cand, T);
+  }
   if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-  if (hipError_t e = hipFuncSetAttribute((const void *)&top_sort_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)(kTopSel * sizeof(ulonglong2)));
-      e != hipSuccess)
-    return e;
-  hipLaunchKernelGGL(top_sort_kernel, dim3(1), dim3(kTopSortBlock), kTopSel * sizeof(ulonglong2), s, T);
+  if (hipError_t e = launch_top_select(cur, w, k, cap, cand, T, s); e != hipSuccess) return e;
+  hipLaunchKernelGGL(movers_rows_kernel, dim3((k + kTopBlock - 1) / kTopBlock), dim3(kTopBlock), 0, s, base, cur, d, w,
+                     shift, seeds, T, O);
   return hipGetLastError();
 }
 

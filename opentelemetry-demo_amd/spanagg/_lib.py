@@ -108,6 +108,20 @@ class sa_top_result(C.Structure):
     ]
 
 
+SA_MOVERS_FALL = 1
+i64p = C.POINTER(C.c_int64)
+
+
+class sa_movers_result(C.Structure):
+    _fields_ = [
+        ("base_first", C.c_uint64), ("base_last", C.c_uint64), ("cur_first", C.c_uint64), ("cur_last", C.c_uint64),
+        ("k", C.c_uint32), ("n", C.c_uint32), ("flags", C.c_uint32), ("pad", C.c_uint32),
+        ("n_resident", C.c_uint64), ("n_matched", C.c_uint64),
+        ("error_spans_base", C.c_uint64), ("error_spans_cur", C.c_uint64),
+        ("key_hash", u64p), ("score", i64p), ("baseline", u64p), ("current", u64p),
+    ]
+
+
 SA_OVERLAP_MAX_SERVICES = OVERLAP_MAX_SERVICES = 64
 
 
@@ -186,6 +200,11 @@ SIGNATURES = [
     ("sa_group_window_top", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32,
                                       C.POINTER(C.POINTER(sa_top_result))]),
     ("sa_top_result_free", None, [C.POINTER(sa_top_result)]),
+    ("sa_window_movers", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64,
+                                   C.c_uint32, C.POINTER(C.POINTER(sa_movers_result))]),
+    ("sa_group_window_movers", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
+                                         C.c_uint64, C.c_uint32, C.POINTER(C.POINTER(sa_movers_result))]),
+    ("sa_movers_result_free", None, [C.POINTER(sa_movers_result)]),
     ("sa_window_overlap", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, u32p, C.c_uint32, C.c_uint32,
                                     C.POINTER(C.POINTER(sa_overlap_result))]),
     ("sa_group_window_overlap", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, u32p, C.c_uint32, C.c_uint32,

@@ -196,6 +196,28 @@ class TopResult:
 
 
 @dataclass
+class MoversResult:
+    """sa_movers_result: the series whose ERROR spans per window rose most (fall:
+    fell most) from the baseline range to the current one, among the series
+    resident in the engine's key table, by the two ranges' summed count-mins."""
+    base: tuple                   # (first, last) of the baseline range
+    cur: tuple                    # (first, last) of the current range
+    fall: bool
+    keys: np.ndarray              # [n] u64, by score descending then key ascending
+    score: np.ndarray             # [n] i64: current * n_base - baseline * n_cur (negated when fall), >= 1
+    baseline: np.ndarray          # [n] u64: window_range(*base, [keys[i]]).errors[0]
+    current: np.ndarray           # [n] u64: window_range(*cur, [keys[i]]).errors[0]
+    n_resident: int               # series in the key table when the call ran: the candidates
+    n_matched: int                # candidates with a score >= max(min_score, 1)
+    error_spans_base: int         # ERROR spans the baseline range's sketches counted, exact
+    error_spans_cur: int          # the same of the current range
+
+    def items(self):
+        """[(key, score, baseline, current)] as sketch.movers returns them."""
+        return [(int(k), int(s), int(b), int(c)) for k, s, b, c in zip(self.keys, self.score, self.baseline, self.current)]
+
+
+@dataclass
 class OverlapResult:
     """sa_overlap_result: for every pair of the selected services the traces
     both saw over windows first..last, by inclusion-exclusion on the merged
@@ -340,6 +362,24 @@ def _window_top(obj, fn, what, first, last, k, min_count) -> TopResult:
                          int(r.n_resident), int(r.n_matched), int(r.error_spans))
     finally:
         obj.lib.sa_top_result_free(out)
+
+
+def _window_movers(obj, fn, what, base, cur, k, min_score, fall) -> MoversResult:
+    """sa_window_movers / sa_group_window_movers -> MoversResult (copies), freeing the library's result."""
+    (bf, bl), (cf, cl) = base, cur
+    out = C.POINTER(_lib.sa_movers_result)()
+    obj._check(fn(obj._h, int(bf), int(bl), int(cf), int(cl), int(k), int(min_score),
+                  _lib.SA_MOVERS_FALL if fall else 0, C.byref(out)), what)
+    try:
+        r = out.contents
+        n = int(r.n)
+        col = lambda p, dt=np.uint64: np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, dt)
+        return MoversResult((int(r.base_first), int(r.base_last)), (int(r.cur_first), int(r.cur_last)),
+                            bool(r.flags & _lib.SA_MOVERS_FALL), col(r.key_hash), col(r.score, np.int64),
+                            col(r.baseline), col(r.current), int(r.n_resident), int(r.n_matched),
+                            int(r.error_spans_base), int(r.error_spans_cur))
+    finally:
+        obj.lib.sa_movers_result_free(out)
 
 
 def _window_overlap(obj, fn, what, first, last, services) -> OverlapResult:
@@ -557,6 +597,14 @@ class Engine:
         >= min_count -- scanned, selected and sorted on the device."""
         return _window_top(self, self.lib.sa_window_top, "sa_window_top", first, last, k, min_count)
 
+    def window_movers(self, base, cur, k: int = 10, min_score: int = 1, fall: bool = False) -> MoversResult:
+        """sa_window_movers: the k series whose ERROR spans per window rose
+        most (fall: fell most) from the windows base = (first, last) to the
+        windows cur = (first, last), among the series resident in the key
+        table with a score >= min_score -- one scan of the table against both
+        ranges' summed count-mins, selected and sorted on the device."""
+        return _window_movers(self, self.lib.sa_window_movers, "sa_window_movers", base, cur, k, min_score, fall)
+
     def window_overlap(self, first: int, last: int, services=None) -> OverlapResult:
         """sa_window_overlap: the traces every pair of `services` (ids, at most
         OVERLAP_MAX_SERVICES; None: every service of an engine with no more
@@ -742,6 +790,12 @@ class Group:
         """sa_group_window_top: Engine.window_top over the members' merge
         (n_resident and n_matched summed over the members)."""
         return _window_top(self, self.lib.sa_group_window_top, "sa_group_window_top", first, last, k, min_count)
+
+    def window_movers(self, base, cur, k: int = 10, min_score: int = 1, fall: bool = False) -> MoversResult:
+        """sa_group_window_movers: Engine.window_movers over the members' merge
+        (n_resident and n_matched are summed over members)."""
+        return _window_movers(self, self.lib.sa_group_window_movers, "sa_group_window_movers", base, cur, k, min_score,
+                              fall)
 
     def window_overlap(self, first: int, last: int, services=None) -> OverlapResult:
         """sa_group_window_overlap: Engine.window_overlap over the members' merge."""

@@ -37,6 +37,24 @@ def heavy_hitters(cms: np.ndarray, error_keys: Iterable[int], k: int = 10):
     return est[:k]
 
 
+def movers(cms_base: np.ndarray, cms_cur: np.ndarray, n_base: int, n_cur: int, keys: Iterable[int], k: int = 10,
+           min_score: int = 1, fall: bool = False):
+    """Top-k (key, score, baseline, current) of `keys` by the change of their
+    ERROR spans per window from the baseline range (cms_base: the cells of
+    its n_base windows summed) to the current one (cms_cur, n_cur): score =
+    current * n_base - baseline * n_cur, negated when `fall` -- the difference
+    of the per-window means times n_base * n_cur, so no division enters.  Rows
+    with score >= max(min_score, 1), by score descending then key ascending."""
+    rows = []
+    for key in keys:
+        b, c = cms_query(cms_base, key), cms_query(cms_cur, key)
+        score = c * int(n_base) - b * int(n_cur)
+        rows.append((int(key), -score if fall else score, b, c))
+    rows = [r for r in rows if r[1] >= max(int(min_score), 1)]
+    rows.sort(key=lambda r: (-r[1], r[0]))
+    return rows[:k]
+
+
 def distinct_traces(hll: np.ndarray, p: int) -> np.ndarray:
     """[n_services] HLL estimates of distinct trace ids."""
     return np.array([hll_estimate(hll[s], p) for s in range(hll.shape[0])])
