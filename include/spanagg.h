@@ -22,6 +22,7 @@
  *   (new) heavy hitters over a span of windows      sa_window_top (key table scanned on the device)
  *   (new) traces shared by pairs of services        sa_window_overlap (pairwise register maxima on the device)
  *   (new) series whose ERROR rate changed most      sa_window_movers (key table against two ranges' cells on the device)
+ *   (new) duration quantiles per service and window sa_window_latency (log-linear histograms in the ring, SA_OPT_WINDOW_LATENCY)
  *
  * Boundary rules (mirroring the connector's contracts):
  *  - Ownership: batches are borrowed for the duration of the call (page-locked
@@ -115,7 +116,18 @@ typedef enum { SA_UNIT_MS = 0, SA_UNIT_S = 1 } sa_unit;
  * SA_ESTATE (no hash -> slot map on the device; nothing is ever full, flush
  * never reclaims); sa_stats.n_keys is the number of bound indices. */
 #define SA_OPT_DENSE_IDS     (1u << 9)
-#define SA_OPT_ALL           0x3FFu
+/* Latency histograms over the window ring (spanagg_latency.hip): the engine
+ * also keeps, per resident window and service, a histogram of span durations
+ * in SA_LAT_BINS log-linear bins, read by sa_window_latency.  It combines with
+ * every other option and runs beside every ingest path: one more streaming
+ * kernel per launch, which reads start_ns, end_ns and meta (20 bytes a span)
+ * and no key.  The ring holds n_windows * n_services * SA_LAT_BINS u64:
+ * sa_create returns SA_EINVAL when n_windows * n_services > 2^18 (512 MiB)
+ * and SA_ENOMEM when the allocation fails.  With the option
+ * sa_ingest_device_many takes the one-by-one path (no graph).  Without it
+ * nothing is allocated and nothing more is launched. */
+#define SA_OPT_WINDOW_LATENCY (1u << 10)
+#define SA_OPT_ALL           0x7FFu
 
 typedef struct {
     /* histogram.explicit.buckets (sorted ascending, finite) and histogram.unit */
@@ -252,7 +264,8 @@ int sa_ingest_device(sa_engine *e, const sa_span_batch *batch, void *stream);
  * the stream reaches the end of the k).  Small-table engines launch the k
  * ingests as one HIP graph, so consecutive launches carry no per-launch
  * dispatch gap; other engines (binned, exponential, laboratory options) and
- * batches that would need a split take the one-by-one path.  Unlike
+ * batches that would need a split take the one-by-one path, and so does every
+ * engine with SA_OPT_WINDOW_LATENCY.  Unlike
  * sa_ingest_device, the graph path can block the host: the engine keeps two
  * instantiated graphs and, before it re-points one at new batches, waits
  * (hipEventSynchronize) until that graph's previous launch -- the one of two
@@ -519,6 +532,66 @@ int sa_window_overlap(sa_engine *e, uint64_t first, uint64_t last, const uint32_
                       uint32_t n_sel, uint32_t flags, sa_overlap_result **out);
 void sa_overlap_result_free(sa_overlap_result *r);
 
+/* ---- duration quantiles over the window ring (SA_OPT_WINDOW_LATENCY) ----
+ * "What was checkout's p99 in each of the last 30 windows": per resident
+ * window and service the engine keeps a histogram of span durations in
+ * SA_LAT_BINS log-linear bins.  Histograms add over windows (and over a
+ * group's members), so every output of a sliding series costs one row added
+ * and one subtracted, and only counts and quantiles cross the bus.
+ *
+ * Bin of a duration d = end > start ? end - start : 0 (ns), with q = d >> 7:
+ *   q < 16:  bin q                                   (bins 0..15, 128 ns wide)
+ *   else:    e = floor(log2 q), bin min(255, ((e - 3) << 3) + (q >> (e - 3)))
+ * -- from 2,048 ns up eight bins an octave, each at most 12.5 % wide relative
+ * to its lower bound; bin 255 starts at 15 << 37 ns (about 34 min) and has no
+ * upper bound (sa_latency_bin_bounds gives UINT64_MAX).
+ * Which spans count: exactly those that update their HLL register --
+ * service_id < n_services and end_ns / window_ns inside the ring as it stands
+ * at the launch.  key_hash is not read: key 0, spans dropped by a full table
+ * and unbound dense indices all count. */
+#define SA_LAT_BINS  256u
+#define SA_LAT_MAX_Q 8u
+#define SA_LAT_HIST  1u              /* also return the summed histograms */
+
+typedef struct {
+    uint64_t first_window, last_window;  /* outputs t = first..last, inclusive */
+    uint32_t width, n_out;               /* output t covers windows t-width+1 .. t; n_out = last-first+1 */
+    uint32_t n_sel, n_q;
+    const uint32_t *services;   /* [n_sel] service ids, in the caller's order */
+    const uint32_t *q_ppm;      /* [n_q] as given */
+    const uint64_t *count;      /* [n_out][n_sel] spans of the covered windows */
+    const uint8_t  *q_bin;      /* [n_out][n_sel][n_q] the smallest bin whose cumulative count reaches
+                                   r = max(1, ceil(count * q_ppm / 10^6)); 0 when count == 0 */
+    const uint64_t *q_ns;       /* [n_out][n_sel][n_q] that bin's upper bound (sa_latency_bin_bounds): an
+                                   upper bound on the true quantile, within 12.5 % (127 ns in the
+                                   linear bins); 0 when count == 0 */
+    const uint64_t *hist;       /* [n_out][n_sel][SA_LAT_BINS] the covered windows' bins summed;
+                                   NULL without SA_LAT_HIST */
+} sa_latency_result;
+
+/* A plain range query is first == last with width = the range's length.
+ * services == NULL with n_sel == 0 selects every service in id order.
+ * q_ppm[i]: a quantile in parts per million, 1..1000000; 1 <= n_q <=
+ * SA_LAT_MAX_Q.  Exact while count < 2^44 (count * q_ppm is taken in u64).
+ * Ordering and waiting as sa_window_range: joins every launch in flight, runs
+ * on the engine stream, waits once, clears nothing (two calls give equal
+ * bits).  Works on every ingest path.
+ * SA_ESTATE on an engine without SA_OPT_WINDOW_LATENCY; SA_ERANGE as
+ * sa_window_series (first > last, width == 0, width > n_windows, first + 1 <
+ * width, or first-width+1 or last not resident); SA_EINVAL for a null `out`,
+ * services == NULL with n_sel != 0 or the reverse, an id >= n_services, a
+ * repeated id, n_q == 0 or > SA_LAT_MAX_Q, a q_ppm outside 1..10^6, unknown
+ * flag bits, n_out * n_sel > 2^20 (> 2^16 with SA_LAT_HIST); SA_ENOMEM when
+ * the device scratch or the result cannot be allocated.  While sa_create holds
+ * the ring to 2^18 rows, n_out * n_sel cannot pass 2^18, so only the
+ * SA_LAT_HIST bound is ever met (128 MiB of histograms a result); the other
+ * guards the result's size should the ring's bound move.  The engine stays
+ * usable after any error.  Free the result with sa_latency_result_free. */
+int sa_window_latency(sa_engine *e, uint64_t first, uint64_t last, uint32_t width, const uint32_t *services,
+                      uint32_t n_sel, const uint32_t *q_ppm, uint32_t n_q, uint32_t flags,
+                      sa_latency_result **out);
+void sa_latency_result_free(sa_latency_result *r);
+
 int sa_get_stats(sa_engine *e, sa_stats *out);
 
 /* ---- multi-GPU merge hooks (device pointers on this engine's device) ----
@@ -633,6 +706,15 @@ int sa_group_window_movers(sa_group *g, uint64_t base_first, uint64_t base_last,
  * engine fed every span, bit for bit. */
 int sa_group_window_overlap(sa_group *g, uint64_t first, uint64_t last, const uint32_t *services,
                             uint32_t n_sel, uint32_t flags, sa_overlap_result **out);
+/* sa_window_latency of a group: every member takes the sliding sums of its
+ * own ring on its device, the group's transport adds the members' sums
+ * (histograms are additive over members), and member 0's device takes the
+ * counts and the quantile bins.  Results equal those of one engine fed every
+ * span, bit for bit.  Every member's sums of a call take n_out * n_sel * 2 KiB
+ * on its device: at most the ring's own size, 512 MiB. */
+int sa_group_window_latency(sa_group *g, uint64_t first, uint64_t last, uint32_t width, const uint32_t *services,
+                            uint32_t n_sel, const uint32_t *q_ppm, uint32_t n_q, uint32_t flags,
+                            sa_latency_result **out);
 /* Counters summed over members (n_keys and table_capacity too; window_base and
  * small_table from member 0). */
 int sa_group_get_stats(sa_group *g, sa_stats *out);
@@ -652,6 +734,14 @@ double sa_hll_estimate(const uint8_t *regs, uint32_t p);
  * order; then sa_hll_estimate's alpha and linear-counting branch (zeros =
  * hist[0]).  -1.0 for p outside 4..18.  Defines sa_range_result.distinct. */
 double sa_hll_estimate_hist(const uint32_t *hist, uint32_t p);
+/* The latency bin of a duration in ns (the rule above sa_latency_result). */
+uint32_t sa_latency_bin(uint64_t d_ns);
+/* The durations of one bin, inclusive: for bin < 16 [bin << 7, (bin << 7) +
+ * 127]; else with e = (bin >> 3) + 2 and m = bin & 7, lo = ((8 + m) << (e -
+ * 3)) << 7 and hi = (((9 + m) << (e - 3)) << 7) - 1; hi of bin 255 is
+ * UINT64_MAX.  The bins tile [0, 2^64).  SA_EINVAL for bin >= SA_LAT_BINS or a
+ * null pointer. */
+int sa_latency_bin_bounds(uint32_t bin, uint64_t *lo, uint64_t *hi);
 
 #ifdef __cplusplus
 }

@@ -12,6 +12,7 @@
 #include <string>
 
 #include "sa_engine.h"
+#include "sa_latency.h"
 #include "spanagg_diag.h"
 
 using sa::Path;
@@ -62,6 +63,8 @@ int validate_config(const sa_config *c, sa::Hist &h, std::string &why) {
   if (c->exp_max_size == 1 || c->exp_max_size > sa::kExpoMaxSize)
     return why = "exp_max_size must be 0 (explicit buckets) or 2..4096", SA_EINVAL;
   if (c->options & ~SA_OPT_ALL) return why = "unknown bits in options", SA_EINVAL;
+  if ((c->options & SA_OPT_WINDOW_LATENCY) && (uint64_t)c->n_windows * c->n_services > (1ULL << 18))
+    return why = "SA_OPT_WINDOW_LATENCY: n_windows * n_services must stay within 2^18 (a 512 MiB ring)", SA_EINVAL;
 #ifndef SPANAGG_AB
   if (c->flags) return why = "SA_DIAG_* flags need the laboratory build (libspanagg_ab.so)", SA_EINVAL;
 #endif
@@ -136,6 +139,14 @@ double sa_hll_estimate_hist(const uint32_t *hist, uint32_t p) {
   double est = alpha * (double)m * (double)m / sum;
   if (est <= 2.5 * m && zeros) est = (double)m * std::log((double)m / (double)zeros);
   return est;
+}
+
+uint32_t sa_latency_bin(uint64_t d_ns) { return sa::latency_bin(d_ns); }
+
+int sa_latency_bin_bounds(uint32_t bin, uint64_t *lo, uint64_t *hi) {
+  if (bin >= SA_LAT_BINS || !lo || !hi) return SA_EINVAL;
+  sa::latency_bin_bounds(bin, lo, hi);
+  return SA_OK;
 }
 
 int sa_create(const sa_config *cfg, sa_engine **out) {
@@ -313,6 +324,14 @@ int sa_create(const sa_config *cfg, sa_engine **out) {
   }
   if ((cfg->options & SA_OPT_STAMPS) && (rc = dalloc(e, e->dbg, (size_t)e->G * sa::kDbgPerWg, true)))
     return bail(rc);
+  if (cfg->options & SA_OPT_WINDOW_LATENCY) {
+    sa_engine::Latency &L = e->lat;
+    if ((rc = dalloc(e, L.ring, (size_t)W * S * SA_LAT_BINS, true, "latency ring hipMalloc failed"))) return bail(rc);
+    const sa::LatGeom lg = sa::lat_geometry(cfg->n_services, cfg->n_windows);
+    L.k_slots = lg.k_slots;
+    L.grid_max = e->cus * lg.per_cu;
+    if (L.k_slots && (rc = lds_attr(sa::prepare_lat_ingest((size_t)L.k_slots * cfg->n_services * 1024)))) return bail(rc);
+  }
   if (h.has_bins) {
     if ((rc = dalloc(e, e->d_bins, sa::kBins, true))) return bail(rc);
     if (hipMemcpy(e->d_bins, h.bins, sizeof h.bins, hipMemcpyHostToDevice) != hipSuccess)

@@ -389,7 +389,9 @@ int launch_partitioned(sa_engine *e, uint64_t n, IngestParams &P, hipStream_t s)
     if (dalloc(e, e->part.rec, sa::kPartBins * per_bin_max, false, what) ||
         dalloc(e, e->part.fill, sa::kPartBins, false, what))
       return SA_ENOMEM;
-    if (hipMemset(e->part.fill, 0, sa::kPartBins * 4) != hipSuccess) return fail(e, SA_ENOMEM, what);
+    // (on `s`, ahead of the scatter in stream order: a null-stream memset is
+    // not ordered against a caller's non-blocking stream)
+    if (hipMemsetAsync(e->part.fill, 0, sa::kPartBins * 4, s) != hipSuccess) return fail(e, SA_ENOMEM, what);
   }
   P.part_rec = e->part.rec;
   P.part_fill = e->part.fill;
@@ -463,6 +465,18 @@ int launch_expo(sa_engine *e, const sa_span_batch *b, uint32_t set, uint32_t gri
   return launched(e, st);
 }
 
+// SA_OPT_WINDOW_LATENCY: the latency kernel over the launch's batch, with the
+// launch's own parameters (the same ring base and window fields).  Workgroups
+// of whole 4,096-span tiles, at most the engine's resident round; a range so
+// long that an LDS cell could wrap takes the HBM form.
+int launch_latency(sa_engine *e, uint64_t n, const IngestParams &P, hipStream_t s) {
+  const sa_engine::Latency &L = e->lat;
+  if (!L.ring) return SA_OK;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 4095) / 4096, L.grid_max);
+  const uint64_t chunk = ((n + grid - 1) / grid + 3) / 4 * 4;
+  return launched(e, sa::launch_lat_ingest(P, L.ring, grid, chunk, chunk >> 32 ? 0 : L.k_slots, s));
+}
+
 // One launch of batch b (at most max_spans_per_launch spans) on `s`: the plan,
 // room in the slabs, the order before, the path's launcher, the mark after.
 int ingest_launch(sa_engine *e, const sa_span_batch *b, hipStream_t s) {
@@ -478,6 +492,10 @@ int ingest_launch(sa_engine *e, const sa_span_batch *b, hipStream_t s) {
   fill_params(e, b, set, pl, P);
   hipStream_t hs = s;  // the stream the launch's last kernel runs on (expo: the histogram kernels')
   int rc = SA_OK;
+  // the latency histograms first, on `s`: the set event mark_after records
+  // is behind them on every path (a scatter, an ingest kernel or the
+  // histogram kernels follow on `s`, or wait for something that does)
+  if ((rc = launch_latency(e, b->n, P, s))) return rc;
   switch (e->path) {
     case Path::Small: rc = launch_small(e, pl.grid, P, s); break;
     case Path::Binned:
@@ -664,7 +682,8 @@ int sa_ingest_device_many(sa_engine *e, const sa_span_batch *bs, uint32_t k, voi
     if (int rc = check_batch(e, &bs[i], true)) return rc;
   if (int rc = set_dev(e)) return rc;
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : e->stream;
-  bool graph = k > 1 && e->path == Path::Small && !e->dbg && !e->diag();
+  // (SA_OPT_WINDOW_LATENCY: one by one, each launch with its latency kernel)
+  bool graph = k > 1 && e->path == Path::Small && !e->dbg && !e->diag() && !e->lat.ring;
   std::vector<LaunchPlan> pl(graph ? k : 0);
   uint64_t load = 0;
   for (uint32_t i = 0; graph && i < k; ++i) {

@@ -413,9 +413,162 @@ int overlap_on(sa_engine *e, uint64_t first, uint64_t last, const uint8_t *regs,
   *out = &h.release()->r;
   return SA_OK;
 }
+// ---- latency quantiles (sa_window_latency; kernels in spanagg_latency.hip) ----
+// rows of sliding sums one tile of outputs holds (64 MiB; at least one output's)
+constexpr uint64_t kLatTileRows = 1u << 15;
+
+int latency_enabled(sa_engine *e) {
+  if (e->lat.ring) return SA_OK;
+  return fail(e, SA_ESTATE, "window latency: the engine was not created with SA_OPT_WINDOW_LATENCY");
+}
+
+int latency_range(sa_engine *e, uint64_t first, uint64_t last, uint32_t width) {
+  if (first > last || width == 0 || width > e->cfg.n_windows || first + 1 < width || !resident(e, first - width + 1) ||
+      !resident(e, last))
+    return fail(e, SA_ERANGE, "window latency: first > last, a width outside 1..n_windows, or a covered window is not resident");
+  return SA_OK;
+}
+
+// Room for a selection of n_sel ids, sum_rows rows of sliding sums in the
+// engine's own tile and `rows` rows' counts and quantile bins.
+int latency_buffers(sa_engine *e, uint64_t n_sel, uint64_t sum_rows, uint64_t rows, uint32_t n_q) {
+  sa_engine::Latency &L = e->lat;
+  if (int rc = series_grow(e, L.sel, L.sel_cap, n_sel ? std::max<uint64_t>(n_sel, 64) : 0,
+                           "window latency: selection hipMalloc failed"))
+    return rc;
+  if (int rc = series_grow(e, L.sums, L.sums_cap, sum_rows * SA_LAT_BINS, "window latency: sum buffer hipMalloc failed"))
+    return rc;
+  if (int rc = series_grow(e, L.count, L.row_cap, rows, "window latency: count buffer hipMalloc failed")) return rc;
+  return series_grow(e, L.q_bin, L.qbin_cap, rows * n_q, "window latency: quantile buffer hipMalloc failed");
+}
+
+// A member's part of a group query on `s`: the selection onto the device and
+// the sums stage behind it, sums [n_out][sel.size()][SA_LAT_BINS] from window
+// `a` on.  The copy reads the caller's pageable `sel` asynchronously, so it is
+// queued after everything that can fail without a wait, and a failure behind
+// it waits for `s` before it returns; on success the group waits before `sel` goes.
+hipError_t latency_sums_on(sa_engine *e, const std::vector<uint32_t> &sel, uint64_t a, uint32_t width, uint32_t n_out,
+                           unsigned long long *d_sums, hipStream_t s) {
+  const sa_engine::Latency &L = e->lat;
+  hipError_t st = hipMemcpyAsync(L.sel, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, s);
+  if (st == hipSuccess)
+    st = sa::launch_lat_sums(L.ring, e->cfg.n_services, e->cfg.n_windows, L.sel, (uint32_t)sel.size(), a, width, n_out,
+                             d_sums, s);
+  if (st != hipSuccess) (void)hipStreamSynchronize(s);
+  return st;
+}
+
+// On `s`: the counts and quantile bins of rows row0 .. row0 + n_rows - 1 from
+// their sums d_sums [n_rows][SA_LAT_BINS], and with SA_LAT_HIST the sums' copy
+// into the result.
+hipError_t latency_scan_on(sa_engine *e, const unsigned long long *d_sums, uint64_t row0, uint64_t n_rows,
+                           latency_holder *h, hipStream_t s) {
+  const sa_engine::Latency &L = e->lat;
+  const uint32_t n_q = h->r.n_q;
+  hipError_t st = sa::launch_lat_scan(d_sums, n_rows, h->q_ppm.data(), n_q, L.count + row0, L.q_bin + row0 * n_q, s);
+  if (st == hipSuccess && h->r.hist)
+    st = hipMemcpyAsync(h->hist.data() + row0 * SA_LAT_BINS, d_sums, n_rows * SA_LAT_BINS * 8, hipMemcpyDeviceToHost, s);
+  return st;
+}
+
+// The counts and bins into the result (st: what the launches before returned),
+// the call's one wait -- also after a failure: a copy into h may be in flight
+// -- and every bin's upper bound.
+int latency_collect(sa_engine *e, hipError_t st, std::unique_ptr<latency_holder> &h, hipStream_t s,
+                    sa_latency_result **out) {
+  const sa_engine::Latency &L = e->lat;
+  if (st == hipSuccess) st = hipMemcpyAsync(h->count.data(), L.count, h->count.size() * 8, hipMemcpyDeviceToHost, s);
+  if (st == hipSuccess) st = hipMemcpyAsync(h->q_bin.data(), L.q_bin, h->q_bin.size(), hipMemcpyDeviceToHost, s);
+  const hipError_t waited = hipStreamSynchronize(s);
+  if (st != hipSuccess || waited != hipSuccess)
+    return fail(e, SA_EDEVICE, std::string("window latency: ") + hipGetErrorString(st != hipSuccess ? st : waited));
+  const uint32_t n_q = h->r.n_q;
+  for (size_t row = 0; row < h->count.size(); ++row)
+    for (uint32_t i = 0; i < n_q; ++i) {
+      uint64_t lo = 0, hi = 0;
+      if (h->count[row]) (void)sa_latency_bin_bounds(h->q_bin[row * n_q + i], &lo, &hi);
+      h->q_ns[row * n_q + i] = hi;
+    }
+  *out = &h.release()->r;
+  return SA_OK;
+}
+
+std::unique_ptr<latency_holder> latency_result(sa_engine *e, uint64_t first, uint64_t last, uint32_t width,
+                                               const std::vector<uint32_t> &sel, const uint32_t *q_ppm, uint32_t n_q,
+                                               uint32_t flags) {
+  std::unique_ptr<latency_holder> h;
+  try {
+    h.reset(new latency_holder());
+    h->shape(first, last, width, sel, q_ppm, n_q, flags);
+  } catch (const std::bad_alloc &) {
+    h.reset();
+    (void)fail(e, SA_ENOMEM, "window latency: the result does not fit in host memory");
+  }
+  return h;
+}
 }  // namespace
 
 namespace sa_grp {
+const char *latency_args(uint32_t n_services, const uint32_t *services, uint32_t n_sel, const uint32_t *q_ppm,
+                         uint32_t n_q, uint32_t flags, std::vector<uint32_t> *sel) {
+  sel->clear();
+  if (flags & ~SA_LAT_HIST) return "window latency: unknown flag bits";
+  if (n_q == 0 || n_q > SA_LAT_MAX_Q || !q_ppm) return "window latency: n_q outside 1..SA_LAT_MAX_Q or null q_ppm";
+  for (uint32_t i = 0; i < n_q; ++i)
+    if (q_ppm[i] == 0 || q_ppm[i] > 1000000u) return "window latency: a q_ppm outside 1..1000000";
+  if (!services) {
+    if (n_sel) return "window latency: n_sel != 0 with null services";
+    for (uint32_t i = 0; i < n_services; ++i) sel->push_back(i);
+    return nullptr;
+  }
+  if (n_sel == 0) return "window latency: an empty selection";
+  if (n_sel > n_services) return "window latency: more ids than services (a repeated id)";
+  std::vector<bool> seen(n_services, false);
+  for (uint32_t i = 0; i < n_sel; ++i) {
+    if (services[i] >= n_services) return "window latency: a service id at or past n_services";
+    if (seen[services[i]]) return "window latency: a repeated service id";
+    seen[services[i]] = true;
+    sel->push_back(services[i]);
+  }
+  return nullptr;
+}
+
+const char *latency_rows(uint64_t n_out, uint64_t n_sel, uint32_t flags) {
+  if (n_out * n_sel > ((flags & SA_LAT_HIST) ? 1ull << 16 : 1ull << 20))
+    return "window latency: n_out * n_sel above 2^20 (2^16 with SA_LAT_HIST)";
+  return nullptr;
+}
+
+int window_latency_export_async(sa_engine *e, uint64_t first, uint64_t last, uint32_t width,
+                                const std::vector<uint32_t> &sel, uint64_t *d_sums, hipStream_t s) {
+  if (!e || !d_sums || sel.empty()) return SA_EINVAL;
+  if (int rc = latency_enabled(e)) return rc;
+  if (int rc = latency_range(e, first, last, width)) return rc;
+  if (int rc = begin_read(e)) return rc;
+  if (int rc = latency_buffers(e, sel.size(), 0, 0, 0)) return rc;
+  if (int rc = hop_to(e, s)) return rc;
+  SA_HIP(e, latency_sums_on(e, sel, first - width + 1, width, (uint32_t)(last - first + 1),
+                            reinterpret_cast<unsigned long long *>(d_sums), s));
+  if (int rc = hop_back(e, s)) {  // (the selection buffer is the engine's)
+    (void)hipStreamSynchronize(s);
+    return rc;
+  }
+  return SA_OK;
+}
+
+int window_latency_finish(sa_engine *e, uint64_t first, uint64_t last, uint32_t width, const std::vector<uint32_t> &sel,
+                          const uint32_t *q_ppm, uint32_t n_q, uint32_t flags, const uint64_t *d_sums, hipStream_t s,
+                          sa_latency_result **out) {
+  if (!e || !out || !d_sums || sel.empty()) return SA_EINVAL;
+  if (int rc = set_dev(e)) return rc;
+  std::unique_ptr<latency_holder> h = latency_result(e, first, last, width, sel, q_ppm, n_q, flags);
+  if (!h) return SA_ENOMEM;
+  const uint64_t rows = h->count.size();
+  if (int rc = latency_buffers(e, 0, 0, rows, n_q)) return rc;
+  const hipError_t st = latency_scan_on(e, reinterpret_cast<const unsigned long long *>(d_sums), 0, rows, h.get(), s);
+  return latency_collect(e, st, h, s, out);
+}
+
 const char *overlap_select(uint32_t n_services, const uint32_t *services, uint32_t n_sel, std::vector<uint32_t> *sel) {
   sel->clear();
   if (!services) {
@@ -960,6 +1113,44 @@ int sa_window_overlap(sa_engine *e, uint64_t first, uint64_t last, const uint32_
 
 void sa_overlap_result_free(sa_overlap_result *r) { delete reinterpret_cast<overlap_holder *>(r); }
 
+int sa_window_latency(sa_engine *e, uint64_t first, uint64_t last, uint32_t width, const uint32_t *services,
+                      uint32_t n_sel, const uint32_t *q_ppm, uint32_t n_q, uint32_t flags, sa_latency_result **out) {
+  if (!e || !out) return SA_EINVAL;
+  *out = nullptr;
+  if (int rc = latency_enabled(e)) return rc;
+  std::vector<uint32_t> sel;
+  try {
+    if (const char *bad = sa_grp::latency_args(e->cfg.n_services, services, n_sel, q_ppm, n_q, flags, &sel))
+      return fail(e, SA_EINVAL, bad);
+  } catch (const std::bad_alloc &) {
+    return fail(e, SA_ENOMEM, "window latency: the selection does not fit in host memory");
+  }
+  if (int rc = latency_range(e, first, last, width)) return rc;
+  const uint32_t n_out = (uint32_t)(last - first + 1), S = (uint32_t)sel.size();
+  if (const char *bad = sa_grp::latency_rows(n_out, S, flags)) return fail(e, SA_EINVAL, bad);
+  if (int rc = begin_read(e)) return rc;
+  std::unique_ptr<latency_holder> h = latency_result(e, first, last, width, sel, q_ppm, n_q, flags);
+  if (!h) return SA_ENOMEM;
+  // the outputs in tiles of at most kLatTileRows rows of sums (one tile's
+  // sums, then its counts and bins, tile after tile on the engine stream)
+  const uint32_t tile = (uint32_t)std::min<uint64_t>(n_out, std::max<uint64_t>(1, kLatTileRows / S));
+  hipStream_t s = e->stream;
+  if (int rc = latency_buffers(e, S, (uint64_t)tile * S, (uint64_t)n_out * S, n_q)) return rc;
+  const sa_engine::Latency &L = e->lat;
+  // (queued after everything that can fail without a wait: the copy reads the pageable `sel`
+  // asynchronously, and latency_collect waits for `s`, whatever st says, before sel goes)
+  hipError_t st = hipMemcpyAsync(L.sel, sel.data(), (size_t)S * 4, hipMemcpyHostToDevice, s);
+  for (uint32_t o0 = 0; o0 < n_out && st == hipSuccess; o0 += tile) {
+    const uint32_t n_o = std::min(tile, n_out - o0);
+    st = sa::launch_lat_sums(L.ring, e->cfg.n_services, e->cfg.n_windows, L.sel, S, first - width + 1 + o0, width, n_o,
+                             L.sums, s);
+    if (st == hipSuccess) st = latency_scan_on(e, L.sums, (uint64_t)o0 * S, (uint64_t)n_o * S, h.get(), s);
+  }
+  return latency_collect(e, st, h, s, out);
+}
+
+void sa_latency_result_free(sa_latency_result *r) { delete reinterpret_cast<latency_holder *>(r); }
+
 int sa_window_advance(sa_engine *e, uint64_t new_base) {
   if (!e) return SA_EINVAL;
   if (new_base < e->win_base) return fail(e, SA_EINVAL, "window base cannot move backwards");
@@ -977,6 +1168,10 @@ int sa_window_advance(sa_engine *e, uint64_t new_base) {
     SA_HIP(e, hipMemsetAsync(e->cms + ws * e->cms_slot_elems, 0, e->cms_slot_elems * 8, e->stream));
     if (int rc = fold_errslab(e, ws, e->stream)) return rc;  // clears the slab cells
     SA_HIP(e, hipMemsetAsync(e->errcnt + ws * e->cap, 0, e->cap * 8, e->stream));
+    if (e->lat.ring) {  // the window's latency histograms
+      const size_t per = (size_t)e->cfg.n_services * SA_LAT_BINS;
+      SA_HIP(e, hipMemsetAsync(e->lat.ring + ws * per, 0, per * 8, e->stream));
+    }
   }
   e->win_base = new_base;
   return SA_OK;

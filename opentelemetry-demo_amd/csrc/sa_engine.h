@@ -230,6 +230,20 @@ struct sa_engine {
     uint32_t *map = nullptr, *hist = nullptr, *pair_hist = nullptr;
     uint8_t *regs = nullptr;
   } overlap;
+  // SA_OPT_WINDOW_LATENCY (spanagg_latency.hip; nullptr without the option):
+  // ring [n_windows][n_services][SA_LAT_BINS] u64, the ring slots the ingest
+  // kernel holds in LDS (0: the HBM form) and its largest grid; and sa_window_latency's
+  // scratch, grown by the calls that need more: the selection [sel_cap], one
+  // tile of sliding sums [sums_cap rows][SA_LAT_BINS], every row's count
+  // [row_cap] and quantile bins [row_cap][SA_LAT_MAX_Q]
+  struct Latency {
+    unsigned long long *ring = nullptr;
+    uint32_t k_slots = 0, grid_max = 0;
+    uint32_t *sel = nullptr;
+    unsigned long long *sums = nullptr, *count = nullptr;
+    uint8_t *q_bin = nullptr;
+    uint64_t sel_cap = 0, sums_cap = 0, row_cap = 0, qbin_cap = 0;
+  } lat;
   // sa_ingest: two pinned host slots and their HBM copies; a slot is refilled
   // once its event (H2D copy + aggregation of the previous use) has passed
   struct HostStage {

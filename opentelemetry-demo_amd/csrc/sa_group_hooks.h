@@ -57,6 +57,27 @@ int window_overlap_export_async(sa_engine *e, uint64_t first, uint64_t last, uin
 // and the estimates.  sel: overlap_select's.
 int window_overlap_finish(sa_engine *e, uint64_t first, uint64_t last, const uint8_t *d_hll,
                           const std::vector<uint32_t> &sel, hipStream_t s, sa_overlap_result **out);
+// sa_window_latency's argument rules for an engine of n_services services:
+// *sel = the ids in the caller's order (services == nullptr with n_sel == 0:
+// every id).  nullptr when valid, else what is wrong (SA_EINVAL).
+const char *latency_args(uint32_t n_services, const uint32_t *services, uint32_t n_sel, const uint32_t *q_ppm,
+                         uint32_t n_q, uint32_t flags, std::vector<uint32_t> *sel);
+// its size rule, once the span is known to be resident: n_out * n_sel <= 2^20
+// (2^16 with SA_LAT_HIST).  nullptr when valid.
+const char *latency_rows(uint64_t n_out, uint64_t n_sel, uint32_t flags);
+// sa_window_latency's sums stage for one member, without the wait: d_sums
+// [n_out][sel.size()][SA_LAT_BINS] = the rows of the selected services summed
+// over each output's windows, on `s`.  sel (latency_args') must stay until `s`
+// has been waited for.  SA_ESTATE without the option, SA_ERANGE as
+// sa_window_latency.
+int window_latency_export_async(sa_engine *e, uint64_t first, uint64_t last, uint32_t width,
+                                const std::vector<uint32_t> &sel, uint64_t *d_sums, hipStream_t s);
+// the rest of a group's latency query, on member 0 (`e`, whose device holds
+// the members' summed d_sums) and on `s`: the counts and quantile bins, the
+// copies, the wait and the bins' bounds.
+int window_latency_finish(sa_engine *e, uint64_t first, uint64_t last, uint32_t width, const std::vector<uint32_t> &sel,
+                          const uint32_t *q_ppm, uint32_t n_q, uint32_t flags, const uint64_t *d_sums, hipStream_t s,
+                          sa_latency_result **out);
 // What one engine's heavy-hitter scan leaves on the host once its stream
 // passes the copies: head = the matches, the resident keys, the largest
 // estimate, error_spans; rows [k] = (estimate, key) pairs, the first

@@ -508,6 +508,39 @@ hipError_t launch_movers(const unsigned long long *gkeys, uint64_t cap, uint64_t
                          const unsigned long long *cur, uint32_t d, uint32_t w, uint32_t shift, const uint64_t *seeds,
                          uint64_t nb, uint64_t nc, uint32_t fall, uint32_t k, unsigned long long min_score,
                          ulonglong2 *cand, TopCtl *T, MoversOut *O, hipStream_t s);
+// latency histograms over the window ring (spanagg_latency.hip; DESIGN.md
+// section 4, "Latency histograms over the window ring"): ring [n_windows]
+// [n_services][SA_LAT_BINS] u64.  Up to kLatLdsServices services a workgroup
+// of the ingest kernel counts k_slots consecutive ring slots in dynamic LDS
+// (1 KiB a service and slot); above, every span adds to the ring (k_slots 0).
+// One workgroup of the LDS form a CU: its scalar registers (the launch
+// parameters) leave room for 6 or 7 waves a SIMD, two 1,024-thread workgroups
+// need 8; so it takes the slots that fit in 159 KiB of the CU's 160.  The HBM
+// form has room for two.
+constexpr uint32_t kLatLdsServices = 128;
+struct LatGeom {
+  uint32_t k_slots, per_cu;
+};
+inline LatGeom lat_geometry(uint32_t n_services, uint32_t n_windows) {
+  if (n_services > kLatLdsServices) return {0, 2};
+  const uint32_t fit = 159 / n_services;
+  return {fit < n_windows ? fit : n_windows, 1};
+}
+hipError_t prepare_lat_ingest(size_t lds_bytes);
+// One pass over P's start, end and meta columns beside the launch's ingest
+// kernel (P: that kernel's parameters -- the same window fields, so both make
+// the same in-ring decision): `grid` workgroups of `chunk` spans each (a
+// multiple of 4, below 2^32).  k_slots: lat_geometry's, 0 = the HBM form.
+hipError_t launch_lat_ingest(const IngestParams &P, unsigned long long *ring, uint32_t grid, uint64_t chunk,
+                             uint32_t k_slots, hipStream_t s);
+// sums [n_out][n_sel][SA_LAT_BINS]: output o = the rows of service sel[i]
+// (device) summed over windows a + o .. a + o + width - 1
+hipError_t launch_lat_sums(const unsigned long long *ring, uint32_t n_services, uint32_t n_windows, const uint32_t *sel,
+                           uint32_t n_sel, uint64_t a, uint32_t width, uint32_t n_out, unsigned long long *sums,
+                           hipStream_t s);
+// count [n_rows] and q_bin [n_rows][n_q] of sums [n_rows][SA_LAT_BINS]; q_ppm: host, n_q <= SA_LAT_MAX_Q
+hipError_t launch_lat_scan(const unsigned long long *sums, uint64_t n_rows, const uint32_t *q_ppm, uint32_t n_q,
+                           unsigned long long *count, uint8_t *q_bin, hipStream_t s);
 // sorted union of series ids on the device (spanagg_union.hip): out = the
 // distinct non-zero ids of in[0..n) ascending, *d_total (device u32) their
 // count; scratch >= key_union_scratch_bytes(n); big_scratch / big_bytes: a

@@ -186,6 +186,29 @@ struct overlap_holder {
   }
 };
 
+struct latency_holder {
+  sa_latency_result r;
+  std::vector<uint32_t> services, q_ppm;
+  std::vector<uint64_t> count, q_ns, hist;
+  std::vector<uint8_t> q_bin;
+  // the columns sized for outputs first..last of the selection sel and n_q quantiles (hist: with
+  // SA_LAT_HIST), and r pointing at them
+  __attribute__((visibility("hidden"))) void shape(uint64_t first, uint64_t last, uint32_t width,
+                                                   const std::vector<uint32_t> &sel, const uint32_t *ppm, uint32_t n_q,
+                                                   uint32_t flags) {
+    const size_t n_out = (size_t)(last - first + 1), rows = n_out * sel.size();
+    services = sel;
+    q_ppm.assign(ppm, ppm + n_q);
+    count.resize(rows), q_bin.resize(rows * n_q), q_ns.resize(rows * n_q);
+    if (flags & SA_LAT_HIST) hist.resize(rows * SA_LAT_BINS);
+    r.first_window = first, r.last_window = last, r.width = width, r.n_out = (uint32_t)n_out;
+    r.n_sel = (uint32_t)sel.size(), r.n_q = n_q;
+    r.services = services.data(), r.q_ppm = q_ppm.data(), r.count = count.data();
+    r.q_bin = q_bin.data(), r.q_ns = q_ns.data();
+    r.hist = (flags & SA_LAT_HIST) ? hist.data() : nullptr;
+  }
+};
+
 struct sketch_holder {
   sa_sketch_result r;
   std::vector<uint8_t> hll;

@@ -313,6 +313,7 @@ struct sa_group {
   std::vector<ncclComm_t> comm;
   std::vector<Buf> keys, gath, uni, rows, hll, cms;
   std::vector<Buf> cms_base;  // sa_group_window_movers: the baseline range's cells beside cms (the current range's)
+  std::vector<Buf> lat;       // sa_group_window_latency: every member's sliding sums [n_out][n_sel][SA_LAT_BINS]
   std::vector<Buf> srt, ucnt;  // device key union (sa::key_union): its scratch and the distinct count
   std::vector<uint64_t *> big;  // key_union's scratch for oversized buckets (per member)
   std::vector<size_t> big_bytes;
@@ -536,6 +537,7 @@ int sa_group_create(const sa_config *cfg, const int32_t *devices, uint32_t n, sa
   g->hll.resize(n);
   g->cms.resize(n);
   g->cms_base.resize(n);
+  g->lat.resize(n);
   g->dropped_seen.assign(n, 0);
   g->pcnt.resize(2 * n);
   g->hcol.resize(n);
@@ -587,7 +589,7 @@ void sa_group_destroy(sa_group *g) {
       (void)hipStreamSynchronize(g->st[i]);
       (void)hipStreamDestroy(g->st[i]);
     }
-    for (std::vector<Buf> *v : {&g->keys, &g->gath, &g->uni, &g->rows, &g->hll, &g->cms, &g->cms_base, &g->srt, &g->ucnt})
+    for (std::vector<Buf> *v : {&g->keys, &g->gath, &g->uni, &g->rows, &g->hll, &g->cms, &g->cms_base, &g->lat, &g->srt, &g->ucnt})
       if (i < v->size() && (*v)[i].p) (void)hipFree((*v)[i].p);
     if (i < g->big.size() && g->big[i]) (void)hipFree(g->big[i]);
     for (size_t k = 0; k < 2; ++k)
@@ -1277,6 +1279,61 @@ int sa_group_window_overlap(sa_group *g, uint64_t first, uint64_t last, const ui
     sa_overlap_result_free(*out);
     *out = nullptr;
     return gfail(g, SA_EDEVICE, std::string("window overlap: ") + hipGetErrorString(st));
+  }
+  return SA_OK;
+}
+
+// Each member takes the sliding sums of its own ring for the selected
+// services, the transport adds the members' sums -- as it adds count-min cells
+// -- and member 0's device takes the counts and the quantile bins.
+int sa_group_window_latency(sa_group *g, uint64_t first, uint64_t last, uint32_t width, const uint32_t *services,
+                            uint32_t n_sel, const uint32_t *q_ppm, uint32_t n_q, uint32_t flags,
+                            sa_latency_result **out) {
+  if (!g || !out) return SA_EINVAL;
+  *out = nullptr;
+  if (!(g->cfg.options & SA_OPT_WINDOW_LATENCY))
+    return gfail(g, SA_ESTATE, "window latency: the group was not created with SA_OPT_WINDOW_LATENCY");
+  std::vector<uint32_t> sel;
+  if (const char *bad = sa_grp::latency_args(g->cfg.n_services, services, n_sel, q_ppm, n_q, flags, &sel))
+    return gfail(g, SA_EINVAL, bad);
+  // (the members check the span against their rings; a span that passes has n_out <= n_windows)
+  if (first <= last && last - first < g->cfg.n_windows)
+    if (const char *bad = sa_grp::latency_rows(last - first + 1, sel.size(), flags)) return gfail(g, SA_EINVAL, bad);
+  const uint32_t n = (uint32_t)g->eng.size();
+  const uint64_t elems = first <= last && last - first < g->cfg.n_windows ? (last - first + 1) * sel.size() * SA_LAT_BINS : 1;
+  for (uint32_t i = 0; i < n; ++i)  // (before any member reads `sel`: nothing below returns without a wait)
+    if (int rc = ensure(g, g->dev[i], g->lat[i], elems * 8)) return rc;
+  int rc = SA_OK;
+  uint32_t at = 0;  // the member rc is about
+  for (; at < n && rc == SA_OK; ++at)
+    rc = sa_grp::window_latency_export_async(g->eng[at], first, last, width, sel, static_cast<uint64_t *>(g->lat[at].p),
+                                             g->st[at]);
+  at -= 1;
+  auto merge = [&]() -> int {
+    if (g->rccl) {
+      SG_NCCL(g, ncclGroupStart());
+      for (uint32_t i = 0; i < n; ++i)
+        SG_NCCL(g, ncclAllReduce(g->lat[i].p, g->lat[i].p, elems, ncclUint64, ncclSum, g->comm[i], g->st[i]));
+      SG_NCCL(g, ncclGroupEnd());
+      return SA_OK;
+    }
+    return copy_reduce(g, g->lat, elems, false);
+  };
+  const int merged = rc == SA_OK ? merge() : SA_OK;
+  if (rc == SA_OK && merged == SA_OK) {
+    at = 0;
+    rc = sa_grp::window_latency_finish(g->eng[0], first, last, width, sel, q_ppm, n_q, flags,
+                                       static_cast<const uint64_t *>(g->lat[0].p), g->st[0], out);
+  }
+  // every member's stream, also after a failure: the copies out of `sel` may be
+  // in flight, and an all-reduce ends on every member's stream
+  const hipError_t st = wait_members(g);
+  if (rc) return member_error(g, at, rc, "window latency");
+  if (merged) return merged;
+  if (st != hipSuccess) {
+    sa_latency_result_free(*out);
+    *out = nullptr;
+    return gfail(g, SA_EDEVICE, std::string("window latency: ") + hipGetErrorString(st));
   }
   return SA_OK;
 }

@@ -23,6 +23,8 @@ OPT_NO_HLL_FILTER, OPT_PARTITIONED, OPT_ATOMIC_TABLE, OPT_EXPO_HBM, OPT_EXPO_CAC
 OPT_IDENTITY_IDS, OPT_STAMPS, OPT_GROUP_COPY, OPT_GROUP_RCCL = 32, 64, 128, 256
 # the key_hash column carries dense series indices (spanagg.dense.DenseIds, Engine.bind_ids)
 OPT_DENSE_IDS = 512
+# per window and service a 256-bin histogram of durations beside every ingest path (Engine.window_latency)
+OPT_WINDOW_LATENCY = 1024
 STATUS_NAMES = {
     SA_OK: "SA_OK", SA_EINVAL: "SA_EINVAL", SA_ENOMEM: "SA_ENOMEM", SA_EDEVICE: "SA_EDEVICE",
     SA_EFULL: "SA_EFULL", SA_ERANGE: "SA_ERANGE", SA_ESTATE: "SA_ESTATE",
@@ -133,6 +135,19 @@ class sa_overlap_result(C.Structure):
     ]
 
 
+SA_LAT_BINS = LAT_BINS = 256
+SA_LAT_MAX_Q = LAT_MAX_Q = 8
+SA_LAT_HIST = 1
+
+
+class sa_latency_result(C.Structure):
+    _fields_ = [
+        ("first_window", C.c_uint64), ("last_window", C.c_uint64), ("width", C.c_uint32), ("n_out", C.c_uint32),
+        ("n_sel", C.c_uint32), ("n_q", C.c_uint32), ("services", u32p), ("q_ppm", u32p), ("count", u64p),
+        ("q_bin", u8p), ("q_ns", u64p), ("hist", u64p),
+    ]
+
+
 class sa_stats(C.Structure):
     _fields_ = [
         ("spans", C.c_uint64), ("zero_key", C.c_uint64), ("invalid_service", C.c_uint64),
@@ -210,6 +225,13 @@ SIGNATURES = [
     ("sa_group_window_overlap", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, u32p, C.c_uint32, C.c_uint32,
                                           C.POINTER(C.POINTER(sa_overlap_result))]),
     ("sa_overlap_result_free", None, [C.POINTER(sa_overlap_result)]),
+    ("sa_window_latency", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, u32p, C.c_uint32, u32p, C.c_uint32,
+                                    C.c_uint32, C.POINTER(C.POINTER(sa_latency_result))]),
+    ("sa_group_window_latency", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, u32p, C.c_uint32, u32p,
+                                          C.c_uint32, C.c_uint32, C.POINTER(C.POINTER(sa_latency_result))]),
+    ("sa_latency_result_free", None, [C.POINTER(sa_latency_result)]),
+    ("sa_latency_bin", C.c_uint32, [C.c_uint64]),
+    ("sa_latency_bin_bounds", C.c_int, [C.c_uint32, u64p, u64p]),
     ("sa_hll_estimate_hist", C.c_double, [u32p, C.c_uint32]),
     ("sa_get_stats", C.c_int, [C.c_void_p, C.POINTER(sa_stats)]),
     ("sa_bind_ids", C.c_int, [C.c_void_p, u64p, u64p, C.c_uint64]),

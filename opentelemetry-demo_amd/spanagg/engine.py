@@ -252,6 +252,23 @@ class OverlapResult:
         return [(int(self.services[i]), int(self.services[j]), float(self.shared[i, j])) for i, j in pairs[:k]]
 
 
+@dataclass
+class LatencyResult:
+    """sa_latency_result: per output window and selected service the spans of
+    the covered windows and, for each quantile, the histogram bin that holds it
+    and that bin's upper bound in ns -- an upper bound on the true quantile,
+    within 12.5 % (127 ns below 2,048 ns)."""
+    first: int
+    last: int
+    width: int
+    services: np.ndarray          # [n_sel] u32 service ids, in the caller's order
+    q_ppm: np.ndarray             # [n_q] u32: round(quantile * 1e6)
+    count: np.ndarray             # [n_out, n_sel] u64
+    q_bin: np.ndarray             # [n_out, n_sel, n_q] u8
+    q_ns: np.ndarray              # [n_out, n_sel, n_q] u64: sketch.latency_bin_bounds(q_bin)[1]; 0 where count == 0
+    hist: Optional[np.ndarray]    # [n_out, n_sel, 256] u64 summed bins (hist=True), else None
+
+
 def hll_estimate(regs: np.ndarray, p: int) -> float:
     lib = _lib.load()
     r = np.ascontiguousarray(regs, dtype=np.uint8)
@@ -405,6 +422,30 @@ def _window_overlap(obj, fn, what, first, last, services) -> OverlapResult:
             union, shared, int(r.hll_p))
     finally:
         obj.lib.sa_overlap_result_free(out)
+
+
+def _window_latency(obj, fn, what, first, last, width, services, quantiles, hist) -> LatencyResult:
+    """sa_window_latency / sa_group_window_latency -> LatencyResult (copies), freeing the library's result."""
+    sv = None if services is None else np.ascontiguousarray(services, dtype=np.uint32).reshape(-1)
+    ppm = np.ascontiguousarray([int(round(float(q) * 1e6)) for q in quantiles], dtype=np.uint32)
+    out = C.POINTER(_lib.sa_latency_result)()
+    obj._check(fn(obj._h, int(first), int(last), int(width), None if sv is None else sv.ctypes.data_as(_lib.u32p),
+                  0 if sv is None else len(sv), ppm.ctypes.data_as(_lib.u32p), len(ppm),
+                  _lib.SA_LAT_HIST if hist else 0, C.byref(out)), what)
+    try:
+        r = out.contents
+        n, S, Q = int(r.n_out), int(r.n_sel), int(r.n_q)
+        return LatencyResult(
+            int(r.first_window), int(r.last_window), int(r.width),
+            np.ctypeslib.as_array(r.services, shape=(S,)).copy(), np.ctypeslib.as_array(r.q_ppm, shape=(Q,)).copy(),
+            np.ctypeslib.as_array(r.count, shape=(n, S)).copy(), np.ctypeslib.as_array(r.q_bin, shape=(n, S, Q)).copy(),
+            np.ctypeslib.as_array(r.q_ns, shape=(n, S, Q)).copy(),
+            np.ctypeslib.as_array(r.hist, shape=(n, S, _lib.SA_LAT_BINS)).copy() if r.hist else None)
+    finally:
+        obj.lib.sa_latency_result_free(out)
+
+
+_QUANTILES = (0.5, 0.95, 0.99)
 
 
 def _ptr(x) -> int:
@@ -613,6 +654,22 @@ class Engine:
         device."""
         return _window_overlap(self, self.lib.sa_window_overlap, "sa_window_overlap", first, last, services)
 
+    def window_latency(self, first: int, last: int, services=None, quantiles=_QUANTILES,
+                       hist: bool = False) -> LatencyResult:
+        """sa_window_latency as a range query (OPT_WINDOW_LATENCY engines): one
+        output over the windows first..last -- per service of `services` (ids;
+        None: every service) the spans counted there and each quantile's
+        histogram bin and upper bound in ns.  hist: also the summed bins."""
+        return _window_latency(self, self.lib.sa_window_latency, "sa_window_latency", last, last, last - first + 1,
+                               services, quantiles, hist)
+
+    def window_latency_series(self, first: int, last: int, width: int = 1, services=None, quantiles=_QUANTILES,
+                              hist: bool = False) -> LatencyResult:
+        """sa_window_latency: for every window t of first..last the answers of
+        window_latency(t - width + 1, t), from sliding sums on the device."""
+        return _window_latency(self, self.lib.sa_window_latency, "sa_window_latency", first, last, width, services,
+                               quantiles, hist)
+
     def flush_exp(self, allow_drops: bool = False) -> ExpoResult:
         out = C.POINTER(_lib.sa_exp_result)()
         rc = self.lib.sa_flush_exp(self._h, C.byref(out))
@@ -801,6 +858,20 @@ class Group:
         """sa_group_window_overlap: Engine.window_overlap over the members' merge."""
         return _window_overlap(self, self.lib.sa_group_window_overlap, "sa_group_window_overlap", first, last,
                                services)
+
+    def window_latency(self, first: int, last: int, services=None, quantiles=_QUANTILES,
+                       hist: bool = False) -> LatencyResult:
+        """sa_group_window_latency as a range query: Engine.window_latency
+        over the members' summed histograms."""
+        return _window_latency(self, self.lib.sa_group_window_latency, "sa_group_window_latency", last, last,
+                               last - first + 1, services, quantiles, hist)
+
+    def window_latency_series(self, first: int, last: int, width: int = 1, services=None, quantiles=_QUANTILES,
+                              hist: bool = False) -> LatencyResult:
+        """sa_group_window_latency: Engine.window_latency_series over the
+        members' summed histograms."""
+        return _window_latency(self, self.lib.sa_group_window_latency, "sa_group_window_latency", first, last, width,
+                               services, quantiles, hist)
 
     def window_advance(self, new_base: int):
         self._check(self.lib.sa_group_window_advance(self._h, int(new_base)), "sa_group_window_advance")

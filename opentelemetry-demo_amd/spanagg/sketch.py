@@ -60,6 +60,45 @@ def distinct_traces(hll: np.ndarray, p: int) -> np.ndarray:
     return np.array([hll_estimate(hll[s], p) for s in range(hll.shape[0])])
 
 
+LAT_BINS = 256
+
+
+def latency_bin(d_ns: int) -> int:
+    """The latency histogram's bin of a duration in ns (include/spanagg.h,
+    sa_latency_bin): bins 0..15 are 128 ns wide; from 2,048 ns up eight bins an
+    octave; bin 255 has no upper bound."""
+    q = int(d_ns) >> 7
+    if q < 16:
+        return q
+    e = q.bit_length() - 1
+    return min(LAT_BINS - 1, ((e - 3) << 3) + (q >> (e - 3)))
+
+
+def latency_bin_bounds(b: int):
+    """(lo, hi) of bin b in ns, inclusive (sa_latency_bin_bounds); hi of bin 255 is 2^64 - 1."""
+    if not 0 <= b < LAT_BINS:
+        raise ValueError("latency_bin_bounds: a bin in 0..255")
+    if b < 16:
+        return b << 7, (b << 7) + 127
+    e, m = (b >> 3) + 2, b & 7
+    return ((8 + m) << (e - 3)) << 7, M64 if b == LAT_BINS - 1 else (((9 + m) << (e - 3)) << 7) - 1
+
+
+def latency_quantile_bin(hist, q_ppm: int) -> int:
+    """The smallest bin whose cumulative count reaches r = max(1, ceil(count *
+    q_ppm / 10^6)) -- sa_latency_result.q_bin; 0 for an empty histogram."""
+    count = sum(int(c) for c in hist)
+    if count == 0:
+        return 0
+    r = max(1, -(-count * int(q_ppm) // 1_000_000))
+    run = 0
+    for b, c in enumerate(hist):
+        run += int(c)
+        if run >= r:
+            return b
+    raise AssertionError("unreachable: r <= count")
+
+
 def anomalous(series: Sequence[float], factor: float, min_base: float = 1.0) -> list:
     """Indices whose value exceeds `factor` x the series median (floor min_base)."""
     x = np.asarray(series, dtype=np.float64)
