@@ -23,6 +23,7 @@
  *   (new) traces shared by pairs of services        sa_window_overlap (pairwise register maxima on the device)
  *   (new) series whose ERROR rate changed most      sa_window_movers (key table against two ranges' cells on the device)
  *   (new) duration quantiles per service and window sa_window_latency (log-linear histograms in the ring, SA_OPT_WINDOW_LATENCY)
+ *   (new) services whose latency shifted most       sa_window_latency_movers (two ranges' histograms summed, scored and selected on the device)
  *
  * Boundary rules (mirroring the connector's contracts):
  *  - Ownership: batches are borrowed for the duration of the call (page-locked
@@ -592,6 +593,70 @@ int sa_window_latency(sa_engine *e, uint64_t first, uint64_t last, uint32_t widt
                       sa_latency_result **out);
 void sa_latency_result_free(sa_latency_result *r);
 
+/* ---- latency movers over the window ring (SA_OPT_WINDOW_LATENCY) ----
+ * "Which services got slower": every service is a candidate, and each is held
+ * against its own duration histograms summed over two ranges -- a baseline and
+ * a current one -- in one pass over the ring; the shift of the ranking
+ * quantile's bin is the score.  No state beyond sa_window_latency's. */
+#define SA_LATMOV_FALL 1u            /* rank by the fall (speed-ups) instead of the rise */
+typedef struct {
+    uint64_t base_first, base_last, cur_first, cur_last;  /* inclusive */
+    uint32_t k, n;                   /* asked for; returned (n <= k) */
+    uint32_t n_q, flags;
+    uint64_t n_services;             /* the candidates: every service id 0 .. n_services-1 */
+    uint64_t n_eligible;             /* services with count_base >= mc and count_cur >= mc, mc = max(min_count, 1) */
+    uint64_t n_matched;              /* eligible services with shift >= max(min_shift, 1) */
+    uint64_t spans_base, spans_cur;  /* every service's count summed over each range, exact */
+    const uint32_t *q_ppm;           /* [n_q] as given; q_ppm[0] is the ranking quantile */
+    const uint32_t *services;        /* [n] */
+    const int32_t  *shift;           /* [n] */
+    const uint64_t *count_base, *count_cur;   /* [n] */
+    const uint8_t  *q_bin_base, *q_bin_cur;   /* [n][n_q] */
+    const uint64_t *q_ns_base,  *q_ns_cur;    /* [n][n_q] */
+} sa_latency_movers_result;
+
+/* Sums: for every service, Hb is its SA_LAT_BINS-bin rows summed over windows
+ * base_first..base_last and Hc the same over cur_first..cur_last -- range
+ * sums: the quantile of a sum is not a mean of per-window quantiles --
+ * count_base = sum Hb and count_cur = sum Hc.
+ * Bins: q_bin_*[i][j] is the smallest bin whose cumulative count reaches
+ * max(1, ceil(count * q_ppm[j] / 10^6)) -- exactly sa_window_latency's rule --
+ * and q_ns_* that bin's upper bound from sa_latency_bin_bounds.
+ * Shift: shift = q_bin_cur[..][0] - q_bin_base[..][0], the sign flipped under
+ * SA_LATMOV_FALL, so a returned shift is always >= 1.  From 2,048 ns up 8 bins
+ * are a factor of two; below, a bin is 128 ns.  min_shift above 255 matches
+ * nothing.
+ * Consistency with sa_window_latency: a row's count_base, q_bin_base and
+ * q_ns_base are bit for bit what sa_window_latency(e, base_last, base_last,
+ * base_last - base_first + 1, &services[i], 1, q_ppm, n_q, 0, ..) returns, and
+ * the same holds for cur.
+ * Order: the n_matched services -- the eligible ones (count_base >= mc and
+ * count_cur >= mc, mc = max(min_count, 1)) with shift >= max(min_shift, 1) --
+ * sorted by shift descending, then count_cur descending (among equally shifted
+ * services the busiest first; for ordering count_cur is clamped at 2^48 - 1),
+ * then service id ascending: a total order.  The first n = min(k, n_matched)
+ * are returned, in that order.  Exact while counts stay below 2^44, as
+ * sa_window_latency.  Service id 0 is an ordinary candidate.
+ * Ranges: independent -- each must be resident; they may overlap, be equal, or
+ * have base after cur.  Equal ranges give n_matched == 0 with n_eligible and
+ * both spans_* filled and equal.
+ * Ordering and waiting as sa_window_movers: joins every launch in flight, runs
+ * on the engine stream, waits once, clears nothing (two calls give equal
+ * bits).  Works on every ingest path: only the latency ring is read.
+ * SA_ESTATE on an engine without SA_OPT_WINDOW_LATENCY; SA_ERANGE for either
+ * range as sa_window_range; SA_EINVAL for a null `out`, k == 0, k >
+ * SA_TOP_MAX_K, n_q == 0 or > SA_LAT_MAX_Q, a null q_ppm, a q_ppm outside
+ * 1..10^6, flag bits other than SA_LATMOV_FALL; SA_ENOMEM when the device
+ * scratch (both ranges' sums, 2 x n_services x 2 KiB, the candidates, 16 B a
+ * service, and the select's state, allocated by the first call) or the result
+ * cannot be allocated.  The engine stays usable after any error.  Free with
+ * sa_latency_movers_result_free. */
+int sa_window_latency_movers(sa_engine *e, uint64_t base_first, uint64_t base_last, uint64_t cur_first,
+                             uint64_t cur_last, uint32_t k, uint64_t min_count, uint32_t min_shift,
+                             const uint32_t *q_ppm, uint32_t n_q, uint32_t flags,
+                             sa_latency_movers_result **out);
+void sa_latency_movers_result_free(sa_latency_movers_result *r);
+
 int sa_get_stats(sa_engine *e, sa_stats *out);
 
 /* ---- multi-GPU merge hooks (device pointers on this engine's device) ----
@@ -715,6 +780,16 @@ int sa_group_window_overlap(sa_group *g, uint64_t first, uint64_t last, const ui
 int sa_group_window_latency(sa_group *g, uint64_t first, uint64_t last, uint32_t width, const uint32_t *services,
                             uint32_t n_sel, const uint32_t *q_ppm, uint32_t n_q, uint32_t flags,
                             sa_latency_result **out);
+/* sa_window_latency_movers of a group: every member sums both ranges of its
+ * own ring on its device, the group's transport adds the members' sums
+ * (histograms are additive over members), and member 0's device scores,
+ * selects and reads the rows.  Results equal those of one engine fed every
+ * span, bit for bit.  Every member's sums of a call take 2 x n_services x 2 KiB
+ * on its device. */
+int sa_group_window_latency_movers(sa_group *g, uint64_t base_first, uint64_t base_last, uint64_t cur_first,
+                                   uint64_t cur_last, uint32_t k, uint64_t min_count, uint32_t min_shift,
+                                   const uint32_t *q_ppm, uint32_t n_q, uint32_t flags,
+                                   sa_latency_movers_result **out);
 /* Counters summed over members (n_keys and table_capacity too; window_base and
  * small_table from member 0). */
 int sa_group_get_stats(sa_group *g, sa_stats *out);

@@ -506,6 +506,45 @@ std::unique_ptr<latency_holder> latency_result(sa_engine *e, uint64_t first, uin
   }
   return h;
 }
+
+// ---- latency movers (sa_window_latency_movers; kernels in spanagg_latency.hip, the select in spanagg_range.hip) ----
+// range: base first, base last, current first, current last
+int latency_movers_ranges(sa_engine *e, const uint64_t range[4]) {
+  for (int i = 0; i < 4; i += 2)
+    if (range[i] > range[i + 1] || !resident(e, range[i]) || !resident(e, range[i + 1]))
+      return fail(e, SA_ERANGE, "window latency movers: first > last or a window of a range is not resident");
+  return SA_OK;
+}
+
+// Both ranges' sums of the engine's own ring [2][n_services][SA_LAT_BINS].
+int latency_movers_sums(sa_engine *e) {
+  sa_engine::Latency &L = e->lat;
+  if (L.mov_sums) return SA_OK;
+  return dalloc(e, L.mov_sums, 2 * (size_t)e->cfg.n_services * SA_LAT_BINS, false,
+                "window latency movers: sum buffer hipMalloc failed");
+}
+
+// What the stages after the sums work in: the counts, the candidates (one a
+// service), the rows, and sa_window_top's control block.
+int latency_movers_buffers(sa_engine *e) {
+  sa_engine::Latency &L = e->lat;
+  const size_t S = e->cfg.n_services;
+  if (!e->top.ctl)
+    if (int rc = dalloc(e, e->top.ctl, 1, false, "window latency movers: control block hipMalloc failed")) return rc;
+  if (!L.mov_counts)
+    if (int rc = dalloc(e, L.mov_counts, 2 * S, false, "window latency movers: count buffer hipMalloc failed")) return rc;
+  if (!L.mov_cand)
+    if (int rc = dalloc(e, L.mov_cand, S, false, "window latency movers: candidate buffer hipMalloc failed")) return rc;
+  if (!L.mov_out)
+    if (int rc = dalloc(e, L.mov_out, 1, false, "window latency movers: row buffer hipMalloc failed")) return rc;
+  return SA_OK;
+}
+
+hipError_t latency_movers_sums_on(sa_engine *e, const uint64_t range[4], unsigned long long *d_sums, hipStream_t s) {
+  return sa::launch_lat_pair_sums(e->lat.ring, e->cfg.n_services, e->cfg.n_windows, range[0],
+                                  (uint32_t)(range[1] - range[0] + 1), range[2], (uint32_t)(range[3] - range[2] + 1),
+                                  d_sums, s);
+}
 }  // namespace
 
 namespace sa_grp {
@@ -567,6 +606,87 @@ int window_latency_finish(sa_engine *e, uint64_t first, uint64_t last, uint32_t 
   if (int rc = latency_buffers(e, 0, 0, rows, n_q)) return rc;
   const hipError_t st = latency_scan_on(e, reinterpret_cast<const unsigned long long *>(d_sums), 0, rows, h.get(), s);
   return latency_collect(e, st, h, s, out);
+}
+
+const char *latency_movers_args(uint32_t k, const uint32_t *q_ppm, uint32_t n_q, uint32_t flags) {
+  if (k == 0 || k > SA_TOP_MAX_K) return "window latency movers: k outside 1..SA_TOP_MAX_K";
+  if (flags & ~SA_LATMOV_FALL) return "window latency movers: unknown flag bits";
+  if (n_q == 0 || n_q > SA_LAT_MAX_Q || !q_ppm) return "window latency movers: n_q outside 1..SA_LAT_MAX_Q or null q_ppm";
+  for (uint32_t i = 0; i < n_q; ++i)
+    if (q_ppm[i] == 0 || q_ppm[i] > 1000000u) return "window latency movers: a q_ppm outside 1..1000000";
+  return nullptr;
+}
+
+int window_latency_movers_export_async(sa_engine *e, const uint64_t range[4], uint64_t *d_sums, hipStream_t s) {
+  if (!e || !d_sums) return SA_EINVAL;
+  if (int rc = latency_enabled(e)) return rc;
+  if (int rc = latency_movers_ranges(e, range)) return rc;
+  if (int rc = begin_read(e)) return rc;
+  if (int rc = hop_to(e, s)) return rc;
+  SA_HIP(e, latency_movers_sums_on(e, range, reinterpret_cast<unsigned long long *>(d_sums), s));
+  return hop_back(e, s);  // (a later launch that writes the ring orders after these reads)
+}
+
+int window_latency_movers_finish(sa_engine *e, const uint64_t range[4], uint32_t k, uint64_t min_count,
+                                 uint32_t min_shift, const uint32_t *q_ppm, uint32_t n_q, uint32_t flags,
+                                 const uint64_t *d_sums, hipStream_t s, sa_latency_movers_result **out) {
+  if (!e || !out || !d_sums) return SA_EINVAL;
+  if (int rc = set_dev(e)) return rc;
+  if (int rc = latency_movers_buffers(e)) return rc;
+  const sa_engine::Latency &L = e->lat;
+  sa::TopCtl *T = e->top.ctl;
+  unsigned long long head[4] = {};
+  std::vector<ulonglong2> sel;
+  std::vector<unsigned char> rows;  // LatMovOut's head and its first k rows
+  try {
+    sel.resize(k);
+    rows.resize(offsetof(sa::LatMovOut, row) + (size_t)k * sizeof(sa::LatMovRow));
+  } catch (const std::bad_alloc &) {
+    return fail(e, SA_ENOMEM, "window latency movers: the rows do not fit in host memory");
+  }
+  // (the scratch is the engine's: after its own earlier use, before its next)
+  if (int rc = hop_to(e, s)) return rc;
+  hipError_t st = sa::launch_lat_movers(reinterpret_cast<const unsigned long long *>(d_sums), e->cfg.n_services, k,
+                                        std::max<uint64_t>(min_count, 1), std::max(min_shift, 1u),
+                                        flags & SA_LATMOV_FALL ? 1u : 0u, q_ppm, n_q, L.mov_counts, L.mov_cand, T,
+                                        L.mov_out, s);
+  if (st == hipSuccess) st = hipMemcpyAsync(head, T, sizeof head, hipMemcpyDeviceToHost, s);
+  if (st == hipSuccess) st = hipMemcpyAsync(sel.data(), T->sel, (size_t)k * 16, hipMemcpyDeviceToHost, s);
+  if (st == hipSuccess) st = hipMemcpyAsync(rows.data(), L.mov_out, rows.size(), hipMemcpyDeviceToHost, s);
+  const hipError_t waited = hipStreamSynchronize(s);  // the call's one wait (also after a failure: copies may be in flight)
+  if (st != hipSuccess || waited != hipSuccess)
+    return fail(e, SA_EDEVICE, std::string("window latency movers: ") + hipGetErrorString(st != hipSuccess ? st : waited));
+  const uint32_t n = (uint32_t)std::min<uint64_t>(k, head[0]);
+  std::unique_ptr<latency_movers_holder> h;
+  try {
+    h.reset(new latency_movers_holder());
+    h->shape(range, k, n, q_ppm, n_q, flags, e->cfg.n_services);
+  } catch (const std::bad_alloc &) {
+    return fail(e, SA_ENOMEM, "window latency movers: the result does not fit in host memory");
+  }
+  // (TopCtl's head: the matches, the eligible services, ..; LatMovOut's: the two ranges' spans)
+  h->r.n_matched = head[0], h->r.n_eligible = head[1];
+  std::memcpy(&h->r.spans_base, rows.data(), 8);
+  std::memcpy(&h->r.spans_cur, rows.data() + 8, 8);
+  for (uint32_t i = 0; i < n; ++i) {
+    sa::LatMovRow row;
+    std::memcpy(&row, rows.data() + offsetof(sa::LatMovOut, row) + (size_t)i * sizeof row, sizeof row);
+    h->services[i] = (uint32_t)sel[i].y;
+    h->shift[i] = (int32_t)(sel[i].x >> 48);
+    h->count_base[i] = row.count[0], h->count_cur[i] = row.count[1];
+    for (uint32_t q = 0; q < n_q; ++q) {
+      uint64_t lo = 0, hi = 0;
+      const size_t at = (size_t)i * n_q + q;
+      h->q_bin_base[at] = row.q_bin[0][q], h->q_bin_cur[at] = row.q_bin[1][q];
+      // (a returned row is eligible: neither count is 0)
+      (void)sa_latency_bin_bounds(row.q_bin[0][q], &lo, &hi);
+      h->q_ns_base[at] = row.count[0] ? hi : 0;
+      (void)sa_latency_bin_bounds(row.q_bin[1][q], &lo, &hi);
+      h->q_ns_cur[at] = row.count[1] ? hi : 0;
+    }
+  }
+  *out = &h.release()->r;
+  return SA_OK;
 }
 
 const char *overlap_select(uint32_t n_services, const uint32_t *services, uint32_t n_sel, std::vector<uint32_t> *sel) {
@@ -1150,6 +1270,26 @@ int sa_window_latency(sa_engine *e, uint64_t first, uint64_t last, uint32_t widt
 }
 
 void sa_latency_result_free(sa_latency_result *r) { delete reinterpret_cast<latency_holder *>(r); }
+
+int sa_window_latency_movers(sa_engine *e, uint64_t base_first, uint64_t base_last, uint64_t cur_first,
+                             uint64_t cur_last, uint32_t k, uint64_t min_count, uint32_t min_shift,
+                             const uint32_t *q_ppm, uint32_t n_q, uint32_t flags, sa_latency_movers_result **out) {
+  if (!e || !out) return SA_EINVAL;
+  *out = nullptr;
+  if (int rc = latency_enabled(e)) return rc;
+  if (const char *bad = sa_grp::latency_movers_args(k, q_ppm, n_q, flags)) return fail(e, SA_EINVAL, bad);
+  const uint64_t range[4] = {base_first, base_last, cur_first, cur_last};
+  if (int rc = latency_movers_ranges(e, range)) return rc;
+  if (int rc = begin_read(e)) return rc;
+  if (int rc = latency_movers_sums(e)) return rc;
+  if (int rc = latency_movers_buffers(e)) return rc;
+  // (the sums, then the stages a group runs on its member 0 after adding the members' sums)
+  SA_HIP(e, latency_movers_sums_on(e, range, e->lat.mov_sums, e->stream));
+  return sa_grp::window_latency_movers_finish(e, range, k, min_count, min_shift, q_ppm, n_q, flags,
+                                              reinterpret_cast<const uint64_t *>(e->lat.mov_sums), e->stream, out);
+}
+
+void sa_latency_movers_result_free(sa_latency_movers_result *r) { delete reinterpret_cast<latency_movers_holder *>(r); }
 
 int sa_window_advance(sa_engine *e, uint64_t new_base) {
   if (!e) return SA_EINVAL;

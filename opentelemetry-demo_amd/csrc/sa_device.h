@@ -546,6 +546,17 @@ __device__ __forceinline__ uint32_t lane_rank(uint64_t mask) {
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
 
+// One returning atomic for the lanes of `m` (a ballot this lane is part of):
+// the wave's first position from *counter, this lane's own behind it.
+__device__ __forceinline__ unsigned long long wave_ticket(unsigned long long *counter, uint64_t m) {
+  const int leader = __builtin_ctzll(m);
+  unsigned long long base = 0;
+  if ((int)(threadIdx.x & 63u) == leader) base = atomicAdd(counter, (unsigned long long)__popcll(m));
+  base = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(base >> 32), leader) << 32) |
+         (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)base, leader);
+  return base + lane_rank(m);
+}
+
 __device__ __forceinline__ void cold_cms_add(uint32_t ws, uint64_t key) {
   SA_CONST const IngestParams &Q = cold_params();
   SA_GLOBAL unsigned long long *row0 = gbl(Q.cms) + (uint64_t)ws * Q.cms_d * Q.cms_w;

@@ -235,7 +235,13 @@ struct sa_engine {
   // kernel holds in LDS (0: the HBM form) and its largest grid; and sa_window_latency's
   // scratch, grown by the calls that need more: the selection [sel_cap], one
   // tile of sliding sums [sums_cap rows][SA_LAT_BINS], every row's count
-  // [row_cap] and quantile bins [row_cap][SA_LAT_MAX_Q]
+  // [row_cap] and quantile bins [row_cap][SA_LAT_MAX_Q].
+  // sa_window_latency_movers (allocated by its first call): both ranges' sums
+  // mov_sums [2][n_services][SA_LAT_BINS], their counts mov_counts [2]
+  // [n_services], the candidates mov_cand [n_services] -- its own: sa_window_top's
+  // buffer holds a table's slots, which can be fewer -- and the rows' counts
+  // and bins mov_out; the select works in sa_window_top's control block
+  // (calls are serialised)
   struct Latency {
     unsigned long long *ring = nullptr;
     uint32_t k_slots = 0, grid_max = 0;
@@ -243,6 +249,9 @@ struct sa_engine {
     unsigned long long *sums = nullptr, *count = nullptr;
     uint8_t *q_bin = nullptr;
     uint64_t sel_cap = 0, sums_cap = 0, row_cap = 0, qbin_cap = 0;
+    unsigned long long *mov_sums = nullptr, *mov_counts = nullptr;
+    ulonglong2 *mov_cand = nullptr;
+    sa::LatMovOut *mov_out = nullptr;
   } lat;
   // sa_ingest: two pinned host slots and their HBM copies; a slot is refilled
   // once its event (H2D copy + aggregation of the previous use) has passed

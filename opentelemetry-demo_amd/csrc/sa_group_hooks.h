@@ -78,6 +78,21 @@ int window_latency_export_async(sa_engine *e, uint64_t first, uint64_t last, uin
 int window_latency_finish(sa_engine *e, uint64_t first, uint64_t last, uint32_t width, const std::vector<uint32_t> &sel,
                           const uint32_t *q_ppm, uint32_t n_q, uint32_t flags, const uint64_t *d_sums, hipStream_t s,
                           sa_latency_result **out);
+// sa_window_latency_movers' argument rules (the ranges apart): nullptr when
+// valid, else what is wrong (SA_EINVAL).
+const char *latency_movers_args(uint32_t k, const uint32_t *q_ppm, uint32_t n_q, uint32_t flags);
+// sa_window_latency_movers' sums stage for one member, without the wait:
+// d_sums [2][n_services][SA_LAT_BINS] = every service's rows summed over
+// range[0]..range[1] (the baseline) and over range[2]..range[3] (the current
+// range), on `s`.  SA_ESTATE without the option, SA_ERANGE as sa_window_range.
+int window_latency_movers_export_async(sa_engine *e, const uint64_t range[4], uint64_t *d_sums, hipStream_t s);
+// the rest of the query, on `e` (a group's member 0, whose device holds the
+// members' summed d_sums) and on `s`: the scores, the select and the sort, the
+// selected rows, the copies, the wait and the bins' bounds.  The arguments
+// (latency_movers_args passed them) and *out as sa_window_latency_movers.
+int window_latency_movers_finish(sa_engine *e, const uint64_t range[4], uint32_t k, uint64_t min_count,
+                                 uint32_t min_shift, const uint32_t *q_ppm, uint32_t n_q, uint32_t flags,
+                                 const uint64_t *d_sums, hipStream_t s, sa_latency_movers_result **out);
 // What one engine's heavy-hitter scan leaves on the host once its stream
 // passes the copies: head = the matches, the resident keys, the largest
 // estimate, error_spans; rows [k] = (estimate, key) pairs, the first

@@ -482,6 +482,14 @@ struct TopCtl {
 hipError_t launch_top(const unsigned long long *gkeys, uint64_t cap, uint64_t kinv, const unsigned long long *cells,
                       uint32_t d, uint32_t w, uint32_t shift, const uint64_t *seeds, uint32_t k,
                       unsigned long long min_count, ulonglong2 *cand, TopCtl *T, hipStream_t s);
+// The select and the sort alone, for a scan of the caller's own: after it left
+// its matches (x: what they are ranked by, y: the key; at most cap of them) in
+// cand and T->n_matched, T->max_est (the largest x) and T->n_resident in a T
+// whose first offsetof(TopCtl, sel) bytes were zeroed before it, T->sel[0 ..
+// min(k, T->n_matched)) = the first k by (x descending, y ascending) and
+// T->error_spans = the sum of cells[0 .. w).  A key of 0 orders like any other.
+hipError_t launch_top_select(const unsigned long long *cells, uint32_t w, uint32_t k, uint64_t cap,
+                             const ulonglong2 *cand, TopCtl *T, hipStream_t s);
 // movers between two ranges' summed cells (sa_window_movers; DESIGN.md section
 // 4, "Movers between two ranges").  kMoversCellsLds: the scan stages both
 // arrays in LDS while together they fit this size -- 128 KiB, two default
@@ -541,6 +549,39 @@ hipError_t launch_lat_sums(const unsigned long long *ring, uint32_t n_services, 
 // count [n_rows] and q_bin [n_rows][n_q] of sums [n_rows][SA_LAT_BINS]; q_ppm: host, n_q <= SA_LAT_MAX_Q
 hipError_t launch_lat_scan(const unsigned long long *sums, uint64_t n_rows, const uint32_t *q_ppm, uint32_t n_q,
                            unsigned long long *count, uint8_t *q_bin, hipStream_t s);
+// latency movers (sa_window_latency_movers; DESIGN.md section 4, "Latency
+// movers over the window ring").  What the call leaves beside TopCtl: the
+// two ranges' span counts, and per selected row (T->sel's order) the two
+// counts and the two ranges' quantile bins, range 0 the baseline (128 KiB;
+// the head and the first k rows are one copy).
+struct LatMovRow {
+  unsigned long long count[2];
+  uint8_t q_bin[2][8];  // (SA_LAT_MAX_Q: asserted in spanagg_latency.hip)
+};
+struct LatMovOut {
+  unsigned long long spans_base, spans_cur;
+  LatMovRow row[kTopSel];
+};
+// The stripes a (range, service) unit's windows are split into for the longer
+// range `len` (1, 2 or a multiple of 4): a power of two, no more than fill
+// about 4,096 waves over the 2 * n_services units, none finer than 8 windows.
+uint32_t lat_pair_stripes(uint32_t n_services, uint32_t len);
+// sums [2][n_services][SA_LAT_BINS]: every service's rows summed over windows
+// first_b .. first_b + len_b - 1 (sums[0]) and first_c .. first_c + len_c - 1
+// (sums[1]), 1 <= len <= n_windows
+hipError_t launch_lat_pair_sums(const unsigned long long *ring, uint32_t n_services, uint32_t n_windows,
+                                uint64_t first_b, uint32_t len_b, uint64_t first_c, uint32_t len_c,
+                                unsigned long long *sums, hipStream_t s);
+// The rest of the query on `s`, from sums [2][n_services][SA_LAT_BINS]: every
+// service scored by q_ppm[0] (min_count >= 1, min_shift >= 1, fall 0 or 1)
+// into counts [2][n_services] and cand [n_services], the select and the sort
+// -- T->sel[0 .. min(k, T->n_matched)) = (score, service) in the call's order,
+// T->n_resident the eligible services -- and O: both ranges' spans and the
+// selected rows' counts and bins of all n_q quantiles (q_ppm: host).  k <= kTopSel.
+hipError_t launch_lat_movers(const unsigned long long *sums, uint32_t n_services, uint32_t k,
+                             unsigned long long min_count, uint32_t min_shift, uint32_t fall, const uint32_t *q_ppm,
+                             uint32_t n_q, unsigned long long *counts, ulonglong2 *cand, TopCtl *T, LatMovOut *O,
+                             hipStream_t s);
 // sorted union of series ids on the device (spanagg_union.hip): out = the
 // distinct non-zero ids of in[0..n) ascending, *d_total (device u32) their
 // count; scratch >= key_union_scratch_bytes(n); big_scratch / big_bytes: a

@@ -209,6 +209,30 @@ struct latency_holder {
   }
 };
 
+struct latency_movers_holder {
+  sa_latency_movers_result r;
+  std::vector<uint32_t> q_ppm, services;
+  std::vector<int32_t> shift;
+  std::vector<uint64_t> count_base, count_cur, q_ns_base, q_ns_cur;
+  std::vector<uint8_t> q_bin_base, q_bin_cur;
+  // the columns sized for n rows of n_q quantiles, and r pointing at them; range: base first, base last,
+  // current first, current last
+  __attribute__((visibility("hidden"))) void shape(const uint64_t range[4], uint32_t k, uint32_t n, const uint32_t *ppm,
+                                                   uint32_t n_q, uint32_t flags, uint64_t n_services) {
+    q_ppm.assign(ppm, ppm + n_q);
+    services.resize(n), shift.resize(n), count_base.resize(n), count_cur.resize(n);
+    q_bin_base.resize((size_t)n * n_q), q_bin_cur.resize((size_t)n * n_q);
+    q_ns_base.resize((size_t)n * n_q), q_ns_cur.resize((size_t)n * n_q);
+    r.base_first = range[0], r.base_last = range[1], r.cur_first = range[2], r.cur_last = range[3];
+    r.k = k, r.n = n, r.n_q = n_q, r.flags = flags;
+    r.n_services = n_services, r.n_eligible = r.n_matched = r.spans_base = r.spans_cur = 0;
+    r.q_ppm = q_ppm.data(), r.services = services.data(), r.shift = shift.data();
+    r.count_base = count_base.data(), r.count_cur = count_cur.data();
+    r.q_bin_base = q_bin_base.data(), r.q_bin_cur = q_bin_cur.data();
+    r.q_ns_base = q_ns_base.data(), r.q_ns_cur = q_ns_cur.data();
+  }
+};
+
 struct sketch_holder {
   sa_sketch_result r;
   std::vector<uint8_t> hll;

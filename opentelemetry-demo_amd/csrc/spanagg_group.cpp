@@ -1338,6 +1338,55 @@ int sa_group_window_latency(sa_group *g, uint64_t first, uint64_t last, uint32_t
   return SA_OK;
 }
 
+// Each member sums both ranges of its own ring, the transport adds the
+// members' sums -- as it adds sa_group_window_latency's -- and member 0's
+// device scores, selects and reads the rows.
+int sa_group_window_latency_movers(sa_group *g, uint64_t base_first, uint64_t base_last, uint64_t cur_first,
+                                   uint64_t cur_last, uint32_t k, uint64_t min_count, uint32_t min_shift,
+                                   const uint32_t *q_ppm, uint32_t n_q, uint32_t flags,
+                                   sa_latency_movers_result **out) {
+  if (!g || !out) return SA_EINVAL;
+  *out = nullptr;
+  if (!(g->cfg.options & SA_OPT_WINDOW_LATENCY))
+    return gfail(g, SA_ESTATE, "window latency movers: the group was not created with SA_OPT_WINDOW_LATENCY");
+  if (const char *bad = sa_grp::latency_movers_args(k, q_ppm, n_q, flags)) return gfail(g, SA_EINVAL, bad);
+  const uint64_t range[4] = {base_first, base_last, cur_first, cur_last};
+  const uint32_t n = (uint32_t)g->eng.size();
+  const uint64_t elems = 2ull * g->cfg.n_services * SA_LAT_BINS;
+  for (uint32_t i = 0; i < n; ++i)
+    if (int rc = ensure(g, g->dev[i], g->lat[i], elems * 8)) return rc;
+  int rc = SA_OK;
+  uint32_t at = 0;  // the member rc is about
+  for (; at < n && rc == SA_OK; ++at)
+    rc = sa_grp::window_latency_movers_export_async(g->eng[at], range, static_cast<uint64_t *>(g->lat[at].p), g->st[at]);
+  at -= 1;
+  auto merge = [&]() -> int {
+    if (g->rccl) {
+      SG_NCCL(g, ncclGroupStart());
+      for (uint32_t i = 0; i < n; ++i)
+        SG_NCCL(g, ncclAllReduce(g->lat[i].p, g->lat[i].p, elems, ncclUint64, ncclSum, g->comm[i], g->st[i]));
+      SG_NCCL(g, ncclGroupEnd());
+      return SA_OK;
+    }
+    return copy_reduce(g, g->lat, elems, false);
+  };
+  const int merged = rc == SA_OK ? merge() : SA_OK;
+  if (rc == SA_OK && merged == SA_OK) {
+    at = 0;
+    rc = sa_grp::window_latency_movers_finish(g->eng[0], range, k, min_count, min_shift, q_ppm, n_q, flags,
+                                              static_cast<const uint64_t *>(g->lat[0].p), g->st[0], out);
+  }
+  const hipError_t st = wait_members(g);  // (also after a failure; an all-reduce ends on every member's stream)
+  if (rc) return member_error(g, at, rc, "window latency movers");
+  if (merged) return merged;
+  if (st != hipSuccess) {
+    sa_latency_movers_result_free(*out);
+    *out = nullptr;
+    return gfail(g, SA_EDEVICE, std::string("window latency movers: ") + hipGetErrorString(st));
+  }
+  return SA_OK;
+}
+
 int sa_group_window_advance(sa_group *g, uint64_t new_base) {
   if (!g) return SA_EINVAL;
   for (uint32_t i = 0; i < g->eng.size(); ++i)

@@ -15,6 +15,12 @@
 //                      subtracted, one wave a (service, chunk of outputs).
 //   lat_scan_kernel    a summed row's count and quantile bins: lane-local
 //                      prefix, wave scan, ballot.
+//   lat_pair_sums_kernel, lat_score_kernel, lat_mov_rows_kernel
+//                      sa_window_latency_movers: two ranges' rows summed per
+//                      service (a long range split over waves), every service
+//                      scored by the shift of its ranking quantile's bin --
+//                      the select and the sort are the heavy hitters' -- and
+//                      the selected services' counts and bins.
 //
 // The two query stages are apart because a group adds its members' sums
 // between them.  Every cell is an integer sum, so the order of the atomics
@@ -30,6 +36,7 @@ namespace sa {
 namespace {
 
 static_assert(kLatBins == SA_LAT_BINS, "one bin count");
+static_assert(sizeof(LatMovRow::q_bin) == 2 * SA_LAT_MAX_Q, "a row's bins hold the most quantiles");
 constexpr uint32_t kLatBlock = 1024;
 constexpr uint32_t kLatNoSlot = 0xFFFFFFFFu;
 constexpr uint32_t kLatQueryBlock = 256;  // four waves: a row (scan) or a (service, chunk) (sums) each
@@ -197,9 +204,43 @@ struct LatQuantiles {
   uint32_t n, ppm[SA_LAT_MAX_Q];
 };
 
+// A wave's view of one row of 256 bins, lane l holding bins 4l .. 4l + 3: p[j] =
+// the lane's own bins 0..j summed, incl / excl = the wave's prefix over the
+// lanes' sums with and without this lane's, total = the row's count (every lane).
+struct LatRowScan {
+  unsigned long long p[4], incl, excl, total;
+};
+__device__ __forceinline__ LatRowScan lat_row_scan(const U64x4 &v, uint32_t lane) {
+  LatRowScan R;
+  R.p[0] = v.v[0], R.p[1] = R.p[0] + v.v[1], R.p[2] = R.p[1] + v.v[2], R.p[3] = R.p[2] + v.v[3];
+  unsigned long long incl = R.p[3];
+#pragma unroll
+  for (uint32_t d = 1; d < 64; d <<= 1) {
+    const unsigned long long t = __shfl_up(incl, d);
+    if (lane >= d) incl += t;
+  }
+  R.incl = incl, R.excl = incl - R.p[3], R.total = __shfl(incl, 63);
+  return R;
+}
+// The quantile rule (every lane of the wave calls it, every lane gets the
+// answer): the smallest bin whose cumulative count reaches r = max(1,
+// ceil(total * ppm / 10^6)) (total * ppm < 2^64 while total < 2^44), 0 for an
+// empty row.
+__device__ __forceinline__ uint32_t lat_quantile_bin(const LatRowScan &R, uint32_t ppm) {
+  unsigned long long rank = (R.total * ppm + 999999ULL) / 1000000ULL;
+  if (rank == 0) rank = 1;
+  const unsigned long long reached = __ballot(R.incl >= rank);
+  const uint32_t j = R.excl + R.p[0] >= rank ? 0u : R.excl + R.p[1] >= rank ? 1u : R.excl + R.p[2] >= rank ? 2u : 3u;
+  uint32_t bin = 0;
+  if (reached) {  // (total >= rank >= 1: some lane reaches it)
+    const uint32_t first = (uint32_t)__ffsll((long long)reached) - 1u;
+    bin = first * 4 + (uint32_t)__shfl((int)j, (int)first);
+  }
+  return bin;
+}
+
 // One wave a row of sums [n_rows][256]: count[row] = the row's total, q_bin[row]
-// [i] = the smallest bin whose cumulative count reaches r = max(1, ceil(count *
-// ppm[i] / 10^6)) (count * ppm < 2^64 while count < 2^44), 0 for an empty row.
+// [i] = lat_quantile_bin of ppm[i].
 __global__ __launch_bounds__(kLatQueryBlock) void lat_scan_kernel(const unsigned long long *__restrict__ sums,
                                                                   uint64_t n_rows, LatQuantiles Q,
                                                                   unsigned long long *__restrict__ count,
@@ -207,27 +248,191 @@ __global__ __launch_bounds__(kLatQueryBlock) void lat_scan_kernel(const unsigned
   const uint32_t lane = threadIdx.x & 63u;
   const uint64_t r = (uint64_t)blockIdx.x * (kLatQueryBlock / 64) + (threadIdx.x >> 6);
   if (r >= n_rows) return;  // (wave-uniform)
-  const U64x4 v = lat_row(sums + (r << 8) + lane * 4);
-  const unsigned long long p0 = v.v[0], p1 = p0 + v.v[1], p2 = p1 + v.v[2], p3 = p2 + v.v[3];
-  unsigned long long incl = p3;
-#pragma unroll
-  for (uint32_t d = 1; d < 64; d <<= 1) {
-    const unsigned long long t = __shfl_up(incl, d);
-    if (lane >= d) incl += t;
-  }
-  const unsigned long long total = __shfl(incl, 63), excl = incl - p3;
-  if (lane == 0) count[r] = total;
+  const LatRowScan R = lat_row_scan(lat_row(sums + (r << 8) + lane * 4), lane);
+  if (lane == 0) count[r] = R.total;
   for (uint32_t i = 0; i < Q.n; ++i) {
-    unsigned long long rank = (total * Q.ppm[i] + 999999ULL) / 1000000ULL;
-    if (rank == 0) rank = 1;
-    const unsigned long long reached = __ballot(incl >= rank);
-    const uint32_t j = excl + p0 >= rank ? 0u : excl + p1 >= rank ? 1u : excl + p2 >= rank ? 2u : 3u;
-    uint32_t bin = 0;
-    if (reached) {  // (total >= rank >= 1: some lane reaches it)
-      const uint32_t first = (uint32_t)__ffsll((long long)reached) - 1u;
-      bin = first * 4 + (uint32_t)__shfl((int)j, (int)first);
-    }
+    const uint32_t bin = lat_quantile_bin(R, Q.ppm[i]);
     if (lane == 0) q_bin[r * Q.n + i] = (uint8_t)bin;
+  }
+}
+
+// ---- latency movers (sa_window_latency_movers): both ranges' rows summed per
+// service, every service scored by the shift of its ranking quantile's bin,
+// the select and the sort the heavy hitters' (spanagg_range.hip), then the
+// selected services' rows ----
+constexpr uint32_t kLatPairBlock = 256;    // four waves: stripes of one unit, or one-stripe units
+constexpr uint32_t kLatPairWaves = 4096;   // the sums split units into stripes up to about this many waves
+constexpr uint32_t kLatStripeRows = 8;     // ... and no finer than this many windows a stripe
+constexpr uint32_t kLatScoreBlock = 1024;  // sixteen waves, a service each at a time: one set of atomics a workgroup
+constexpr uint32_t kLatScoreGrid = 512;    // the score stage's workgroups, while a wave then has no more than ...
+constexpr uint32_t kLatScoreIters = 8;     // ... this many services (65,536 services: exactly both)
+constexpr uint32_t kLatScoreList = kLatScoreBlock / 64 * kLatScoreIters;  // a workgroup's matches in LDS
+
+// Unit u = r * n_services + s is service s over range r (0 the baseline, 1 the
+// current one): windows first[r] .. first[r] + len[r] - 1.  A unit is `stripes`
+// waves (1, 2 or a multiple of 4, so the waves of a workgroup that share a
+// unit are `grp` = min(stripes, 4) neighbours); stripe t sums the t-th run of
+// ceil(len / stripes) consecutive windows of the unit (interleaved stripes
+// took 8 % longer on a 1,024-window ring) -- lane l bins 4l .. 4l + 3, a row
+// one coalesced 2 KiB read, four rows in flight -- and the grp waves add up
+// through LDS.
+// Up to 4 stripes the first wave stores the unit's row of sums [2][n_services]
+// [256]; above, the workgroups of a unit add theirs to the row (zeroed by the
+// launcher) -- integer adds, so neither the split nor the order shows.  The
+// ring index stays below (win_mask + 1) * n_services * 256: s < n_services, and
+// k < len[r] <= win_mask + 1.
+__global__ __launch_bounds__(kLatPairBlock) void lat_pair_sums_kernel(const unsigned long long *__restrict__ ring,
+                                                                      uint32_t n_services, uint32_t win_mask,
+                                                                      uint64_t first_b, uint32_t len_b, uint64_t first_c,
+                                                                      uint32_t len_c, uint32_t stripes, uint32_t grp,
+                                                                      unsigned long long *__restrict__ sums) {
+  __shared__ unsigned long long part[kLatPairBlock / 64][SA_LAT_BINS];
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  const uint64_t gw = (uint64_t)blockIdx.x * (kLatPairBlock / 64) + wv;
+  const uint64_t u = gw / stripes;
+  const uint32_t t = (uint32_t)(gw % stripes);
+  const bool live = u < 2ull * n_services;  // (wave-uniform; a dead wave still meets the barrier)
+  U64x4 acc{{0, 0, 0, 0}};
+  if (live) {
+    const uint32_t r = u >= n_services ? 1u : 0u, s = (uint32_t)(u - (uint64_t)r * n_services);
+    const uint64_t first = r ? first_c : first_b;
+    const uint32_t len = r ? len_c : len_b;
+    const uint64_t at = ((uint64_t)s << 8) + lane * 4;
+    const uint32_t per = (len + stripes - 1) / stripes, k0 = min(len, t * per), k1 = min(len, k0 + per);
+#pragma unroll 4
+    for (uint32_t k = k0; k < k1; ++k) {
+      const U64x4 v = lat_row(ring + ((((first + k) & win_mask) * n_services) << 8) + at);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc.v[j] += v.v[j];
+    }
+  }
+  if (grp > 1) {  // (a launch parameter: every thread takes the same side)
+    const uint32_t lead = wv & ~(grp - 1);
+    if (wv != lead) {
+      ulonglong2 *dst = reinterpret_cast<ulonglong2 *>(&part[wv][lane * 4]);
+      dst[0] = ulonglong2{acc.v[0], acc.v[1]};
+      dst[1] = ulonglong2{acc.v[2], acc.v[3]};
+    }
+    __syncthreads();
+    if (wv != lead) return;
+    for (uint32_t o = 1; o < grp; ++o) {
+      const U64x4 v = lat_row(&part[lead + o][lane * 4]);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc.v[j] += v.v[j];
+    }
+  }
+  if (!live) return;
+  unsigned long long *dst = sums + (u << 8) + lane * 4;
+  if (stripes <= 4) {
+    reinterpret_cast<ulonglong2 *>(dst)[0] = ulonglong2{acc.v[0], acc.v[1]};
+    reinterpret_cast<ulonglong2 *>(dst)[1] = ulonglong2{acc.v[2], acc.v[3]};
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (acc.v[j]) atomicAdd(dst + j, acc.v[j]);
+  }
+}
+
+struct LatMovParams {
+  unsigned long long min_count;  // >= 1
+  uint32_t min_shift;            // >= 1 (above 255: nothing matches)
+  uint32_t fall, ppm0;
+};
+
+// One wave a service s of sums [2][n_services][256] at a time, the waves of the
+// grid striding the services: both counts (into counts [2][n_services]) and
+// both ranking-quantile bins; eligible when both counts reach min_count, shift
+// = cur's bin - base's (negated when fall), a match when eligible with shift
+// >= min_shift.  A match leaves as (score, s), score = (shift << 48) |
+// min(count_cur, 2^48 - 1): ordered as the heavy hitters' pairs -- score
+// descending, then id ascending -- that is (shift, count_cur) descending, then
+// id ascending.  A wave has one candidate at a time, so a workgroup gathers
+// its matches in LDS (at most kLatScoreList: the launcher's grid leaves a wave
+// no more than kLatScoreIters services) and takes one place range in cand
+// [n_services] for all of them (T->n_matched), and one add or max each for
+// T->n_resident (the eligible), T->max_est (the largest score) and
+// O->spans_base and O->spans_cur (the sums of the two counts): 65,536
+// services are 512 workgroups' atomics on those words, not 4,096's.
+__global__ __launch_bounds__(kLatScoreBlock) void lat_score_kernel(const unsigned long long *__restrict__ sums,
+                                                                   uint32_t n_services, LatMovParams M,
+                                                                   unsigned long long *__restrict__ counts,
+                                                                   ulonglong2 *__restrict__ cand, TopCtl *T,
+                                                                   LatMovOut *O) {
+  constexpr uint32_t kWaves = kLatScoreBlock / 64;
+  __shared__ ulonglong2 s_cand[kLatScoreList];
+  __shared__ unsigned long long s_largest[kWaves], s_base[kWaves], s_cur[kWaves];
+  __shared__ uint32_t s_elig[kWaves], s_n;
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  if (threadIdx.x == 0) s_n = 0;
+  __syncthreads();
+  unsigned long long largest = 0, base = 0, cur = 0;  // (the wave's own, the same in every lane)
+  uint32_t ne = 0;
+  for (uint32_t s = blockIdx.x * kWaves + wv; s < n_services; s += gridDim.x * kWaves) {  // (wave-uniform)
+    const LatRowScan B = lat_row_scan(lat_row(sums + ((uint64_t)s << 8) + lane * 4), lane);
+    const LatRowScan C = lat_row_scan(lat_row(sums + (((uint64_t)n_services + s) << 8) + lane * 4), lane);
+    const uint32_t bb = lat_quantile_bin(B, M.ppm0), bc = lat_quantile_bin(C, M.ppm0);
+    base += B.total, cur += C.total;
+    const bool elig = B.total >= M.min_count && C.total >= M.min_count;
+    ne += elig ? 1u : 0u;
+    const int32_t shift = M.fall ? (int32_t)bb - (int32_t)bc : (int32_t)bc - (int32_t)bb;
+    if (lane == 0) counts[s] = B.total, counts[(uint64_t)n_services + s] = C.total;
+    if (elig && shift >= 1 && (uint32_t)shift >= M.min_shift) {
+      const unsigned long long top = (1ULL << 48) - 1;
+      const unsigned long long score = ((unsigned long long)(uint32_t)shift << 48) | (C.total < top ? C.total : top);
+      largest = score > largest ? score : largest;
+      if (lane == 0) {
+        const uint32_t at = atomicAdd(&s_n, 1u);
+        if (at < kLatScoreList) s_cand[at] = ulonglong2{score, (unsigned long long)s};
+      }
+    }
+  }
+  if (lane == 0) s_largest[wv] = largest, s_base[wv] = base, s_cur[wv] = cur, s_elig[wv] = ne;
+  __syncthreads();
+  if (wv) return;
+  const uint32_t n = min(s_n, kLatScoreList);
+  if (n) {
+    unsigned long long pos = 0;
+    if (lane == 0) pos = atomicAdd(&T->n_matched, (unsigned long long)n);
+    pos = __shfl(pos, 0);
+    for (uint32_t i = lane; i < n; i += 64)
+      if (pos + i < n_services) cand[pos + i] = s_cand[i];
+  }
+  const bool mine = lane < kWaves;
+  base = mine ? s_base[lane] : 0, cur = mine ? s_cur[lane] : 0, largest = mine ? s_largest[lane] : 0;
+  ne = mine ? s_elig[lane] : 0;
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) {  // (lanes 0..15 hold everything)
+    const unsigned long long ob = __shfl_xor(base, o), oc = __shfl_xor(cur, o), ol = __shfl_xor(largest, o);
+    base += ob, cur += oc;
+    largest = ol > largest ? ol : largest;
+    ne += __shfl_xor(ne, o);
+  }
+  if (lane == 0) {
+    if (ne) atomicAdd(&T->n_resident, (unsigned long long)ne);
+    if (largest) atomicMax(&T->max_est, largest);
+    if (base) atomicAdd(&O->spans_base, base);
+    if (cur) atomicAdd(&O->spans_cur, cur);
+  }
+}
+
+// After the sort, one wave a row i < T->want of T->sel: the service's two
+// counts and, for both of its summed rows, every quantile's bin -- O->row[i]
+// (the rule lat_scan_kernel applies, on the same sums).
+__global__ __launch_bounds__(kLatQueryBlock) void lat_mov_rows_kernel(const unsigned long long *__restrict__ sums,
+                                                                      uint32_t n_services, LatQuantiles Q,
+                                                                      const TopCtl *T, LatMovOut *O) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t i = blockIdx.x * (kLatQueryBlock / 64) + (threadIdx.x >> 6);
+  if (i >= T->want || i >= kTopSel) return;  // (wave-uniform)
+  const uint64_t s = T->sel[i].y;
+  if (s >= n_services) return;  // (a candidate is a service id: never taken)
+  for (uint32_t r = 0; r < 2; ++r) {
+    const LatRowScan R = lat_row_scan(lat_row(sums + (((uint64_t)r * n_services + s) << 8) + lane * 4), lane);
+    if (lane == 0) O->row[i].count[r] = R.total;
+    for (uint32_t q = 0; q < SA_LAT_MAX_Q; ++q) {  // (the unasked ones 0: the row is copied whole)
+      const uint32_t bin = q < Q.n ? lat_quantile_bin(R, Q.ppm[q]) : 0u;
+      if (lane == 0) O->row[i].q_bin[r][q] = (uint8_t)bin;
+    }
   }
 }
 
@@ -270,6 +475,48 @@ hipError_t launch_lat_scan(const unsigned long long *sums, uint64_t n_rows, cons
   const uint64_t per = kLatQueryBlock / 64;
   hipLaunchKernelGGL(lat_scan_kernel, dim3((uint32_t)((n_rows + per - 1) / per)), dim3(kLatQueryBlock), 0, s, sums,
                      n_rows, Q, count, q_bin);
+  return hipGetLastError();
+}
+
+uint32_t lat_pair_stripes(uint32_t n_services, uint32_t len) {
+  uint32_t stripes = 1;
+  while (2 * stripes * 2ull * n_services <= kLatPairWaves && stripes * kLatStripeRows < len) stripes *= 2;
+  return stripes;
+}
+
+hipError_t launch_lat_pair_sums(const unsigned long long *ring, uint32_t n_services, uint32_t n_windows,
+                                uint64_t first_b, uint32_t len_b, uint64_t first_c, uint32_t len_c,
+                                unsigned long long *sums, hipStream_t s) {
+  const uint32_t stripes = lat_pair_stripes(n_services, std::max(len_b, len_c));
+  const uint64_t waves = 2ull * n_services * stripes, per = kLatPairBlock / 64;
+  if (stripes > 4)  // (the workgroups of a unit add to its row)
+    if (hipError_t e = hipMemsetAsync(sums, 0, 2ull * n_services * SA_LAT_BINS * 8, s); e != hipSuccess) return e;
+  hipLaunchKernelGGL(lat_pair_sums_kernel, dim3((uint32_t)((waves + per - 1) / per)), dim3(kLatPairBlock), 0, s, ring,
+                     n_services, n_windows - 1, first_b, len_b, first_c, len_c, stripes, std::min(stripes, 4u), sums);
+  return hipGetLastError();
+}
+
+hipError_t launch_lat_movers(const unsigned long long *sums, uint32_t n_services, uint32_t k,
+                             unsigned long long min_count, uint32_t min_shift, uint32_t fall, const uint32_t *q_ppm,
+                             uint32_t n_q, unsigned long long *counts, ulonglong2 *cand, TopCtl *T, LatMovOut *O,
+                             hipStream_t s) {
+  LatQuantiles Q{};
+  Q.n = std::min<uint32_t>(n_q, SA_LAT_MAX_Q);
+  for (uint32_t i = 0; i < Q.n; ++i) Q.ppm[i] = q_ppm[i];
+  if (hipError_t e = hipMemsetAsync(T, 0, offsetof(TopCtl, sel), s); e != hipSuccess) return e;
+  if (hipError_t e = hipMemsetAsync(O, 0, offsetof(LatMovOut, row), s); e != hipSuccess) return e;
+  // a service a wave up to kLatScoreGrid workgroups, then several -- no more than a workgroup's list holds
+  const uint32_t per = kLatScoreBlock / 64;
+  const uint32_t score_grid = std::max(std::min((n_services + per - 1) / per, kLatScoreGrid),
+                                       (n_services + kLatScoreList - 1) / kLatScoreList);
+  hipLaunchKernelGGL(lat_score_kernel, dim3(score_grid), dim3(kLatScoreBlock), 0, s, sums, n_services,
+                     LatMovParams{min_count, min_shift, fall, Q.ppm[0]}, counts, cand, T, O);
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  // (no row to sum: the score kernel took both ranges' spans)
+  if (hipError_t e = launch_top_select(counts, 0, k, n_services, cand, T, s); e != hipSuccess) return e;
+  const uint32_t rows_per = kLatQueryBlock / 64;
+  hipLaunchKernelGGL(lat_mov_rows_kernel, dim3((k + rows_per - 1) / rows_per), dim3(kLatQueryBlock), 0, s, sums,
+                     n_services, Q, T, O);
   return hipGetLastError();
 }
 

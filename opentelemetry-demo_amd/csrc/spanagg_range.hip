@@ -435,17 +435,6 @@ __device__ __forceinline__ uint32_t top_digit(unsigned long long est, unsigned l
   return (uint32_t)((level >= 8 ? est >> (8 * (level - 8)) : nkey >> (8 * level)) & 0xFFu);
 }
 
-// One returning atomic for the lanes of `m` (a ballot this lane is part of):
-// the wave's first position from *counter, this lane's own behind it.
-__device__ __forceinline__ unsigned long long wave_ticket(unsigned long long *counter, uint64_t m) {
-  const int leader = __builtin_ctzll(m);
-  unsigned long long base = 0;
-  if ((int)(threadIdx.x & 63u) == leader) base = atomicAdd(counter, (unsigned long long)__popcll(m));
-  base = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(base >> 32), leader) << 32) |
-         (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)base, leader);
-  return base + lane_rank(m);
-}
-
 // Walks gkeys[0..cap) once.  A slot's key is recovered as fold_errcnt_slots
 // does (stored id * kinv; a dense engine's bound hash, 0 when unbound); its
 // estimate is the minimum over the rows of cells [d][w] -- staged in LDS
@@ -756,13 +745,15 @@ static uint32_t top_scan_grid(uint64_t cap) {
 
 // After a scan left its matches in cand [cap] and its counters in T: the row-0
 // sum of cells [..][w] into T->error_spans, then the select and the sort.
-static hipError_t launch_top_select(const unsigned long long *cells, uint32_t w, uint32_t k, uint64_t cap,
-                                    const ulonglong2 *cand, TopCtl *T, hipStream_t s) {
+hipError_t launch_top_select(const unsigned long long *cells, uint32_t w, uint32_t k, uint64_t cap,
+                             const ulonglong2 *cand, TopCtl *T, hipStream_t s) {
   hipLaunchKernelGGL(top_prepare_kernel, dim3(1), dim3(kTopBlock), 0, s, cells, w, k, T);
   // the select's workgroups stride the matches (at most cap); every digit's
-  // launch is enqueued, the device decides which ones work
+  // launch is enqueued, the device decides which ones work -- none does when
+  // the matches cannot outnumber what the sort holds (the prepare kernel sets
+  // T->done), so those launches are left out
   const uint32_t grid = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, (cap + 8 * kTopBlock - 1) / (8 * kTopBlock)), 1024);
-  for (uint32_t digit = 0; digit < kTopDigits; ++digit)
+  for (uint32_t digit = 0; digit < kTopDigits && cap > kTopSel; ++digit)
     hipLaunchKernelGGL(top_digit_kernel, dim3(grid), dim3(kTopBlock), 0, s, cand, T);
   hipLaunchKernelGGL(top_gather_kernel, dim3(grid), dim3(kTopBlock), 0, s, cand, T);
   if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;

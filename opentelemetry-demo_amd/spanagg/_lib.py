@@ -148,6 +148,21 @@ class sa_latency_result(C.Structure):
     ]
 
 
+SA_LATMOV_FALL = 1
+i32p = C.POINTER(C.c_int32)
+
+
+class sa_latency_movers_result(C.Structure):
+    _fields_ = [
+        ("base_first", C.c_uint64), ("base_last", C.c_uint64), ("cur_first", C.c_uint64), ("cur_last", C.c_uint64),
+        ("k", C.c_uint32), ("n", C.c_uint32), ("n_q", C.c_uint32), ("flags", C.c_uint32),
+        ("n_services", C.c_uint64), ("n_eligible", C.c_uint64), ("n_matched", C.c_uint64),
+        ("spans_base", C.c_uint64), ("spans_cur", C.c_uint64),
+        ("q_ppm", u32p), ("services", u32p), ("shift", i32p), ("count_base", u64p), ("count_cur", u64p),
+        ("q_bin_base", u8p), ("q_bin_cur", u8p), ("q_ns_base", u64p), ("q_ns_cur", u64p),
+    ]
+
+
 class sa_stats(C.Structure):
     _fields_ = [
         ("spans", C.c_uint64), ("zero_key", C.c_uint64), ("invalid_service", C.c_uint64),
@@ -230,6 +245,13 @@ SIGNATURES = [
     ("sa_group_window_latency", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, u32p, C.c_uint32, u32p,
                                           C.c_uint32, C.c_uint32, C.POINTER(C.POINTER(sa_latency_result))]),
     ("sa_latency_result_free", None, [C.POINTER(sa_latency_result)]),
+    ("sa_window_latency_movers", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
+                                           C.c_uint64, C.c_uint32, u32p, C.c_uint32, C.c_uint32,
+                                           C.POINTER(C.POINTER(sa_latency_movers_result))]),
+    ("sa_group_window_latency_movers", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
+                                                 C.c_uint32, C.c_uint64, C.c_uint32, u32p, C.c_uint32, C.c_uint32,
+                                                 C.POINTER(C.POINTER(sa_latency_movers_result))]),
+    ("sa_latency_movers_result_free", None, [C.POINTER(sa_latency_movers_result)]),
     ("sa_latency_bin", C.c_uint32, [C.c_uint64]),
     ("sa_latency_bin_bounds", C.c_int, [C.c_uint32, u64p, u64p]),
     ("sa_hll_estimate_hist", C.c_double, [u32p, C.c_uint32]),

@@ -269,6 +269,37 @@ class LatencyResult:
     hist: Optional[np.ndarray]    # [n_out, n_sel, 256] u64 summed bins (hist=True), else None
 
 
+@dataclass
+class LatencyMoversResult:
+    """sa_latency_movers_result: the services whose ranking quantile (q_ppm[0])
+    moved up most bins (fall: down) from the baseline range's summed histogram
+    to the current range's, among the services with enough spans in both.
+    From 2,048 ns up eight bins are a factor of two."""
+    base: tuple                   # (first, last) of the baseline range
+    cur: tuple                    # (first, last) of the current range
+    fall: bool
+    q_ppm: np.ndarray             # [n_q] u32: round(quantile * 1e6); q_ppm[0] ranks
+    services: np.ndarray          # [n] u32, by shift descending, count_cur descending, id ascending
+    shift: np.ndarray             # [n] i32: q_bin_cur[:, 0] - q_bin_base[:, 0] (negated when fall), >= 1
+    count_base: np.ndarray        # [n] u64: window_latency(*base, services=[s]).count
+    count_cur: np.ndarray         # [n] u64
+    q_bin_base: np.ndarray        # [n, n_q] u8: window_latency(*base, services=[s], quantiles).q_bin
+    q_bin_cur: np.ndarray         # [n, n_q] u8
+    q_ns_base: np.ndarray         # [n, n_q] u64: the bins' upper bounds in ns
+    q_ns_cur: np.ndarray          # [n, n_q] u64
+    n_services: int               # the candidates: every service
+    n_eligible: int               # services with at least max(min_count, 1) spans in both ranges
+    n_matched: int                # eligible services with shift >= max(min_shift, 1)
+    spans_base: int               # spans of every service over the baseline range, exact
+    spans_cur: int                # the same of the current range
+
+    def items(self):
+        """[(service, shift, count_base, count_cur, q_bin_base, q_bin_cur)] as sketch.latency_movers returns them."""
+        return [(int(s), int(d), int(b), int(c), tuple(int(x) for x in qb), tuple(int(x) for x in qc))
+                for s, d, b, c, qb, qc in zip(self.services, self.shift, self.count_base, self.count_cur,
+                                              self.q_bin_base, self.q_bin_cur)]
+
+
 def hll_estimate(regs: np.ndarray, p: int) -> float:
     lib = _lib.load()
     r = np.ascontiguousarray(regs, dtype=np.uint8)
@@ -445,7 +476,32 @@ def _window_latency(obj, fn, what, first, last, width, services, quantiles, hist
         obj.lib.sa_latency_result_free(out)
 
 
+def _window_latency_movers(obj, fn, what, base, cur, k, quantiles, min_count, min_shift, fall) -> LatencyMoversResult:
+    """sa_window_latency_movers / sa_group_window_latency_movers -> LatencyMoversResult (copies), freeing the
+    library's result."""
+    (bf, bl), (cf, cl) = base, cur
+    ppm = np.ascontiguousarray([int(round(float(q) * 1e6)) for q in quantiles], dtype=np.uint32)
+    out = C.POINTER(_lib.sa_latency_movers_result)()
+    obj._check(fn(obj._h, int(bf), int(bl), int(cf), int(cl), int(k), int(min_count), int(min_shift),
+                  ppm.ctypes.data_as(_lib.u32p), len(ppm), _lib.SA_LATMOV_FALL if fall else 0, C.byref(out)), what)
+    try:
+        r = out.contents
+        n, Q = int(r.n), int(r.n_q)
+        col = lambda p, dt, *shape: (np.ctypeslib.as_array(p, shape=(n,) + shape).copy() if n
+                                     else np.zeros((0,) + shape, dt))
+        return LatencyMoversResult(
+            (int(r.base_first), int(r.base_last)), (int(r.cur_first), int(r.cur_last)),
+            bool(r.flags & _lib.SA_LATMOV_FALL), np.ctypeslib.as_array(r.q_ppm, shape=(Q,)).copy(),
+            col(r.services, np.uint32), col(r.shift, np.int32), col(r.count_base, np.uint64),
+            col(r.count_cur, np.uint64), col(r.q_bin_base, np.uint8, Q), col(r.q_bin_cur, np.uint8, Q),
+            col(r.q_ns_base, np.uint64, Q), col(r.q_ns_cur, np.uint64, Q), int(r.n_services), int(r.n_eligible),
+            int(r.n_matched), int(r.spans_base), int(r.spans_cur))
+    finally:
+        obj.lib.sa_latency_movers_result_free(out)
+
+
 _QUANTILES = (0.5, 0.95, 0.99)
+_MOVER_QUANTILES = (0.99, 0.5, 0.95)  # the first one ranks
 
 
 def _ptr(x) -> int:
@@ -670,6 +726,17 @@ class Engine:
         return _window_latency(self, self.lib.sa_window_latency, "sa_window_latency", first, last, width, services,
                                quantiles, hist)
 
+    def window_latency_movers(self, base, cur, k: int = 10, quantiles=_MOVER_QUANTILES, min_count: int = 1,
+                              min_shift: int = 1, fall: bool = False) -> LatencyMoversResult:
+        """sa_window_latency_movers (OPT_WINDOW_LATENCY engines): the k
+        services whose quantiles[0] rose most histogram bins (fall: fell most)
+        from the windows base = (first, last) to the windows cur = (first,
+        last), among the services with at least min_count spans in both and a
+        shift >= min_shift -- both ranges summed, scored, selected and sorted
+        on the device; every quantile's bin and bound of the returned rows."""
+        return _window_latency_movers(self, self.lib.sa_window_latency_movers, "sa_window_latency_movers", base, cur, k,
+                                      quantiles, min_count, min_shift, fall)
+
     def flush_exp(self, allow_drops: bool = False) -> ExpoResult:
         out = C.POINTER(_lib.sa_exp_result)()
         rc = self.lib.sa_flush_exp(self._h, C.byref(out))
@@ -872,6 +939,13 @@ class Group:
         members' summed histograms."""
         return _window_latency(self, self.lib.sa_group_window_latency, "sa_group_window_latency", first, last, width,
                                services, quantiles, hist)
+
+    def window_latency_movers(self, base, cur, k: int = 10, quantiles=_MOVER_QUANTILES, min_count: int = 1,
+                              min_shift: int = 1, fall: bool = False) -> LatencyMoversResult:
+        """sa_group_window_latency_movers: Engine.window_latency_movers over
+        the members' summed histograms."""
+        return _window_latency_movers(self, self.lib.sa_group_window_latency_movers, "sa_group_window_latency_movers",
+                                      base, cur, k, quantiles, min_count, min_shift, fall)
 
     def window_advance(self, new_base: int):
         self._check(self.lib.sa_group_window_advance(self._h, int(new_base)), "sa_group_window_advance")

@@ -99,6 +99,32 @@ def latency_quantile_bin(hist, q_ppm: int) -> int:
     raise AssertionError("unreachable: r <= count")
 
 
+def latency_movers(hist_base, hist_cur, q_ppm: Sequence[int], k: int, min_count: int = 1, min_shift: int = 1,
+                   fall: bool = False):
+    """sa_window_latency_movers over two [n_services][256] arrays, each a
+    range's windows summed: (rows, n_eligible, n_matched).  A service is
+    eligible with at least max(min_count, 1) spans in both; its shift is the
+    bin of quantile q_ppm[0] in hist_cur minus that in hist_base (negated when
+    `fall`); it matches with shift >= max(min_shift, 1).  rows: the first k
+    matches by shift descending, then count_cur descending (clamped at 2^48 -
+    1), then service ascending, each (service, shift, count_base, count_cur,
+    q_bin_base, q_bin_cur) with the bins of every q_ppm as tuples."""
+    mc, ms = max(int(min_count), 1), max(int(min_shift), 1)
+    n_eligible, rows = 0, []
+    for s, (hb, hc) in enumerate(zip(hist_base, hist_cur)):
+        cb, cc = sum(int(c) for c in hb), sum(int(c) for c in hc)
+        if cb < mc or cc < mc:
+            continue
+        n_eligible += 1
+        qb = tuple(latency_quantile_bin(hb, p) for p in q_ppm)
+        qc = tuple(latency_quantile_bin(hc, p) for p in q_ppm)
+        shift = qb[0] - qc[0] if fall else qc[0] - qb[0]
+        if shift >= ms:
+            rows.append((s, shift, cb, cc, qb, qc))
+    rows.sort(key=lambda r: (-r[1], -min(r[3], (1 << 48) - 1), r[0]))
+    return rows[:k], n_eligible, len(rows)
+
+
 def anomalous(series: Sequence[float], factor: float, min_base: float = 1.0) -> list:
     """Indices whose value exceeds `factor` x the series median (floor min_base)."""
     x = np.asarray(series, dtype=np.float64)
