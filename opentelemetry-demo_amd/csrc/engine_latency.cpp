@@ -1,0 +1,299 @@
+// engine_latency.cpp -- the queries over the ring of latency histograms of an
+// SA_OPT_WINDOW_LATENCY engine: sa_window_latency and sa_window_latency_movers
+// (kernels in spanagg_latency.hip, the movers' select in spanagg_range.hip),
+// each with the asynchronous halves the engine group runs per member (sa_grp,
+// sa_group_hooks.h) and its result's free.  Arguments: sa_query_args.h.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstddef>
+#include <cstring>
+#include <memory>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "sa_engine.h"
+#include "sa_group_hooks.h"
+#include "sa_results.h"
+
+namespace {
+
+// ---- latency quantiles (sa_window_latency) ----
+// rows of sliding sums one tile of outputs holds (64 MiB; at least one output's)
+constexpr uint64_t kLatTileRows = 1u << 15;
+
+int latency_enabled(sa_engine *e, const char *query) {
+  if (const char *bad = sa_args::latency_option(e->cfg.options)) return bad_args(e, SA_ESTATE, query, bad);
+  return SA_OK;
+}
+
+// Room for a selection of n_sel ids, sum_rows rows of sliding sums in the
+// engine's own tile and `rows` rows' counts and quantile bins.
+int latency_buffers(sa_engine *e, uint64_t n_sel, uint64_t sum_rows, uint64_t rows, uint32_t n_q) {
+  sa_engine::Latency &L = e->lat;
+  if (int rc = grow(e, L.sel, L.sel_cap, n_sel ? std::max<uint64_t>(n_sel, 64) : 0, "window latency: selection hipMalloc failed"))
+    return rc;
+  if (int rc = grow(e, L.sums, L.sums_cap, sum_rows * SA_LAT_BINS, "window latency: sum buffer hipMalloc failed")) return rc;
+  if (int rc = grow(e, L.count, L.row_cap, rows, "window latency: count buffer hipMalloc failed")) return rc;
+  return grow(e, L.q_bin, L.qbin_cap, rows * n_q, "window latency: quantile buffer hipMalloc failed");
+}
+
+// A member's part of a group query on `s`: the selection onto the device and
+// the sums stage behind it, sums [n_out][sel.size()][SA_LAT_BINS] from window
+// `a` on.  The copy reads the caller's pageable `sel` asynchronously, so it is
+// queued after everything that can fail without a wait, and a failure behind
+// it waits for `s` before it returns; on success the group waits before `sel` goes.
+hipError_t latency_sums_on(sa_engine *e, const std::vector<uint32_t> &sel, uint64_t a, uint32_t width, uint32_t n_out,
+                           unsigned long long *d_sums, hipStream_t s) {
+  const sa_engine::Latency &L = e->lat;
+  hipError_t st = hipMemcpyAsync(L.sel, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, s);
+  if (st == hipSuccess)
+    st = sa::launch_lat_sums(L.ring, e->cfg.n_services, e->cfg.n_windows, L.sel, (uint32_t)sel.size(), a, width, n_out,
+                             d_sums, s);
+  if (st != hipSuccess) (void)hipStreamSynchronize(s);
+  return st;
+}
+
+// On `s`: the counts and quantile bins of rows row0 .. row0 + n_rows - 1 from
+// their sums d_sums [n_rows][SA_LAT_BINS], and with SA_LAT_HIST the sums' copy
+// into the result.
+hipError_t latency_scan_on(sa_engine *e, const unsigned long long *d_sums, uint64_t row0, uint64_t n_rows,
+                           latency_holder *h, hipStream_t s) {
+  const sa_engine::Latency &L = e->lat;
+  const uint32_t n_q = h->r.n_q;
+  hipError_t st = sa::launch_lat_scan(d_sums, n_rows, h->q_ppm.data(), n_q, L.count + row0, L.q_bin + row0 * n_q, s);
+  if (st == hipSuccess && h->r.hist)
+    st = hipMemcpyAsync(h->hist.data() + row0 * SA_LAT_BINS, d_sums, n_rows * SA_LAT_BINS * 8, hipMemcpyDeviceToHost, s);
+  return st;
+}
+
+// The counts and bins into the result (st: what the launches before returned),
+// the call's one wait -- also after a failure: a copy into h may be in flight
+// -- and every bin's upper bound.
+int latency_collect(sa_engine *e, hipError_t st, std::unique_ptr<latency_holder> &h, hipStream_t s,
+                    sa_latency_result **out) {
+  const sa_engine::Latency &L = e->lat;
+  if (st == hipSuccess) st = hipMemcpyAsync(h->count.data(), L.count, h->count.size() * 8, hipMemcpyDeviceToHost, s);
+  if (st == hipSuccess) st = hipMemcpyAsync(h->q_bin.data(), L.q_bin, h->q_bin.size(), hipMemcpyDeviceToHost, s);
+  const hipError_t waited = hipStreamSynchronize(s);
+  if (st != hipSuccess || waited != hipSuccess)
+    return fail(e, SA_EDEVICE, std::string("window latency: ") + hipGetErrorString(st != hipSuccess ? st : waited));
+  const uint32_t n_q = h->r.n_q;
+  for (size_t row = 0; row < h->count.size(); ++row)
+    for (uint32_t i = 0; i < n_q; ++i) {
+      uint64_t lo = 0, hi = 0;
+      if (h->count[row]) (void)sa_latency_bin_bounds(h->q_bin[row * n_q + i], &lo, &hi);
+      h->q_ns[row * n_q + i] = hi;
+    }
+  *out = &h.release()->r;
+  return SA_OK;
+}
+
+std::unique_ptr<latency_holder> latency_result(sa_engine *e, uint64_t first, uint64_t last, uint32_t width,
+                                               const std::vector<uint32_t> &sel, const uint32_t *q_ppm, uint32_t n_q,
+                                               uint32_t flags) {
+  std::unique_ptr<latency_holder> h;
+  try {
+    h.reset(new latency_holder());
+    h->shape(first, last, width, sel, q_ppm, n_q, flags);
+  } catch (const std::bad_alloc &) {
+    h.reset();
+    (void)fail(e, SA_ENOMEM, "window latency: the result does not fit in host memory");
+  }
+  return h;
+}
+
+// ---- latency movers (sa_window_latency_movers) ----
+// range: base first, base last, current first, current last
+int latency_movers_ranges(sa_engine *e, const uint64_t range[4]) {
+  if (int rc = check_span(e, "window latency movers", range[0], range[1], 1)) return rc;
+  return check_span(e, "window latency movers", range[2], range[3], 1);
+}
+
+// What the stages after the sums work in: the counts, the candidates (one a
+// service), the rows, and sa_window_top's control block.
+int latency_movers_buffers(sa_engine *e) {
+  sa_engine::Latency &L = e->lat;
+  const size_t S = e->cfg.n_services;
+  if (int rc = lazy(e, e->top.ctl, 1, "window latency movers: control block hipMalloc failed")) return rc;
+  if (int rc = lazy(e, L.mov_counts, 2 * S, "window latency movers: count buffer hipMalloc failed")) return rc;
+  if (int rc = lazy(e, L.mov_cand, S, "window latency movers: candidate buffer hipMalloc failed")) return rc;
+  return lazy(e, L.mov_out, 1, "window latency movers: row buffer hipMalloc failed");
+}
+
+hipError_t latency_movers_sums_on(sa_engine *e, const uint64_t range[4], unsigned long long *d_sums, hipStream_t s) {
+  return sa::launch_lat_pair_sums(e->lat.ring, e->cfg.n_services, e->cfg.n_windows, range[0],
+                                  (uint32_t)(range[1] - range[0] + 1), range[2], (uint32_t)(range[3] - range[2] + 1),
+                                  d_sums, s);
+}
+}  // namespace
+
+namespace sa_grp {
+int window_latency_export_async(sa_engine *e, uint64_t first, uint64_t last, uint32_t width,
+                                const std::vector<uint32_t> &sel, uint64_t *d_sums, hipStream_t s) {
+  if (!e || !d_sums || sel.empty()) return SA_EINVAL;
+  if (int rc = latency_enabled(e, "window latency")) return rc;
+  if (int rc = check_span(e, "window latency", first, last, width)) return rc;
+  if (int rc = begin_read(e)) return rc;
+  if (int rc = latency_buffers(e, sel.size(), 0, 0, 0)) return rc;
+  if (int rc = hop_to(e, s)) return rc;
+  SA_HIP(e, latency_sums_on(e, sel, first - width + 1, width, (uint32_t)(last - first + 1),
+                            reinterpret_cast<unsigned long long *>(d_sums), s));
+  if (int rc = hop_back(e, s)) {  // (the selection buffer is the engine's)
+    (void)hipStreamSynchronize(s);
+    return rc;
+  }
+  return SA_OK;
+}
+
+int window_latency_finish(sa_engine *e, uint64_t first, uint64_t last, uint32_t width, const std::vector<uint32_t> &sel,
+                          const uint32_t *q_ppm, uint32_t n_q, uint32_t flags, const uint64_t *d_sums, hipStream_t s,
+                          sa_latency_result **out) {
+  if (!e || !out || !d_sums || sel.empty()) return SA_EINVAL;
+  if (int rc = set_dev(e)) return rc;
+  std::unique_ptr<latency_holder> h = latency_result(e, first, last, width, sel, q_ppm, n_q, flags);
+  if (!h) return SA_ENOMEM;
+  const uint64_t rows = h->count.size();
+  if (int rc = latency_buffers(e, 0, 0, rows, n_q)) return rc;
+  const hipError_t st = latency_scan_on(e, reinterpret_cast<const unsigned long long *>(d_sums), 0, rows, h.get(), s);
+  return latency_collect(e, st, h, s, out);
+}
+
+int window_latency_movers_export_async(sa_engine *e, const uint64_t range[4], uint64_t *d_sums, hipStream_t s) {
+  if (!e || !d_sums) return SA_EINVAL;
+  if (int rc = latency_enabled(e, "window latency movers")) return rc;
+  if (int rc = latency_movers_ranges(e, range)) return rc;
+  if (int rc = begin_read(e)) return rc;
+  if (int rc = hop_to(e, s)) return rc;
+  SA_HIP(e, latency_movers_sums_on(e, range, reinterpret_cast<unsigned long long *>(d_sums), s));
+  return hop_back(e, s);  // (a later launch that writes the ring orders after these reads)
+}
+
+int window_latency_movers_finish(sa_engine *e, const uint64_t range[4], uint32_t k, uint64_t min_count,
+                                 uint32_t min_shift, const uint32_t *q_ppm, uint32_t n_q, uint32_t flags,
+                                 const uint64_t *d_sums, hipStream_t s, sa_latency_movers_result **out) {
+  if (!e || !out || !d_sums) return SA_EINVAL;
+  if (int rc = set_dev(e)) return rc;
+  if (int rc = latency_movers_buffers(e)) return rc;
+  const sa_engine::Latency &L = e->lat;
+  sa::TopCtl *T = e->top.ctl;
+  unsigned long long head[4] = {};
+  std::vector<ulonglong2> sel;
+  std::vector<unsigned char> rows;  // LatMovOut's head and its first k rows
+  try {
+    sel.resize(k);
+    rows.resize(offsetof(sa::LatMovOut, row) + (size_t)k * sizeof(sa::LatMovRow));
+  } catch (const std::bad_alloc &) {
+    return fail(e, SA_ENOMEM, "window latency movers: the rows do not fit in host memory");
+  }
+  // (the scratch is the engine's: after its own earlier use, before its next)
+  if (int rc = hop_to(e, s)) return rc;
+  hipError_t st = sa::launch_lat_movers(reinterpret_cast<const unsigned long long *>(d_sums), e->cfg.n_services, k,
+                                        std::max<uint64_t>(min_count, 1), std::max(min_shift, 1u),
+                                        flags & SA_LATMOV_FALL ? 1u : 0u, q_ppm, n_q, L.mov_counts, L.mov_cand, T,
+                                        L.mov_out, s);
+  if (st == hipSuccess) st = copy_top(T, k, head, sel.data(), s);
+  if (st == hipSuccess) st = hipMemcpyAsync(rows.data(), L.mov_out, rows.size(), hipMemcpyDeviceToHost, s);
+  const hipError_t waited = hipStreamSynchronize(s);  // the call's one wait (also after a failure: copies may be in flight)
+  if (st != hipSuccess || waited != hipSuccess)
+    return fail(e, SA_EDEVICE, std::string("window latency movers: ") + hipGetErrorString(st != hipSuccess ? st : waited));
+  const uint32_t n = (uint32_t)std::min<uint64_t>(k, head[0]);
+  std::unique_ptr<latency_movers_holder> h;
+  try {
+    h.reset(new latency_movers_holder());
+    h->shape(range, k, n, q_ppm, n_q, flags, e->cfg.n_services);
+  } catch (const std::bad_alloc &) {
+    return fail(e, SA_ENOMEM, "window latency movers: the result does not fit in host memory");
+  }
+  // (TopCtl's head: the matches, the eligible services, ..; LatMovOut's: the two ranges' spans)
+  h->r.n_matched = head[0], h->r.n_eligible = head[1];
+  std::memcpy(&h->r.spans_base, rows.data(), 8);
+  std::memcpy(&h->r.spans_cur, rows.data() + 8, 8);
+  for (uint32_t i = 0; i < n; ++i) {
+    sa::LatMovRow row;
+    std::memcpy(&row, rows.data() + offsetof(sa::LatMovOut, row) + (size_t)i * sizeof row, sizeof row);
+    h->services[i] = (uint32_t)sel[i].y;
+    h->shift[i] = (int32_t)(sel[i].x >> 48);
+    h->count_base[i] = row.count[0], h->count_cur[i] = row.count[1];
+    for (uint32_t q = 0; q < n_q; ++q) {
+      uint64_t lo = 0, hi = 0;
+      const size_t at = (size_t)i * n_q + q;
+      h->q_bin_base[at] = row.q_bin[0][q], h->q_bin_cur[at] = row.q_bin[1][q];
+      // (a returned row is eligible: neither count is 0)
+      (void)sa_latency_bin_bounds(row.q_bin[0][q], &lo, &hi);
+      h->q_ns_base[at] = row.count[0] ? hi : 0;
+      (void)sa_latency_bin_bounds(row.q_bin[1][q], &lo, &hi);
+      h->q_ns_cur[at] = row.count[1] ? hi : 0;
+    }
+  }
+  *out = &h.release()->r;
+  return SA_OK;
+}
+}  // namespace sa_grp
+
+extern "C" {
+
+int sa_window_latency(sa_engine *e, uint64_t first, uint64_t last, uint32_t width, const uint32_t *services,
+                      uint32_t n_sel, const uint32_t *q_ppm, uint32_t n_q, uint32_t flags, sa_latency_result **out) {
+  if (!e || !out) return SA_EINVAL;
+  *out = nullptr;
+  if (int rc = latency_enabled(e, "window latency")) return rc;
+  std::vector<uint32_t> sel;
+  try {
+    if (const char *bad = sa_args::latency_args(e->cfg.n_services, services, n_sel, q_ppm, n_q, flags, &sel))
+      return bad_args(e, SA_EINVAL, "window latency", bad);
+  } catch (const std::bad_alloc &) {
+    return fail(e, SA_ENOMEM, "window latency: the selection does not fit in host memory");
+  }
+  if (int rc = check_span(e, "window latency", first, last, width)) return rc;
+  const uint32_t n_out = (uint32_t)(last - first + 1), S = (uint32_t)sel.size();
+  if (const char *bad = sa_args::latency_rows(n_out, S, flags)) return bad_args(e, SA_EINVAL, "window latency", bad);
+  if (int rc = begin_read(e)) return rc;
+  std::unique_ptr<latency_holder> h = latency_result(e, first, last, width, sel, q_ppm, n_q, flags);
+  if (!h) return SA_ENOMEM;
+  // the outputs in tiles of at most kLatTileRows rows of sums (one tile's
+  // sums, then its counts and bins, tile after tile on the engine stream)
+  const uint32_t tile = (uint32_t)std::min<uint64_t>(n_out, std::max<uint64_t>(1, kLatTileRows / S));
+  hipStream_t s = e->stream;
+  if (int rc = latency_buffers(e, S, (uint64_t)tile * S, (uint64_t)n_out * S, n_q)) return rc;
+  const sa_engine::Latency &L = e->lat;
+  // (queued after everything that can fail without a wait: the copy reads the pageable `sel`
+  // asynchronously, and latency_collect waits for `s`, whatever st says, before sel goes)
+  hipError_t st = hipMemcpyAsync(L.sel, sel.data(), (size_t)S * 4, hipMemcpyHostToDevice, s);
+  for (uint32_t o0 = 0; o0 < n_out && st == hipSuccess; o0 += tile) {
+    const uint32_t n_o = std::min(tile, n_out - o0);
+    st = sa::launch_lat_sums(L.ring, e->cfg.n_services, e->cfg.n_windows, L.sel, S, first - width + 1 + o0, width, n_o,
+                             L.sums, s);
+    if (st == hipSuccess) st = latency_scan_on(e, L.sums, (uint64_t)o0 * S, (uint64_t)n_o * S, h.get(), s);
+  }
+  return latency_collect(e, st, h, s, out);
+}
+
+void sa_latency_result_free(sa_latency_result *r) { delete reinterpret_cast<latency_holder *>(r); }
+
+int sa_window_latency_movers(sa_engine *e, uint64_t base_first, uint64_t base_last, uint64_t cur_first,
+                             uint64_t cur_last, uint32_t k, uint64_t min_count, uint32_t min_shift,
+                             const uint32_t *q_ppm, uint32_t n_q, uint32_t flags, sa_latency_movers_result **out) {
+  if (!e || !out) return SA_EINVAL;
+  *out = nullptr;
+  if (int rc = latency_enabled(e, "window latency movers")) return rc;
+  if (const char *bad = sa_args::latency_movers_args(k, q_ppm, n_q, flags))
+    return bad_args(e, SA_EINVAL, "window latency movers", bad);
+  const uint64_t range[4] = {base_first, base_last, cur_first, cur_last};
+  if (int rc = latency_movers_ranges(e, range)) return rc;
+  if (int rc = begin_read(e)) return rc;
+  // both ranges' sums of the engine's own ring [2][n_services][SA_LAT_BINS]
+  if (int rc = lazy(e, e->lat.mov_sums, 2 * (size_t)e->cfg.n_services * SA_LAT_BINS,
+                    "window latency movers: sum buffer hipMalloc failed"))
+    return rc;
+  if (int rc = latency_movers_buffers(e)) return rc;
+  // (the sums, then the stages a group runs on its member 0 after adding the members' sums)
+  SA_HIP(e, latency_movers_sums_on(e, range, e->lat.mov_sums, e->stream));
+  return sa_grp::window_latency_movers_finish(e, range, k, min_count, min_shift, q_ppm, n_q, flags,
+                                              reinterpret_cast<const uint64_t *>(e->lat.mov_sums), e->stream, out);
+}
+
+void sa_latency_movers_result_free(sa_latency_movers_result *r) { delete reinterpret_cast<latency_movers_holder *>(r); }
+
+}  // extern "C"

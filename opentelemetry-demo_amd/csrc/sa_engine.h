@@ -1,7 +1,10 @@
-// sa_engine.h -- internal: struct sa_engine and what the engine's three
-// sources share.  engine_create.cpp validates, picks the path (sa_path.h) and
-// owns creation and destruction; engine_ingest.cpp launches; engine_read.cpp
-// reads back.  One engine owns one gfx950 device.
+// sa_engine.h -- internal: struct sa_engine and what the engine's sources
+// share.  engine_create.cpp validates, picks the path (sa_path.h) and owns
+// creation and destruction; engine_ingest.cpp launches; three files read back:
+// engine_read.cpp (flush, reclamation, stats, sa_bind_ids, the probes, one
+// window's sketches and the merge hooks), engine_window.cpp (the queries over
+// the sketch ring: range, series, top, movers, overlap) and engine_latency.cpp
+// (latency and latency movers).  One engine owns one gfx950 device.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,6 +15,7 @@
 #include "sa_internal.h"
 #include "sa_lab.h"
 #include "sa_path.h"
+#include "sa_query_args.h"
 #include "spanagg.h"
 
 // internal to the library: none of this is exported
@@ -306,6 +310,33 @@ void dfree(sa_engine *e, T *&p) {
   e->res.release(p);
   p = nullptr;
 }
+// A query's scratch, allocated by the first call that needs it.
+template <class T>
+int lazy(sa_engine *e, T *&p, size_t count, const char *what) {
+  return p ? SA_OK : dalloc(e, p, count, false, what);
+}
+// p (holding cap elements) grown to at least `want`, its contents dropped.
+template <class T>
+int grow(sa_engine *e, T *&p, uint64_t &cap, uint64_t want, const char *what) {
+  if (want <= cap) return SA_OK;
+  dfree(e, p);  // (hipFree waits for the device)
+  cap = 0;
+  if (int rc = dalloc(e, p, want, false, what)) return rc;
+  cap = want;
+  return SA_OK;
+}
+
+// An argument rule's verdict (sa_query_args.h) as the call's: "<query>: <what is wrong>"
+inline int bad_args(sa_engine *e, int code, const char *query, const char *bad) {
+  return fail(e, code, std::string(query) + ": " + bad);
+}
+// sa_args::span on the engine's ring: SA_ERANGE unless every window the
+// outputs first..last cover, `width` windows each, is resident
+inline int check_span(sa_engine *e, const char *query, uint64_t first, uint64_t last, uint32_t width = 1) {
+  if (const char *bad = sa_args::span(first, last, width, e->win_base, e->cfg.n_windows))
+    return bad_args(e, SA_ERANGE, query, bad);
+  return SA_OK;
+}
 
 // engine_ingest.cpp
 // Orders the engine stream after every outstanding launch (each set's last
@@ -316,5 +347,21 @@ int join_checked(sa_engine *e);
 int reduce_slabs(sa_engine *e, hipStream_t s);
 sa::ExpoParams expo_params(sa_engine *e, const sa_span_batch *b, uint32_t set = 0);
 uint32_t bt_region_for(const sa_engine *e, uint64_t wg_chunk);
+
+// engine_read.cpp
+// Every read starts here: the engine's device, and every launch in flight
+// joined onto the engine stream (a pending aggregate that failed is returned).
+int begin_read(sa_engine *e);
+// A caller's stream `s` takes over from the engine stream (ev_a), and hands
+// back: later engine work orders after what the caller's stream did (ev_b).
+int hop_to(sa_engine *e, hipStream_t s);
+int hop_back(sa_engine *e, hipStream_t s);
+// Derive the count-min cells of window slot ws from its exact per-slot error
+// counts (see sketch_post in sa_device.h).
+int fold_errslab(sa_engine *e, uint64_t ws, hipStream_t s);
+
+// engine_window.cpp
+// sa::TopCtl's head and its first k selected rows to the host, on `s`
+hipError_t copy_top(const sa::TopCtl *ctl, uint32_t k, unsigned long long head[4], ulonglong2 *rows, hipStream_t s);
 
 #pragma GCC visibility pop

@@ -1,8 +1,11 @@
 // sa_group_hooks.h -- internal (not in the C-ABI): asynchronous forms of the
-// engine's merge hooks for the engine group's flush (spanagg_group.cpp), so a
-// flush of n members waits once per phase instead of once per member per
-// call.  Host outputs must be page-locked (the copies are asynchronous);
-// every call orders `s` after the engine's earlier work.
+// engine's merge hooks for the engine group (spanagg_group.cpp), so a flush or
+// a window query of n members waits once per phase instead of once per member
+// per call.  The flush-time hooks are engine_read.cpp's, a window query's
+// export and finish halves engine_window.cpp's and engine_latency.cpp's; the
+// queries' argument rules are sa_query_args.h's.  Host outputs must be
+// page-locked (the copies are asynchronous); every call orders `s` after the
+// engine's earlier work.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -42,10 +45,6 @@ int window_range_export_async(sa_engine *e, uint64_t first, uint64_t last, uint8
 // sa_window_range.
 int window_range_finish(sa_engine *e, uint64_t first, uint64_t last, const uint8_t *d_hll, const uint64_t *d_cms,
                         const uint64_t *keys, uint64_t n_keys, uint32_t flags, hipStream_t s, sa_range_result **out);
-// sa_window_overlap's selection rules for an engine of n_services services:
-// *sel = the ids in the caller's order (services == nullptr with n_sel == 0:
-// every id).  nullptr when valid, else what is wrong (SA_EINVAL).
-const char *overlap_select(uint32_t n_services, const uint32_t *services, uint32_t n_sel, std::vector<uint32_t> *sel);
 // sa_window_overlap's merge for one member, without the wait: d_hll
 // [n_services][2^p] = the registers of windows first..last max-merged, on `s`
 // (no cell is folded or summed: only the registers are read).  SA_ERANGE as
@@ -54,20 +53,12 @@ int window_overlap_export_async(sa_engine *e, uint64_t first, uint64_t last, uin
 // the rest of a group's overlap query, on member 0 (`e`, whose device holds
 // the members' merged d_hll [n_services][2^p]) and on `s`: the selected rows
 // gathered with their histograms, the pairs' histograms, the copies, the wait
-// and the estimates.  sel: overlap_select's.
+// and the estimates.  sel: sa_args::overlap_select's.
 int window_overlap_finish(sa_engine *e, uint64_t first, uint64_t last, const uint8_t *d_hll,
                           const std::vector<uint32_t> &sel, hipStream_t s, sa_overlap_result **out);
-// sa_window_latency's argument rules for an engine of n_services services:
-// *sel = the ids in the caller's order (services == nullptr with n_sel == 0:
-// every id).  nullptr when valid, else what is wrong (SA_EINVAL).
-const char *latency_args(uint32_t n_services, const uint32_t *services, uint32_t n_sel, const uint32_t *q_ppm,
-                         uint32_t n_q, uint32_t flags, std::vector<uint32_t> *sel);
-// its size rule, once the span is known to be resident: n_out * n_sel <= 2^20
-// (2^16 with SA_LAT_HIST).  nullptr when valid.
-const char *latency_rows(uint64_t n_out, uint64_t n_sel, uint32_t flags);
 // sa_window_latency's sums stage for one member, without the wait: d_sums
 // [n_out][sel.size()][SA_LAT_BINS] = the rows of the selected services summed
-// over each output's windows, on `s`.  sel (latency_args') must stay until `s`
+// over each output's windows, on `s`.  sel (sa_args::latency_args') must stay until `s`
 // has been waited for.  SA_ESTATE without the option, SA_ERANGE as
 // sa_window_latency.
 int window_latency_export_async(sa_engine *e, uint64_t first, uint64_t last, uint32_t width,
@@ -78,9 +69,6 @@ int window_latency_export_async(sa_engine *e, uint64_t first, uint64_t last, uin
 int window_latency_finish(sa_engine *e, uint64_t first, uint64_t last, uint32_t width, const std::vector<uint32_t> &sel,
                           const uint32_t *q_ppm, uint32_t n_q, uint32_t flags, const uint64_t *d_sums, hipStream_t s,
                           sa_latency_result **out);
-// sa_window_latency_movers' argument rules (the ranges apart): nullptr when
-// valid, else what is wrong (SA_EINVAL).
-const char *latency_movers_args(uint32_t k, const uint32_t *q_ppm, uint32_t n_q, uint32_t flags);
 // sa_window_latency_movers' sums stage for one member, without the wait:
 // d_sums [2][n_services][SA_LAT_BINS] = every service's rows summed over
 // range[0]..range[1] (the baseline) and over range[2]..range[3] (the current
@@ -89,7 +77,7 @@ int window_latency_movers_export_async(sa_engine *e, const uint64_t range[4], ui
 // the rest of the query, on `e` (a group's member 0, whose device holds the
 // members' summed d_sums) and on `s`: the scores, the select and the sort, the
 // selected rows, the copies, the wait and the bins' bounds.  The arguments
-// (latency_movers_args passed them) and *out as sa_window_latency_movers.
+// (sa_args::latency_movers_args passed them) and *out as sa_window_latency_movers.
 int window_latency_movers_finish(sa_engine *e, const uint64_t range[4], uint32_t k, uint64_t min_count,
                                  uint32_t min_shift, const uint32_t *q_ppm, uint32_t n_q, uint32_t flags,
                                  const uint64_t *d_sums, hipStream_t s, sa_latency_movers_result **out);

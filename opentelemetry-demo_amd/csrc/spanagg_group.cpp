@@ -14,7 +14,6 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
-#include <initializer_list>
 #include <map>
 #include <memory>
 #include <cstdlib>
@@ -25,6 +24,7 @@
 
 #include "sa_group_hooks.h"
 #include "sa_internal.h"
+#include "sa_query_args.h"
 #include "sa_results.h"
 #include "spanagg.h"
 
@@ -411,6 +411,106 @@ int copy_reduce(sa_group *g, std::vector<Buf> &bufs, uint64_t len, bool max_u8) 
                        static_cast<const unsigned long long *>(g->stack.p), n, len);
   SG_HIP(g, hipGetLastError());
   return SA_OK;
+}
+
+// An argument rule's verdict (sa_query_args.h) as the call's: "<query>: <what is wrong>"
+int bad_args(sa_group *g, int code, const char *query, const char *bad) {
+  return gfail(g, code, std::string(query) + ": " + bad);
+}
+
+template <class T>
+T *buf(std::vector<Buf> &v, uint32_t i) {
+  return static_cast<T *>(v[i].p);
+}
+
+// One array of a merge: every member's `len` elements in (*bufs)[i],
+// max-merged (u8: HLL registers) or summed (u64: cells, latency sums, rows).
+struct Part {
+  std::vector<Buf> *bufs;
+  uint64_t len;
+  bool max_u8;
+};
+Part regs_part(sa_group *g) { return {&g->hll, g->hll_bytes, true}; }
+Part cells_part(sa_group *g, std::vector<Buf> &cells) { return {&cells, g->cms_elems, false}; }
+
+// room for every part on every member's device
+int ensure_parts(sa_group *g, const std::vector<Part> &parts) {
+  for (uint32_t i = 0; i < g->eng.size(); ++i)
+    for (const Part &p : parts)
+      if (int rc = ensure(g, g->dev[i], (*p.bufs)[i], p.len * (p.max_u8 ? 1 : 8))) return rc;
+  return SA_OK;
+}
+
+// The members' parts, written on their streams, merged.  RCCL all-reduces
+// every part in one group call and leaves the result on every member; the copy
+// transport reduces part after part onto member 0's device (copy_reduce).
+int reduce_members(sa_group *g, const std::vector<Part> &parts) {
+  if (!g->rccl) {
+    for (const Part &p : parts)
+      if (int rc = copy_reduce(g, *p.bufs, p.len, p.max_u8)) return rc;
+    return SA_OK;
+  }
+  SG_NCCL(g, ncclGroupStart());
+  for (uint32_t i = 0; i < g->eng.size(); ++i)
+    for (const Part &p : parts)
+      SG_NCCL(g, ncclAllReduce((*p.bufs)[i].p, (*p.bufs)[i].p, p.len, p.max_u8 ? ncclUint8 : ncclUint64,
+                               p.max_u8 ? ncclMax : ncclSum, g->comm[i], g->st[i]));
+  SG_NCCL(g, ncclGroupEnd());
+  return SA_OK;
+}
+
+// The members' cell arrays summed (reduce_members) and the sums left on every member's device before its
+// stream goes on: RCCL's all-reduce leaves it there; the copy transport copies
+// member 0's back.
+int sum_cells_everywhere(sa_group *g, const std::vector<Part> &parts) {
+  const uint32_t n = (uint32_t)g->eng.size();
+  if (int rc = reduce_members(g, parts)) return rc;
+  if (g->rccl || n == 1) return SA_OK;
+  SG_HIP(g, hipSetDevice(g->dev[0]));  // (copy_reduce drained the members' streams)
+  for (const Part &p : parts)
+    for (uint32_t i = 1; i < n; ++i) {
+      if (g->dev[i] == g->dev[0])
+        SG_HIP(g, hipMemcpyAsync((*p.bufs)[i].p, (*p.bufs)[0].p, p.len * 8, hipMemcpyDeviceToDevice, g->st[0]));
+      else
+        SG_HIP(g, hipMemcpyPeerAsync((*p.bufs)[i].p, g->dev[i], (*p.bufs)[0].p, g->dev[0], p.len * 8, g->st[0]));
+    }
+  SG_HIP(g, hipStreamSynchronize(g->st[0]));  // the result is on every member before its scan starts
+  return SA_OK;
+}
+
+// f(i) for every member until one fails: SA_OK, or that member's error.
+template <class F>
+int each_member(sa_group *g, const char *what, F &&f) {
+  for (uint32_t i = 0; i < g->eng.size(); ++i)
+    if (int rc = f(i)) return member_error(g, i, rc, what);
+  return SA_OK;
+}
+
+// Waits for every member's stream (also after a failure: copies into host
+// results may be in flight); the first error met.
+hipError_t wait_members(sa_group *g) {
+  hipError_t st = hipSuccess;
+  for (uint32_t i = 0; i < g->eng.size(); ++i) {
+    hipError_t a = hipSetDevice(g->dev[i]);
+    if (a == hipSuccess) a = hipStreamSynchronize(g->st[i]);
+    if (st == hipSuccess) st = a;
+  }
+  return st;
+}
+
+// The end of every window query: every member's stream waited for -- whatever
+// failed: copies out of the caller's arrays may be in flight, and an
+// all-reduce ends on every member's stream -- then the member's error, the
+// merge's, the device's.  A result built before a device error is freed.
+template <class R>
+int end_query(sa_group *g, const char *what, int member, int merged, R **out, void (*free_result)(R *)) {
+  const hipError_t st = wait_members(g);
+  if (member) return member;
+  if (merged) return merged;
+  if (st == hipSuccess) return SA_OK;
+  free_result(*out);
+  *out = nullptr;
+  return gfail(g, SA_EDEVICE, std::string(what) + ": " + hipGetErrorString(st));
 }
 
 // The sorted union of `n_in` series ids in `in` (member i's device, stream
@@ -900,12 +1000,7 @@ int sa_group_flush(sa_group *g, sa_red_result **out) {
     }
     bool one_device = true;
     for (uint32_t i = 1; i < n; ++i) one_device = one_device && g->dev[i] == g->dev[0];
-    if (g->rccl) {
-      SG_NCCL(g, ncclGroupStart());
-      for (uint32_t i = 0; i < n; ++i)
-        SG_NCCL(g, ncclAllReduce(g->rows[i].p, g->rows[i].p, len, ncclUint64, ncclSum, g->comm[i], g->st[i]));
-      SG_NCCL(g, ncclGroupEnd());
-    } else if (one_device && n > 1) {
+    if (!g->rccl && one_device && n > 1) {
       // every member's rows on one device: summed from their buffers into
       // member 0's (each element read from every member before its one write)
       for (uint32_t i = 1; i < n; ++i) {
@@ -918,7 +1013,7 @@ int sa_group_flush(sa_group *g, sa_red_result **out) {
       hipLaunchKernelGGL(sum_ptrs_u64, dim3(grid_for(len)), dim3(256), 0, g->st[0],
                          static_cast<unsigned long long *>(g->rows[0].p), src, n, len);
       SG_HIP(g, hipGetLastError());
-    } else if (int rc = copy_reduce(g, g->rows, len, false)) {
+    } else if (int rc = reduce_members(g, {{&g->rows, len, false}})) {
       return drop(rc);
     }
     const size_t fin_bytes = (size_t)nu * (g->nbk + 3) * 8;
@@ -1040,52 +1135,37 @@ int sa_group_flush_exp(sa_group *g, sa_exp_result **out) {
 int sa_group_window_read(sa_group *g, uint64_t window_id, sa_sketch_result **out) {
   if (!g || !out) return SA_EINVAL;
   *out = nullptr;
-  const uint32_t n = (uint32_t)g->eng.size();
-  for (uint32_t i = 0; i < n; ++i) {
-    if (int rc = ensure(g, g->dev[i], g->hll[i], g->hll_bytes)) return rc;
-    if (int rc = ensure(g, g->dev[i], g->cms[i], g->cms_elems * 8)) return rc;
-    if (int rc = sa_window_export(g->eng[i], window_id, static_cast<uint8_t *>(g->hll[i].p),
-                                  static_cast<uint64_t *>(g->cms[i].p), g->st[i]))
-      return member_error(g, i, rc, "sa_window_export");
-  }
-  if (g->rccl) {
-    SG_NCCL(g, ncclGroupStart());
-    for (uint32_t i = 0; i < n; ++i) {
-      SG_NCCL(g, ncclAllReduce(g->hll[i].p, g->hll[i].p, g->hll_bytes, ncclUint8, ncclMax, g->comm[i], g->st[i]));
-      SG_NCCL(g, ncclAllReduce(g->cms[i].p, g->cms[i].p, g->cms_elems, ncclUint64, ncclSum, g->comm[i], g->st[i]));
-    }
-    SG_NCCL(g, ncclGroupEnd());
-  } else {
-    if (int rc = copy_reduce(g, g->hll, g->hll_bytes, true)) return rc;
-    if (int rc = copy_reduce(g, g->cms, g->cms_elems, false)) return rc;
-  }
+  const std::vector<Part> parts = {regs_part(g), cells_part(g, g->cms)};
+  if (int rc = ensure_parts(g, parts)) return rc;
+  if (int rc = each_member(g, "sa_window_export", [&](uint32_t i) {
+        return sa_window_export(g->eng[i], window_id, buf<uint8_t>(g->hll, i), buf<uint64_t>(g->cms, i), g->st[i]);
+      }))
+    return rc;
+  if (int rc = reduce_members(g, parts)) return rc;
   auto *h = new sketch_holder();
   h->hll.resize(g->hll_bytes);
   std::vector<uint64_t> c64(g->cms_elems);
   (void)hipSetDevice(g->dev[0]);
   hipError_t a = hipMemcpyAsync(h->hll.data(), g->hll[0].p, g->hll_bytes, hipMemcpyDeviceToHost, g->st[0]);
   hipError_t b = hipMemcpyAsync(c64.data(), g->cms[0].p, g->cms_elems * 8, hipMemcpyDeviceToHost, g->st[0]);
-  hipError_t c = hipStreamSynchronize(g->st[0]);
-  for (uint32_t i = 1; i < n && c == hipSuccess; ++i) {
-    (void)hipSetDevice(g->dev[i]);
-    c = hipStreamSynchronize(g->st[i]);
-  }
+  const hipError_t c = wait_members(g);  // (an all-reduce ends on every member's stream)
   if (a != hipSuccess || b != hipSuccess || c != hipSuccess) {
     delete h;
     return gfail(g, SA_EDEVICE, "group window read failed");
   }
   h->cms.resize(g->cms_elems);
   for (size_t i = 0; i < c64.size(); ++i) h->cms[i] = c64[i] > UINT32_MAX ? UINT32_MAX : (uint32_t)c64[i];
-  h->r.window_id = window_id;
-  h->r.n_services = g->cfg.n_services;
-  h->r.hll_p = g->cfg.hll_p;
-  h->r.hll = h->hll.data();
-  h->r.cms_d = g->cfg.cms_d;
-  h->r.cms_w = g->cfg.cms_w;
-  h->r.cms = h->cms.data();
+  h->wire(window_id, g->cfg);
   *out = &h->r;
   return SA_OK;
 }
+
+// The window queries.  Each reads as: the arguments (sa_query_args.h; the
+// members check the spans against their rings), every member's export into its
+// group buffers, the members' arrays merged (reduce_members), and the finish on
+// member 0 -- or a scan on every member -- before the one ending (end_query).
+// A query that fails, at any step, drains every member's stream before it
+// returns.
 
 // Each member merges its own windows first..last on its device (registers
 // max-merged, cells summed), the transport merges the members' arrays as for
@@ -1094,81 +1174,21 @@ int sa_group_window_range(sa_group *g, uint64_t first, uint64_t last, const uint
                           uint32_t flags, sa_range_result **out) {
   if (!g || !out) return SA_EINVAL;
   *out = nullptr;
-  if (n_keys && !keys) return gfail(g, SA_EINVAL, "window range: n_keys != 0 with null keys");
-  if (flags & ~(SA_RANGE_REGISTERS | SA_RANGE_CELLS)) return gfail(g, SA_EINVAL, "window range: unknown flag bits");
-  const uint32_t n = (uint32_t)g->eng.size();
-  for (uint32_t i = 0; i < n; ++i) {
-    if (int rc = ensure(g, g->dev[i], g->hll[i], g->hll_bytes)) return rc;
-    if (int rc = ensure(g, g->dev[i], g->cms[i], g->cms_elems * 8)) return rc;
-    if (int rc = sa_grp::window_range_export_async(g->eng[i], first, last, static_cast<uint8_t *>(g->hll[i].p),
-                                                   static_cast<uint64_t *>(g->cms[i].p), g->st[i]))
-      return member_error(g, i, rc, "window range");
-  }
-  if (g->rccl) {
-    SG_NCCL(g, ncclGroupStart());
-    for (uint32_t i = 0; i < n; ++i) {
-      SG_NCCL(g, ncclAllReduce(g->hll[i].p, g->hll[i].p, g->hll_bytes, ncclUint8, ncclMax, g->comm[i], g->st[i]));
-      SG_NCCL(g, ncclAllReduce(g->cms[i].p, g->cms[i].p, g->cms_elems, ncclUint64, ncclSum, g->comm[i], g->st[i]));
-    }
-    SG_NCCL(g, ncclGroupEnd());
-  } else {
-    if (int rc = copy_reduce(g, g->hll, g->hll_bytes, true)) return rc;
-    if (int rc = copy_reduce(g, g->cms, g->cms_elems, false)) return rc;
-  }
-  const int rc = sa_grp::window_range_finish(g->eng[0], first, last, static_cast<const uint8_t *>(g->hll[0].p),
-                                             static_cast<const uint64_t *>(g->cms[0].p), keys, n_keys, flags, g->st[0],
-                                             out);
-  hipError_t st = hipSuccess;
-  for (uint32_t i = 1; i < n && st == hipSuccess; ++i) {  // (an all-reduce ends on every member's stream)
-    st = hipSetDevice(g->dev[i]);
-    if (st == hipSuccess) st = hipStreamSynchronize(g->st[i]);
-  }
-  if (rc) return member_error(g, 0, rc, "window range");
-  if (st != hipSuccess) {
-    sa_range_result_free(*out);
-    *out = nullptr;
-    return gfail(g, SA_EDEVICE, std::string("window range: ") + hipGetErrorString(st));
-  }
-  return SA_OK;
-}
-
-// The members' cell arrays of every `which` (on their streams) summed, the sums
-// left on every member's device before its stream goes on: RCCL's all-reduce
-// leaves them there; the copy transport copies member 0's sums back.
-static int sum_cells_everywhere(sa_group *g, std::initializer_list<std::vector<Buf> *> which) {
-  const uint32_t n = (uint32_t)g->eng.size();
-  if (g->rccl) {
-    SG_NCCL(g, ncclGroupStart());
-    for (std::vector<Buf> *b : which)
-      for (uint32_t i = 0; i < n; ++i)
-        SG_NCCL(g, ncclAllReduce((*b)[i].p, (*b)[i].p, g->cms_elems, ncclUint64, ncclSum, g->comm[i], g->st[i]));
-    SG_NCCL(g, ncclGroupEnd());
-  } else if (n > 1) {
-    for (std::vector<Buf> *b : which) {
-      if (int rc = copy_reduce(g, *b, g->cms_elems, false)) return rc;  // (the members' streams are drained)
-      SG_HIP(g, hipSetDevice(g->dev[0]));
-      for (uint32_t i = 1; i < n; ++i) {
-        if (g->dev[i] == g->dev[0])
-          SG_HIP(g, hipMemcpyAsync((*b)[i].p, (*b)[0].p, g->cms_elems * 8, hipMemcpyDeviceToDevice, g->st[0]));
-        else
-          SG_HIP(g, hipMemcpyPeerAsync((*b)[i].p, g->dev[i], (*b)[0].p, g->dev[0], g->cms_elems * 8, g->st[0]));
-      }
-    }
-    SG_HIP(g, hipStreamSynchronize(g->st[0]));  // the sums are on every member before its scan starts
-  }
-  return SA_OK;
-}
-
-// Waits for every member's stream (also after a failure: copies into host
-// results may be in flight); the first error met.
-static hipError_t wait_members(sa_group *g) {
-  hipError_t st = hipSuccess;
-  for (uint32_t i = 0; i < g->eng.size(); ++i) {
-    hipError_t a = hipSetDevice(g->dev[i]);
-    if (a == hipSuccess) a = hipStreamSynchronize(g->st[i]);
-    if (st == hipSuccess) st = a;
-  }
-  return st;
+  const char *const what = "window range";
+  if (const char *bad = sa_args::keys(keys, n_keys)) return bad_args(g, SA_EINVAL, what, bad);
+  if (const char *bad = sa_args::flags(flags, SA_RANGE_REGISTERS | SA_RANGE_CELLS)) return bad_args(g, SA_EINVAL, what, bad);
+  const std::vector<Part> parts = {regs_part(g), cells_part(g, g->cms)};
+  if (int rc = ensure_parts(g, parts)) return rc;
+  int rc = each_member(g, what, [&](uint32_t i) {
+    return sa_grp::window_range_export_async(g->eng[i], first, last, buf<uint8_t>(g->hll, i), buf<uint64_t>(g->cms, i),
+                                             g->st[i]);
+  });
+  const int merged = rc ? SA_OK : reduce_members(g, parts);
+  if (!rc && !merged)
+    if (int f = sa_grp::window_range_finish(g->eng[0], first, last, buf<uint8_t>(g->hll, 0), buf<uint64_t>(g->cms, 0), keys,
+                                            n_keys, flags, g->st[0], out))
+      rc = member_error(g, 0, f, what);
+  return end_query(g, what, rc, merged, out, sa_range_result_free);
 }
 
 // The members' cells merged as for sa_group_window_range and left on every
@@ -1179,27 +1199,22 @@ int sa_group_window_top(sa_group *g, uint64_t first, uint64_t last, uint32_t k, 
                         sa_top_result **out) {
   if (!g || !out) return SA_EINVAL;
   *out = nullptr;
-  if (k == 0 || k > SA_TOP_MAX_K) return gfail(g, SA_EINVAL, "window top: k outside 1..SA_TOP_MAX_K");
-  if (flags) return gfail(g, SA_EINVAL, "window top: flags are reserved (0)");
-  const uint32_t n = (uint32_t)g->eng.size();
-  for (uint32_t i = 0; i < n; ++i) {
-    if (int rc = ensure(g, g->dev[i], g->cms[i], g->cms_elems * 8)) return rc;
-    if (int rc = sa_grp::window_range_export_async(g->eng[i], first, last, nullptr, static_cast<uint64_t *>(g->cms[i].p),
-                                                   g->st[i]))
-      return member_error(g, i, rc, "window top");
-  }
-  if (int rc = sum_cells_everywhere(g, {&g->cms})) return rc;
-  std::vector<sa_grp::TopHost> th(n);
-  int rc = SA_OK;
-  uint32_t started = 0;
-  for (; started < n && rc == SA_OK; ++started)
-    rc = sa_grp::window_top_async(g->eng[started], static_cast<const uint64_t *>(g->cms[started].p), k, min_count,
-                                  g->st[started], &th[started]);
-  const uint32_t failed = started - 1;  // (when rc != SA_OK)
-  const hipError_t st = wait_members(g);
-  if (rc) return member_error(g, failed, rc, "window top");
-  if (st != hipSuccess) return gfail(g, SA_EDEVICE, std::string("window top: ") + hipGetErrorString(st));
-  if (int rc2 = sa_grp::top_result(first, last, k, th.data(), n, out))
+  const char *const what = "window top";
+  if (const char *bad = sa_args::top_k(k)) return bad_args(g, SA_EINVAL, what, bad);
+  if (const char *bad = sa_args::flags(flags, 0)) return bad_args(g, SA_EINVAL, what, bad);
+  const std::vector<Part> parts = {cells_part(g, g->cms)};
+  if (int rc = ensure_parts(g, parts)) return rc;
+  int rc = each_member(g, what, [&](uint32_t i) {
+    return sa_grp::window_range_export_async(g->eng[i], first, last, nullptr, buf<uint64_t>(g->cms, i), g->st[i]);
+  });
+  const int merged = rc ? SA_OK : sum_cells_everywhere(g, parts);
+  std::vector<sa_grp::TopHost> th(g->eng.size());
+  if (!rc && !merged)
+    rc = each_member(g, what, [&](uint32_t i) {
+      return sa_grp::window_top_async(g->eng[i], buf<uint64_t>(g->cms, i), k, min_count, g->st[i], &th[i]);
+    });
+  if (int end = end_query(g, what, rc, merged, out, sa_top_result_free)) return end;
+  if (int rc2 = sa_grp::top_result(first, last, k, th.data(), (uint32_t)th.size(), out))
     return gfail(g, rc2, "window top: the result does not fit in host memory");
   return SA_OK;
 }
@@ -1211,33 +1226,28 @@ int sa_group_window_movers(sa_group *g, uint64_t base_first, uint64_t base_last,
                            uint32_t k, uint64_t min_score, uint32_t flags, sa_movers_result **out) {
   if (!g || !out) return SA_EINVAL;
   *out = nullptr;
-  if (k == 0 || k > SA_TOP_MAX_K) return gfail(g, SA_EINVAL, "window movers: k outside 1..SA_TOP_MAX_K");
-  if (flags & ~SA_MOVERS_FALL) return gfail(g, SA_EINVAL, "window movers: unknown flag bits");
-  const uint32_t n = (uint32_t)g->eng.size();
-  for (uint32_t i = 0; i < n; ++i) {
-    if (int rc = ensure(g, g->dev[i], g->cms_base[i], g->cms_elems * 8)) return rc;
-    if (int rc = ensure(g, g->dev[i], g->cms[i], g->cms_elems * 8)) return rc;
-    if (int rc = sa_grp::window_range_export_async(g->eng[i], base_first, base_last, nullptr,
-                                                   static_cast<uint64_t *>(g->cms_base[i].p), g->st[i]))
-      return member_error(g, i, rc, "window movers");
-    if (int rc = sa_grp::window_range_export_async(g->eng[i], cur_first, cur_last, nullptr,
-                                                   static_cast<uint64_t *>(g->cms[i].p), g->st[i]))
-      return member_error(g, i, rc, "window movers");
-  }
-  if (int rc = sum_cells_everywhere(g, {&g->cms_base, &g->cms})) return rc;
-  std::vector<sa_grp::MoversHost> mh(n);
-  int rc = SA_OK;
-  uint32_t started = 0;
-  for (; started < n && rc == SA_OK; ++started)
-    rc = sa_grp::window_movers_async(g->eng[started], static_cast<const uint64_t *>(g->cms_base[started].p),
-                                     static_cast<const uint64_t *>(g->cms[started].p), base_last - base_first + 1,
-                                     cur_last - cur_first + 1, k, min_score, flags, g->st[started], &mh[started]);
-  const uint32_t failed = started - 1;  // (when rc != SA_OK)
-  const hipError_t st = wait_members(g);
-  if (rc) return member_error(g, failed, rc, "window movers");
-  if (st != hipSuccess) return gfail(g, SA_EDEVICE, std::string("window movers: ") + hipGetErrorString(st));
+  const char *const what = "window movers";
+  if (const char *bad = sa_args::top_k(k)) return bad_args(g, SA_EINVAL, what, bad);
+  if (const char *bad = sa_args::flags(flags, SA_MOVERS_FALL)) return bad_args(g, SA_EINVAL, what, bad);
+  const std::vector<Part> parts = {cells_part(g, g->cms_base), cells_part(g, g->cms)};
+  if (int rc = ensure_parts(g, parts)) return rc;
+  int rc = each_member(g, what, [&](uint32_t i) {
+    if (int b = sa_grp::window_range_export_async(g->eng[i], base_first, base_last, nullptr, buf<uint64_t>(g->cms_base, i),
+                                                  g->st[i]))
+      return b;
+    return sa_grp::window_range_export_async(g->eng[i], cur_first, cur_last, nullptr, buf<uint64_t>(g->cms, i), g->st[i]);
+  });
+  const int merged = rc ? SA_OK : sum_cells_everywhere(g, parts);
+  std::vector<sa_grp::MoversHost> mh(g->eng.size());
+  if (!rc && !merged)
+    rc = each_member(g, what, [&](uint32_t i) {
+      return sa_grp::window_movers_async(g->eng[i], buf<uint64_t>(g->cms_base, i), buf<uint64_t>(g->cms, i),
+                                         base_last - base_first + 1, cur_last - cur_first + 1, k, min_score, flags,
+                                         g->st[i], &mh[i]);
+    });
+  if (int end = end_query(g, what, rc, merged, out, sa_movers_result_free)) return end;
   const uint64_t range[4] = {base_first, base_last, cur_first, cur_last};
-  if (int rc2 = sa_grp::movers_result(range, k, flags, mh.data(), n, out))
+  if (int rc2 = sa_grp::movers_result(range, k, flags, mh.data(), (uint32_t)mh.size(), out))
     return gfail(g, rc2, "window movers: the result does not fit in host memory");
   return SA_OK;
 }
@@ -1250,37 +1260,21 @@ int sa_group_window_overlap(sa_group *g, uint64_t first, uint64_t last, const ui
                             uint32_t flags, sa_overlap_result **out) {
   if (!g || !out) return SA_EINVAL;
   *out = nullptr;
-  if (flags) return gfail(g, SA_EINVAL, "window overlap: flags are reserved (0)");
+  const char *const what = "window overlap";
+  if (const char *bad = sa_args::flags(flags, 0)) return bad_args(g, SA_EINVAL, what, bad);
   std::vector<uint32_t> sel;
-  if (const char *bad = sa_grp::overlap_select(g->cfg.n_services, services, n_sel, &sel)) return gfail(g, SA_EINVAL, bad);
-  const uint32_t n = (uint32_t)g->eng.size();
-  for (uint32_t i = 0; i < n; ++i) {
-    if (int rc = ensure(g, g->dev[i], g->hll[i], g->hll_bytes)) return rc;
-    if (int rc = sa_grp::window_overlap_export_async(g->eng[i], first, last, static_cast<uint8_t *>(g->hll[i].p), g->st[i]))
-      return member_error(g, i, rc, "window overlap");
-  }
-  if (g->rccl) {
-    SG_NCCL(g, ncclGroupStart());
-    for (uint32_t i = 0; i < n; ++i)
-      SG_NCCL(g, ncclAllReduce(g->hll[i].p, g->hll[i].p, g->hll_bytes, ncclUint8, ncclMax, g->comm[i], g->st[i]));
-    SG_NCCL(g, ncclGroupEnd());
-  } else {
-    if (int rc = copy_reduce(g, g->hll, g->hll_bytes, true)) return rc;
-  }
-  const int rc = sa_grp::window_overlap_finish(g->eng[0], first, last, static_cast<const uint8_t *>(g->hll[0].p), sel,
-                                               g->st[0], out);
-  hipError_t st = hipSuccess;
-  for (uint32_t i = 1; i < n && st == hipSuccess; ++i) {  // (an all-reduce ends on every member's stream)
-    st = hipSetDevice(g->dev[i]);
-    if (st == hipSuccess) st = hipStreamSynchronize(g->st[i]);
-  }
-  if (rc) return member_error(g, 0, rc, "window overlap");
-  if (st != hipSuccess) {
-    sa_overlap_result_free(*out);
-    *out = nullptr;
-    return gfail(g, SA_EDEVICE, std::string("window overlap: ") + hipGetErrorString(st));
-  }
-  return SA_OK;
+  if (const char *bad = sa_args::overlap_select(g->cfg.n_services, services, n_sel, &sel))
+    return bad_args(g, SA_EINVAL, what, bad);
+  const std::vector<Part> parts = {regs_part(g)};
+  if (int rc = ensure_parts(g, parts)) return rc;
+  int rc = each_member(g, what, [&](uint32_t i) {
+    return sa_grp::window_overlap_export_async(g->eng[i], first, last, buf<uint8_t>(g->hll, i), g->st[i]);
+  });
+  const int merged = rc ? SA_OK : reduce_members(g, parts);
+  if (!rc && !merged)
+    if (int f = sa_grp::window_overlap_finish(g->eng[0], first, last, buf<uint8_t>(g->hll, 0), sel, g->st[0], out))
+      rc = member_error(g, 0, f, what);
+  return end_query(g, what, rc, merged, out, sa_overlap_result_free);
 }
 
 // Each member takes the sliding sums of its own ring for the selected
@@ -1291,51 +1285,27 @@ int sa_group_window_latency(sa_group *g, uint64_t first, uint64_t last, uint32_t
                             sa_latency_result **out) {
   if (!g || !out) return SA_EINVAL;
   *out = nullptr;
-  if (!(g->cfg.options & SA_OPT_WINDOW_LATENCY))
-    return gfail(g, SA_ESTATE, "window latency: the group was not created with SA_OPT_WINDOW_LATENCY");
+  const char *const what = "window latency";
+  if (const char *bad = sa_args::latency_option(g->cfg.options)) return bad_args(g, SA_ESTATE, what, bad);
   std::vector<uint32_t> sel;
-  if (const char *bad = sa_grp::latency_args(g->cfg.n_services, services, n_sel, q_ppm, n_q, flags, &sel))
-    return gfail(g, SA_EINVAL, bad);
+  if (const char *bad = sa_args::latency_args(g->cfg.n_services, services, n_sel, q_ppm, n_q, flags, &sel))
+    return bad_args(g, SA_EINVAL, what, bad);
   // (the members check the span against their rings; a span that passes has n_out <= n_windows)
-  if (first <= last && last - first < g->cfg.n_windows)
-    if (const char *bad = sa_grp::latency_rows(last - first + 1, sel.size(), flags)) return gfail(g, SA_EINVAL, bad);
-  const uint32_t n = (uint32_t)g->eng.size();
-  const uint64_t elems = first <= last && last - first < g->cfg.n_windows ? (last - first + 1) * sel.size() * SA_LAT_BINS : 1;
-  for (uint32_t i = 0; i < n; ++i)  // (before any member reads `sel`: nothing below returns without a wait)
-    if (int rc = ensure(g, g->dev[i], g->lat[i], elems * 8)) return rc;
-  int rc = SA_OK;
-  uint32_t at = 0;  // the member rc is about
-  for (; at < n && rc == SA_OK; ++at)
-    rc = sa_grp::window_latency_export_async(g->eng[at], first, last, width, sel, static_cast<uint64_t *>(g->lat[at].p),
-                                             g->st[at]);
-  at -= 1;
-  auto merge = [&]() -> int {
-    if (g->rccl) {
-      SG_NCCL(g, ncclGroupStart());
-      for (uint32_t i = 0; i < n; ++i)
-        SG_NCCL(g, ncclAllReduce(g->lat[i].p, g->lat[i].p, elems, ncclUint64, ncclSum, g->comm[i], g->st[i]));
-      SG_NCCL(g, ncclGroupEnd());
-      return SA_OK;
-    }
-    return copy_reduce(g, g->lat, elems, false);
-  };
-  const int merged = rc == SA_OK ? merge() : SA_OK;
-  if (rc == SA_OK && merged == SA_OK) {
-    at = 0;
-    rc = sa_grp::window_latency_finish(g->eng[0], first, last, width, sel, q_ppm, n_q, flags,
-                                       static_cast<const uint64_t *>(g->lat[0].p), g->st[0], out);
-  }
-  // every member's stream, also after a failure: the copies out of `sel` may be
-  // in flight, and an all-reduce ends on every member's stream
-  const hipError_t st = wait_members(g);
-  if (rc) return member_error(g, at, rc, "window latency");
-  if (merged) return merged;
-  if (st != hipSuccess) {
-    sa_latency_result_free(*out);
-    *out = nullptr;
-    return gfail(g, SA_EDEVICE, std::string("window latency: ") + hipGetErrorString(st));
-  }
-  return SA_OK;
+  const uint64_t n_out = first <= last && last - first < g->cfg.n_windows ? last - first + 1 : 0;
+  if (n_out)
+    if (const char *bad = sa_args::latency_rows(n_out, sel.size(), flags)) return bad_args(g, SA_EINVAL, what, bad);
+  // every member's sums [n_out][n_sel][SA_LAT_BINS]
+  const std::vector<Part> parts = {{&g->lat, n_out ? n_out * sel.size() * SA_LAT_BINS : 1, false}};
+  if (int rc = ensure_parts(g, parts)) return rc;
+  int rc = each_member(g, what, [&](uint32_t i) {  // (the copies out of `sel` end before end_query returns)
+    return sa_grp::window_latency_export_async(g->eng[i], first, last, width, sel, buf<uint64_t>(g->lat, i), g->st[i]);
+  });
+  const int merged = rc ? SA_OK : reduce_members(g, parts);
+  if (!rc && !merged)
+    if (int f = sa_grp::window_latency_finish(g->eng[0], first, last, width, sel, q_ppm, n_q, flags,
+                                              buf<uint64_t>(g->lat, 0), g->st[0], out))
+      rc = member_error(g, 0, f, what);
+  return end_query(g, what, rc, merged, out, sa_latency_result_free);
 }
 
 // Each member sums both ranges of its own ring, the transport adds the
@@ -1347,44 +1317,22 @@ int sa_group_window_latency_movers(sa_group *g, uint64_t base_first, uint64_t ba
                                    sa_latency_movers_result **out) {
   if (!g || !out) return SA_EINVAL;
   *out = nullptr;
-  if (!(g->cfg.options & SA_OPT_WINDOW_LATENCY))
-    return gfail(g, SA_ESTATE, "window latency movers: the group was not created with SA_OPT_WINDOW_LATENCY");
-  if (const char *bad = sa_grp::latency_movers_args(k, q_ppm, n_q, flags)) return gfail(g, SA_EINVAL, bad);
+  const char *const what = "window latency movers";
+  if (const char *bad = sa_args::latency_option(g->cfg.options)) return bad_args(g, SA_ESTATE, what, bad);
+  if (const char *bad = sa_args::latency_movers_args(k, q_ppm, n_q, flags)) return bad_args(g, SA_EINVAL, what, bad);
   const uint64_t range[4] = {base_first, base_last, cur_first, cur_last};
-  const uint32_t n = (uint32_t)g->eng.size();
-  const uint64_t elems = 2ull * g->cfg.n_services * SA_LAT_BINS;
-  for (uint32_t i = 0; i < n; ++i)
-    if (int rc = ensure(g, g->dev[i], g->lat[i], elems * 8)) return rc;
-  int rc = SA_OK;
-  uint32_t at = 0;  // the member rc is about
-  for (; at < n && rc == SA_OK; ++at)
-    rc = sa_grp::window_latency_movers_export_async(g->eng[at], range, static_cast<uint64_t *>(g->lat[at].p), g->st[at]);
-  at -= 1;
-  auto merge = [&]() -> int {
-    if (g->rccl) {
-      SG_NCCL(g, ncclGroupStart());
-      for (uint32_t i = 0; i < n; ++i)
-        SG_NCCL(g, ncclAllReduce(g->lat[i].p, g->lat[i].p, elems, ncclUint64, ncclSum, g->comm[i], g->st[i]));
-      SG_NCCL(g, ncclGroupEnd());
-      return SA_OK;
-    }
-    return copy_reduce(g, g->lat, elems, false);
-  };
-  const int merged = rc == SA_OK ? merge() : SA_OK;
-  if (rc == SA_OK && merged == SA_OK) {
-    at = 0;
-    rc = sa_grp::window_latency_movers_finish(g->eng[0], range, k, min_count, min_shift, q_ppm, n_q, flags,
-                                              static_cast<const uint64_t *>(g->lat[0].p), g->st[0], out);
-  }
-  const hipError_t st = wait_members(g);  // (also after a failure; an all-reduce ends on every member's stream)
-  if (rc) return member_error(g, at, rc, "window latency movers");
-  if (merged) return merged;
-  if (st != hipSuccess) {
-    sa_latency_movers_result_free(*out);
-    *out = nullptr;
-    return gfail(g, SA_EDEVICE, std::string("window latency movers: ") + hipGetErrorString(st));
-  }
-  return SA_OK;
+  // every member's sums of both ranges [2][n_services][SA_LAT_BINS]
+  const std::vector<Part> parts = {{&g->lat, 2ull * g->cfg.n_services * SA_LAT_BINS, false}};
+  if (int rc = ensure_parts(g, parts)) return rc;
+  int rc = each_member(g, what, [&](uint32_t i) {
+    return sa_grp::window_latency_movers_export_async(g->eng[i], range, buf<uint64_t>(g->lat, i), g->st[i]);
+  });
+  const int merged = rc ? SA_OK : reduce_members(g, parts);
+  if (!rc && !merged)
+    if (int f = sa_grp::window_latency_movers_finish(g->eng[0], range, k, min_count, min_shift, q_ppm, n_q, flags,
+                                                     buf<uint64_t>(g->lat, 0), g->st[0], out))
+      rc = member_error(g, 0, f, what);
+  return end_query(g, what, rc, merged, out, sa_latency_movers_result_free);
 }
 
 int sa_group_window_advance(sa_group *g, uint64_t new_base) {

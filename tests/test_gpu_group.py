@@ -5,13 +5,18 @@ device copies + a reduce kernel, a group of one with SA_OPT_GROUP_RCCL
 merges over a one-rank RCCL communicator.  Bar: the merge equals the CPU
 oracle fed the whole stream (bucket counts, calls, ns sums, HLL registers and
 count-min cells bit-exact; duration sums within 1e-9 relative)."""
+import dataclasses
+import functools
+
 import numpy as np
 import pytest
 
 import pyoracle
+from geometry_util import key_pool, make_batch, ring_start
 from parity_util import assert_red_equal
-from spanagg._lib import OPT_GROUP_COPY, OPT_GROUP_RCCL
-from spanagg import Config, Engine, Group
+from spanagg import _lib
+from spanagg._lib import OPT_GROUP_COPY, OPT_GROUP_RCCL, OPT_WINDOW_LATENCY
+from spanagg import Config, Engine, Group, SpanAggError, SpanBatch
 from spanagg.synth import generate_c2, generate_highcard
 
 pytestmark = pytest.mark.gpu
@@ -109,3 +114,126 @@ def test_group_exponential_histograms_fold_to_one_engine(devices):
         o = pyoracle.Oracle(n_services=wl.n_services)
         o.ingest(wl.batch)
         _check_windows(g, o)
+
+
+# ---- the window queries: one merge path and one ending for all of them -------
+# Two members on device 0 merge through device copies; a group of one that asks
+# for RCCL all-reduces for real.  (The queries' own files, test_gpu_window_*.py,
+# hold each query's group case against the oracle on larger rings; here every
+# group query runs on both transports against one engine, and after a failure.)
+QCFG = Config(n_services=3, n_windows=4, key_capacity=1500, options=OPT_WINDOW_LATENCY)
+TRANSPORTS = [([0, 0], OPT_GROUP_COPY, False), ([0], OPT_GROUP_RCCL, True)]
+SUMMED = ("n_resident", "n_matched")  # of top and movers: a group's are its members' sums
+
+
+@functools.lru_cache(maxsize=1)
+def _query_case():
+    """The ring's first window and 2,000 spans over its four windows, ~30 % of them ERROR."""
+    return ring_start(QCFG), make_batch(np.random.default_rng(0x9A7E), 2000, QCFG, 300)
+
+
+def _queries(base, last=None, k=10):
+    """name -> the call on an Engine or a Group; `last` and `k` as the failing calls bend them."""
+    first, last = base, base + 3 if last is None else last
+    keys = key_pool(300)[:16]
+    return {
+        "window_read": lambda x: x.window_read(first + 1),
+        "window_range": lambda x: x.window_range(first, last, keys, registers=True, cells=True),
+        "window_top": lambda x: x.window_top(first, last, k),
+        "window_movers": lambda x: x.window_movers((first, first + 1), (first + 2, last), k),
+        "window_overlap": lambda x: x.window_overlap(first, last),
+        "window_latency": lambda x: x.window_latency_series(first + 1, last, 2, hist=True),
+        "window_latency_movers": lambda x: x.window_latency_movers((first, first + 1), (first + 2, last), min(k, 3)),
+    }
+
+
+def _loaded(cls, *args):
+    base, batch = _query_case()
+    x = cls(*args)
+    x.window_advance(base)
+    x.ingest(batch)
+    return x
+
+
+def _same(a, b, what, skip=()):
+    """Two results of one dataclass, bit for bit (the float columns too)."""
+    assert type(a) is type(b), what
+    for f in dataclasses.fields(a):
+        va, vb = getattr(a, f.name), getattr(b, f.name)
+        if f.name in skip:
+            continue
+        if isinstance(va, np.ndarray):
+            assert va.dtype == vb.dtype and va.shape == vb.shape and va.tobytes() == vb.tobytes(), (what, f.name)
+        else:
+            assert va == vb, (what, f.name, va, vb)
+
+
+def _raises(code, call):
+    with pytest.raises(SpanAggError) as x:
+        call()
+    assert x.value.code == code, x.value
+
+
+@pytest.mark.parametrize("devices,option,rccl", TRANSPORTS, ids=["copy", "rccl"])
+def test_window_queries_equal_one_engine(devices, option, rccl):
+    base, batch = _query_case()
+    n = len(devices)
+    shards = [SpanBatch(*[col[batch.trace_w1 % np.uint64(n) == i] for col in batch.columns()]) for i in range(n)]
+    with _loaded(Group, devices, dataclasses.replace(QCFG, options=QCFG.options | option)) as g, _loaded(Engine, QCFG) as e:
+        assert g.size == n and g.uses_rccl == rccl
+        members = []
+        for sh in shards if n > 1 else []:  # what each member holds: one engine a shard
+            m = Engine(QCFG)
+            m.window_advance(base)
+            m.ingest(sh)
+            members.append(m)
+        try:
+            got, resident = {}, {}
+            for name, call in _queries(base).items():
+                got[name] = rg = call(g)
+                summed = n > 1 and name in ("window_top", "window_movers")
+                _same(rg, call(e), name, skip=SUMMED if summed else ())
+                if summed:  # every member's candidates are the series it holds
+                    resident[name] = [call(m).n_resident for m in members]
+                    assert rg.n_resident == sum(resident[name]), name
+            if members:
+                # ... and its matches those of them that pass on the merged cells, which one engine's
+                # point queries give: an estimate >= 1, a score current * 2 - baseline * 2 >= 1
+                held = [m.flush().key_hash for m in members]
+                assert [len(h) for h in held] == resident["window_top"] == resident["window_movers"]
+                est = lambda a, b, h: e.window_range(a, b, h).errors.astype(np.int64)
+                assert got["window_top"].n_matched == sum(int((est(base, base + 3, h) >= 1).sum()) for h in held)
+                assert got["window_movers"].n_matched == sum(
+                    int((2 * est(base + 2, base + 3, h) - 2 * est(base, base + 1, h) >= 1).sum()) for h in held)
+            # the answers are not empty ones
+            top, lat = _queries(base)["window_top"](g), _queries(base)["window_latency"](g)
+            assert len(top.keys) == 10 and top.error_spans > 100 and lat.count.sum() > 2000
+            assert _queries(base)["window_latency_movers"](g).spans_cur > 500
+        finally:
+            for m in members:
+                m.close()
+
+
+@pytest.mark.parametrize("devices,option,rccl", TRANSPORTS, ids=["copy", "rccl"])
+def test_a_failed_window_query_leaves_the_next_one_right(devices, option, rccl):
+    """A range one past the ring (SA_ERANGE, found by the members) and k = 0
+    (SA_EINVAL, found by the group): the group drains its members' streams
+    before it returns either, and the next valid query answers as one engine."""
+    base, _ = _query_case()
+    valid = _queries(base)
+    past, k0 = _queries(base, last=base + 4), _queries(base, k=0)
+    with _loaded(Group, devices, dataclasses.replace(QCFG, options=QCFG.options | option)) as g, _loaded(Engine, QCFG) as e:
+        assert g.uses_rccl == rccl
+        want = {name: call(e) for name, call in valid.items()}
+        skip = SUMMED if len(devices) > 1 else ()
+        for name in valid:
+            if name == "window_read":
+                continue
+            _raises(_lib.SA_ERANGE, lambda: past[name](g))
+            assert "member" in g.lib.sa_group_last_error(g._h).decode(), name  # reported as a member's error
+            _same(valid[name](g), want[name], (name, "after SA_ERANGE"), skip)
+            if name in ("window_top", "window_movers", "window_latency_movers"):
+                _raises(_lib.SA_EINVAL, lambda: k0[name](g))
+                _same(valid[name](g), want[name], (name, "after SA_EINVAL"), skip)
+        for name in valid:  # and every query after every failure
+            _same(valid[name](g), want[name], (name, "at the end"), skip)
