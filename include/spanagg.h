@@ -24,6 +24,7 @@
  *   (new) series whose ERROR rate changed most      sa_window_movers (key table against two ranges' cells on the device)
  *   (new) duration quantiles per service and window sa_window_latency (log-linear histograms in the ring, SA_OPT_WINDOW_LATENCY)
  *   (new) services whose latency shifted most       sa_window_latency_movers (two ranges' histograms summed, scored and selected on the device)
+ *   (new) latency SLO burn over sliding widths      sa_window_slo (rows cut to (total, slow) pairs at a threshold, prefix sums on the device)
  *
  * Boundary rules (mirroring the connector's contracts):
  *  - Ownership: batches are borrowed for the duration of the call (page-locked
@@ -657,6 +658,68 @@ int sa_window_latency_movers(sa_engine *e, uint64_t base_first, uint64_t base_la
                              sa_latency_movers_result **out);
 void sa_latency_movers_result_free(sa_latency_movers_result *r);
 
+/* ---- latency SLO burn over sliding widths (SA_OPT_WINDOW_LATENCY) ----
+ * "What share of checkout's requests were slower than its target over the last
+ * 5 minutes and over the last hour, at every window, and is the error budget
+ * burning": the multi-window, multi-burn-rate alert.  A threshold turns a
+ * service's SA_LAT_BINS-bin row into a (total, slow) pair, so every width
+ * slides over 16 bytes a window, the ring is read once whatever the widths,
+ * and only the pairs' sums and the verdicts cross the bus.  No state beyond
+ * sa_window_latency's. */
+#define SA_SLO_MAX_WIDTHS 4u
+typedef struct {
+    uint64_t first_window, last_window;   /* outputs t = first..last, inclusive */
+    uint32_t n_out, n_sel, n_widths, pad;
+    uint64_t min_count;                   /* as applied: max(min_count, 1) */
+    const uint32_t *services;      /* [n_sel] ids, in the caller's order */
+    const uint32_t *widths;        /* [n_widths] as given */
+    const uint32_t *limit_ppm;     /* [n_widths] as given */
+    const uint64_t *threshold_ns;  /* [n_sel] as given */
+    const uint8_t  *threshold_bin; /* [n_sel] sa_latency_bin(threshold_ns[i]) */
+    const uint64_t *effective_ns;  /* [n_sel] that bin's upper bound: "slow" means d > effective_ns */
+    const uint64_t *total;         /* [n_out][n_widths][n_sel] spans of windows t-widths[w]+1 .. t */
+    const uint64_t *slow;          /* [n_out][n_widths][n_sel] of those, spans in bins > threshold_bin */
+    const uint8_t  *burning;       /* [n_out][n_sel] bit w set when width w burns (below) */
+    const uint32_t *alert_outputs; /* [n_sel] outputs whose n_widths low bits are all set */
+} sa_slo_result;
+
+/* Slow: with b = sa_latency_bin(threshold_ns[i]), a span of service
+ * services[i] is slow when its bin is greater than b; spans in bin b itself
+ * count as fast.  So `slow` counts exactly the spans with d > effective_ns,
+ * the upper bound of bin b: exact with respect to the caller's threshold when
+ * that is a bin's upper bound from sa_latency_bin_bounds, else a lower bound
+ * within one bin (12.5 %).  A threshold in bin 255 makes `slow` 0 everywhere.
+ * Counts: total[t][w][i] is bit for bit the count of sa_window_latency(e, t,
+ * t, widths[w], &services[i], 1, ..), and slow[t][w][i] the sum of that call's
+ * SA_LAT_HIST row over the bins above threshold_bin[i].  Which spans count is
+ * sa_window_latency's rule.
+ * Burn: width w burns at (t, i) when total >= max(min_count, 1) and slow *
+ * 10^6 > limit_ppm[w] * total -- strictly; both products are taken in u64 and
+ * are exact while counts stay below 2^44, sa_window_latency's bound.  The
+ * caller folds objective and burn factor into limit_ppm: a 99.9 % objective
+ * at burn 14.4 is 14,400.  alert_outputs[i] counts the outputs at which every
+ * asked width burns: the long-and-short-window rule.
+ * Arguments: 1 <= n_widths <= SA_SLO_MAX_WIDTHS; widths and limit_ppm
+ * non-null, every limit_ppm in 0..10^6; widths in any order, repeats allowed.
+ * The selection as sa_window_latency's: services == NULL with n_sel == 0
+ * selects every service in id order.  threshold_ns is non-null and parallel
+ * to the selection (n_services entries when every service is selected); any
+ * u64 passes.  flags are reserved (0).  n_out * n_sel <= 2^20.
+ * Ordering and waiting as sa_window_latency: joins every launch in flight,
+ * runs on the engine stream, waits once, clears nothing (two calls give equal
+ * bits).  Works on every ingest path: only the latency ring is read.
+ * SA_ESTATE on an engine without SA_OPT_WINDOW_LATENCY; SA_ERANGE when any
+ * width fails sa_window_series' span rule against first..last (every window
+ * first - max(widths) + 1 .. last resident, each width in 1..n_windows);
+ * SA_EINVAL for the argument rules above and a null `out`; SA_ENOMEM when the
+ * device scratch (16 B a covered window and service, twice, and the answers)
+ * or the result cannot be allocated.  The engine stays usable after any
+ * error.  Free the result with sa_slo_result_free. */
+int sa_window_slo(sa_engine *e, uint64_t first, uint64_t last, const uint32_t *widths,
+                  const uint32_t *limit_ppm, uint32_t n_widths, const uint32_t *services, uint32_t n_sel,
+                  const uint64_t *threshold_ns, uint64_t min_count, uint32_t flags, sa_slo_result **out);
+void sa_slo_result_free(sa_slo_result *r);
+
 int sa_get_stats(sa_engine *e, sa_stats *out);
 
 /* ---- multi-GPU merge hooks (device pointers on this engine's device) ----
@@ -790,6 +853,14 @@ int sa_group_window_latency_movers(sa_group *g, uint64_t base_first, uint64_t ba
                                    uint64_t cur_last, uint32_t k, uint64_t min_count, uint32_t min_shift,
                                    const uint32_t *q_ppm, uint32_t n_q, uint32_t flags,
                                    sa_latency_movers_result **out);
+/* sa_window_slo of a group: every member reduces its own ring's covered rows
+ * to (total, slow) pairs on its device, the group's transport adds the
+ * members' pairs (16 B a covered window and service), and member 0's device
+ * slides every width over the sums and judges.  Results equal those of one
+ * engine fed every span, bit for bit. */
+int sa_group_window_slo(sa_group *g, uint64_t first, uint64_t last, const uint32_t *widths,
+                        const uint32_t *limit_ppm, uint32_t n_widths, const uint32_t *services, uint32_t n_sel,
+                        const uint64_t *threshold_ns, uint64_t min_count, uint32_t flags, sa_slo_result **out);
 /* Counters summed over members (n_keys and table_capacity too; window_base and
  * small_table from member 0). */
 int sa_group_get_stats(sa_group *g, sa_stats *out);

@@ -1,6 +1,6 @@
 // engine_latency.cpp -- the queries over the ring of latency histograms of an
-// SA_OPT_WINDOW_LATENCY engine: sa_window_latency and sa_window_latency_movers
-// (kernels in spanagg_latency.hip, the movers' select in spanagg_range.hip),
+// SA_OPT_WINDOW_LATENCY engine: sa_window_latency, sa_window_latency_movers and
+// sa_window_slo (kernels in spanagg_latency.hip, the movers' select in spanagg_range.hip),
 // each with the asynchronous halves the engine group runs per member (sa_grp,
 // sa_group_hooks.h) and its result's free.  Arguments: sa_query_args.h.
 #include <hip/hip_runtime.h>
@@ -127,6 +127,39 @@ hipError_t latency_movers_sums_on(sa_engine *e, const uint64_t range[4], unsigne
                                   (uint32_t)(range[1] - range[0] + 1), range[2], (uint32_t)(range[3] - range[2] + 1),
                                   d_sums, s);
 }
+
+// ---- latency SLO burn (sa_window_slo) ----
+uint32_t slo_max_width(const uint32_t *widths, uint32_t n_widths) { return *std::max_element(widths, widths + n_widths); }
+
+int slo_spans(sa_engine *e, uint64_t first, uint64_t last, const uint32_t *widths, uint32_t n_widths) {
+  if (const char *bad = sa_args::slo_span(first, last, widths, n_widths, e->win_base, e->cfg.n_windows))
+    return bad_args(e, SA_ERANGE, "window slo", bad);
+  return SA_OK;
+}
+
+// Room for a selection of n_sel ids with their threshold bins.
+int slo_selection(sa_engine *e, uint64_t n_sel) {
+  sa_engine::Latency &L = e->lat;
+  const uint64_t want = std::max<uint64_t>(n_sel, 64);
+  if (int rc = grow(e, L.sel, L.sel_cap, want, "window slo: selection hipMalloc failed")) return rc;
+  return grow(e, L.slo_thr, L.slo_thr_cap, want, "window slo: threshold buffer hipMalloc failed");
+}
+
+// A member's part of a query on `s`: the selection and its threshold bins onto
+// the device and the pairs stage behind them, d_pairs [sel.size()][n_cov][2]
+// from window `a` on.  The copies read the caller's pageable `sel` and `bins`
+// asynchronously: as latency_sums_on's.
+hipError_t slo_pairs_on(sa_engine *e, const std::vector<uint32_t> &sel, const std::vector<uint8_t> &bins, uint64_t a,
+                        uint32_t n_cov, unsigned long long *d_pairs, hipStream_t s) {
+  const sa_engine::Latency &L = e->lat;
+  hipError_t st = hipMemcpyAsync(L.sel, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, s);
+  if (st == hipSuccess) st = hipMemcpyAsync(L.slo_thr, bins.data(), bins.size(), hipMemcpyHostToDevice, s);
+  if (st == hipSuccess)
+    st = sa::launch_slo_pairs(L.ring, e->cfg.n_services, e->cfg.n_windows, L.sel, L.slo_thr, (uint32_t)sel.size(), a,
+                              n_cov, d_pairs, s);
+  if (st != hipSuccess) (void)hipStreamSynchronize(s);
+  return st;
+}
 }  // namespace
 
 namespace sa_grp {
@@ -230,6 +263,67 @@ int window_latency_movers_finish(sa_engine *e, const uint64_t range[4], uint32_t
   *out = &h.release()->r;
   return SA_OK;
 }
+
+int window_slo_export_async(sa_engine *e, uint64_t first, uint64_t last, const uint32_t *widths, uint32_t n_widths,
+                            const std::vector<uint32_t> &sel, const std::vector<uint8_t> &bins, uint64_t *d_pairs,
+                            hipStream_t s) {
+  if (!e || !d_pairs || !widths || !n_widths || sel.empty() || bins.size() != sel.size()) return SA_EINVAL;
+  if (int rc = latency_enabled(e, "window slo")) return rc;
+  if (int rc = slo_spans(e, first, last, widths, n_widths)) return rc;
+  if (int rc = begin_read(e)) return rc;
+  if (int rc = slo_selection(e, sel.size())) return rc;
+  if (int rc = hop_to(e, s)) return rc;
+  const uint32_t mw = slo_max_width(widths, n_widths);
+  SA_HIP(e, slo_pairs_on(e, sel, bins, first - mw + 1, (uint32_t)(last - first) + mw,
+                         reinterpret_cast<unsigned long long *>(d_pairs), s));
+  if (int rc = hop_back(e, s)) {  // (the selection buffers are the engine's)
+    (void)hipStreamSynchronize(s);
+    return rc;
+  }
+  return SA_OK;
+}
+
+int window_slo_finish(sa_engine *e, uint64_t first, uint64_t last, const uint32_t *widths, const uint32_t *limit_ppm,
+                      uint32_t n_widths, const std::vector<uint32_t> &sel, const uint64_t *threshold_ns,
+                      uint64_t min_count, const uint64_t *d_pairs, hipStream_t s, sa_slo_result **out) {
+  if (!e || !out || !d_pairs || !widths || !limit_ppm || !n_widths || !threshold_ns || sel.empty()) return SA_EINVAL;
+  if (int rc = set_dev(e)) return rc;
+  const uint64_t mc = std::max<uint64_t>(min_count, 1);
+  std::unique_ptr<slo_holder> h;
+  try {
+    std::vector<uint8_t> bins(sel.size());
+    for (size_t i = 0; i < sel.size(); ++i) bins[i] = (uint8_t)sa_latency_bin(threshold_ns[i]);
+    h.reset(new slo_holder());
+    h->shape(first, last, widths, limit_ppm, n_widths, sel, threshold_ns, bins, mc);
+  } catch (const std::bad_alloc &) {
+    return fail(e, SA_ENOMEM, "window slo: the result does not fit in host memory");
+  }
+  for (size_t i = 0; i < sel.size(); ++i) {
+    uint64_t lo = 0;
+    (void)sa_latency_bin_bounds(h->threshold_bin[i], &lo, &h->effective_ns[i]);
+  }
+  // the answers in one buffer, laid out as the result's block (slo_holder): one copy brings them
+  sa_engine::Latency &L = e->lat;
+  const uint64_t S = sel.size(), n_out = h->r.n_out, n_cov = n_out + slo_max_width(widths, n_widths) - 1;
+  if (int rc = grow(e, L.slo_prefix, L.slo_prefix_cap, S * (n_cov + 1) * 2, "window slo: prefix buffer hipMalloc failed"))
+    return rc;
+  if (int rc = grow(e, L.slo_out, L.slo_out_cap, h->answers.size(), "window slo: answer buffer hipMalloc failed"))
+    return rc;
+  unsigned long long *d_total = L.slo_out, *d_slow = d_total + h->cells;
+  uint32_t *d_alert = reinterpret_cast<uint32_t *>(d_slow + h->cells);
+  uint8_t *d_burn = reinterpret_cast<uint8_t *>(d_slow + h->cells + h->alert_words);
+  // (the scratch is the engine's: after its own earlier use, before its next)
+  if (int rc = hop_to(e, s)) return rc;
+  hipError_t st = sa::launch_slo_slide(reinterpret_cast<const unsigned long long *>(d_pairs), (uint32_t)S, (uint32_t)n_out,
+                                       widths, limit_ppm, n_widths, mc, L.slo_prefix, d_total, d_slow, d_burn, d_alert, s);
+  if (st == hipSuccess)
+    st = hipMemcpyAsync(h->answers.data(), L.slo_out, h->answers.size() * 8, hipMemcpyDeviceToHost, s);
+  const hipError_t waited = hipStreamSynchronize(s);  // the call's one wait (also after a failure: copies may be in flight)
+  if (st != hipSuccess || waited != hipSuccess)
+    return fail(e, SA_EDEVICE, std::string("window slo: ") + hipGetErrorString(st != hipSuccess ? st : waited));
+  *out = &h.release()->r;
+  return SA_OK;
+}
 }  // namespace sa_grp
 
 extern "C" {
@@ -295,5 +389,42 @@ int sa_window_latency_movers(sa_engine *e, uint64_t base_first, uint64_t base_la
 }
 
 void sa_latency_movers_result_free(sa_latency_movers_result *r) { delete reinterpret_cast<latency_movers_holder *>(r); }
+
+int sa_window_slo(sa_engine *e, uint64_t first, uint64_t last, const uint32_t *widths, const uint32_t *limit_ppm,
+                  uint32_t n_widths, const uint32_t *services, uint32_t n_sel, const uint64_t *threshold_ns,
+                  uint64_t min_count, uint32_t flags, sa_slo_result **out) {
+  if (!e || !out) return SA_EINVAL;
+  *out = nullptr;
+  if (int rc = latency_enabled(e, "window slo")) return rc;
+  std::vector<uint32_t> sel;
+  std::vector<uint8_t> bins;
+  try {
+    if (const char *bad = sa_args::slo_args(e->cfg.n_services, widths, limit_ppm, n_widths, services, n_sel,
+                                            threshold_ns, flags, &sel))
+      return bad_args(e, SA_EINVAL, "window slo", bad);
+    bins.resize(sel.size());
+  } catch (const std::bad_alloc &) {
+    return fail(e, SA_ENOMEM, "window slo: the selection does not fit in host memory");
+  }
+  for (size_t i = 0; i < sel.size(); ++i) bins[i] = (uint8_t)sa_latency_bin(threshold_ns[i]);
+  if (int rc = slo_spans(e, first, last, widths, n_widths)) return rc;
+  const uint32_t n_out = (uint32_t)(last - first + 1), S = (uint32_t)sel.size(), mw = slo_max_width(widths, n_widths);
+  if (const char *bad = sa_args::slo_rows(n_out, S)) return bad_args(e, SA_EINVAL, "window slo", bad);
+  if (int rc = begin_read(e)) return rc;
+  const uint32_t n_cov = n_out + mw - 1;
+  if (int rc = slo_selection(e, S)) return rc;
+  if (int rc = grow(e, e->lat.slo_pairs, e->lat.slo_pairs_cap, (uint64_t)S * n_cov * 2,
+                    "window slo: pair buffer hipMalloc failed"))
+    return rc;
+  // (the pairs of the engine's own ring, then the stage a group runs on its member 0 after adding the
+  // members' pairs; a failed launch has waited for the copies out of sel and bins)
+  SA_HIP(e, slo_pairs_on(e, sel, bins, first - mw + 1, n_cov, e->lat.slo_pairs, e->stream));
+  const int rc = sa_grp::window_slo_finish(e, first, last, widths, limit_ppm, n_widths, sel, threshold_ns, min_count,
+                                           reinterpret_cast<const uint64_t *>(e->lat.slo_pairs), e->stream, out);
+  if (rc != SA_OK) (void)hipStreamSynchronize(e->stream);  // (a finish that failed early: the copies may be in flight)
+  return rc;
+}
+
+void sa_slo_result_free(sa_slo_result *r) { delete reinterpret_cast<slo_holder *>(r); }
 
 }  // extern "C"

@@ -256,6 +256,13 @@ struct sa_engine {
     unsigned long long *mov_sums = nullptr, *mov_counts = nullptr;
     ulonglong2 *mov_cand = nullptr;
     sa::LatMovOut *mov_out = nullptr;
+    // sa_window_slo, grown like sums: the selection's threshold bins
+    // [slo_thr_cap], the engine's own pairs [slo_pairs_cap] u64 ([n_sel]
+    // [n_cov][2]), their prefix sums [slo_prefix_cap] u64 ([n_sel][n_cov + 1]
+    // [2]) and the answers [slo_out_cap] u64: total, slow, alert, burning
+    uint8_t *slo_thr = nullptr;
+    unsigned long long *slo_pairs = nullptr, *slo_prefix = nullptr, *slo_out = nullptr;
+    uint64_t slo_thr_cap = 0, slo_pairs_cap = 0, slo_prefix_cap = 0, slo_out_cap = 0;
   } lat;
   // sa_ingest: two pinned host slots and their HBM copies; a slot is refilled
   // once its event (H2D copy + aggregation of the previous use) has passed

@@ -81,6 +81,22 @@ int window_latency_movers_export_async(sa_engine *e, const uint64_t range[4], ui
 int window_latency_movers_finish(sa_engine *e, const uint64_t range[4], uint32_t k, uint64_t min_count,
                                  uint32_t min_shift, const uint32_t *q_ppm, uint32_t n_q, uint32_t flags,
                                  const uint64_t *d_sums, hipStream_t s, sa_latency_movers_result **out);
+// sa_window_slo's pairs stage for one member, without the wait: d_pairs
+// [sel.size()][n_cov][2], n_cov = last - first + max(widths): per selected
+// service and covered window first - max(widths) + 1 .. last the row's spans
+// and those in bins above bins[i] (= sa_latency_bin of the service's
+// threshold), on `s`.  sel (sa_args::slo_args') and bins must stay until `s`
+// has been waited for.  SA_ESTATE without the option, SA_ERANGE as sa_window_slo.
+int window_slo_export_async(sa_engine *e, uint64_t first, uint64_t last, const uint32_t *widths, uint32_t n_widths,
+                            const std::vector<uint32_t> &sel, const std::vector<uint8_t> &bins, uint64_t *d_pairs,
+                            hipStream_t s);
+// the rest of the query, on `e` (a group's member 0, whose device holds the
+// members' summed d_pairs) and on `s`: the prefix sums, every width's sums,
+// the verdicts, the copies and the wait.  The arguments (sa_args::slo_args
+// passed them; threshold_ns parallel to sel) and *out as sa_window_slo.
+int window_slo_finish(sa_engine *e, uint64_t first, uint64_t last, const uint32_t *widths, const uint32_t *limit_ppm,
+                      uint32_t n_widths, const std::vector<uint32_t> &sel, const uint64_t *threshold_ns,
+                      uint64_t min_count, const uint64_t *d_pairs, hipStream_t s, sa_slo_result **out);
 // What one engine's heavy-hitter scan leaves on the host once its stream
 // passes the copies: head = the matches, the resident keys, the largest
 // estimate, error_spans; rows [k] = (estimate, key) pairs, the first

@@ -582,6 +582,21 @@ hipError_t launch_lat_movers(const unsigned long long *sums, uint32_t n_services
                              unsigned long long min_count, uint32_t min_shift, uint32_t fall, const uint32_t *q_ppm,
                              uint32_t n_q, unsigned long long *counts, ulonglong2 *cand, TopCtl *T, LatMovOut *O,
                              hipStream_t s);
+// latency SLO burn (sa_window_slo; DESIGN.md section 4, "Latency SLO burn
+// over sliding widths").  pairs [n_sel][n_cov][2] u64: covered window k =
+// window a + k of the ring, service sel[i] (device): {its row's spans, those
+// in bins above thr_bin[i] (device)}
+hipError_t launch_slo_pairs(const unsigned long long *ring, uint32_t n_services, uint32_t n_windows, const uint32_t *sel,
+                            const uint8_t *thr_bin, uint32_t n_sel, uint64_t a, uint32_t n_cov,
+                            unsigned long long *pairs, hipStream_t s);
+// From pairs [n_sel][n_cov][2], n_cov = n_out + max(widths) - 1: total and slow
+// [n_out][n_widths][n_sel], burning [n_out][n_sel] and alert [n_sel] as
+// sa_slo_result's; prefix [n_sel][n_cov + 1][2] is scratch.  widths and
+// limit_ppm: host, n_widths <= SA_SLO_MAX_WIDTHS; min_count >= 1.
+hipError_t launch_slo_slide(const unsigned long long *pairs, uint32_t n_sel, uint32_t n_out, const uint32_t *widths,
+                            const uint32_t *limit_ppm, uint32_t n_widths, unsigned long long min_count,
+                            unsigned long long *prefix, unsigned long long *total, unsigned long long *slow,
+                            uint8_t *burning, uint32_t *alert, hipStream_t s);
 // sorted union of series ids on the device (spanagg_union.hip): out = the
 // distinct non-zero ids of in[0..n) ascending, *d_total (device u32) their
 // count; scratch >= key_union_scratch_bytes(n); big_scratch / big_bytes: a

@@ -105,5 +105,35 @@ inline const char *latency_movers_args(uint32_t k, const uint32_t *q, uint32_t n
   return q_ppm(q, n_q);
 }
 
+// sa_window_slo's arguments, the spans apart: 1..SA_SLO_MAX_WIDTHS widths (any
+// order, repeats pass) with a limit in 0..10^6 each, a threshold (any u64) a
+// selected service, no flag; *sel as latency_args'
+inline const char *slo_args(uint32_t n_services, const uint32_t *widths, const uint32_t *limit_ppm, uint32_t n_widths,
+                            const uint32_t *services, uint32_t n_sel, const uint64_t *threshold_ns,
+                            uint32_t flag_bits, std::vector<uint32_t> *sel) {
+  sel->clear();
+  if (const char *bad = flags(flag_bits, 0)) return bad;
+  if (n_widths == 0 || n_widths > SA_SLO_MAX_WIDTHS || !widths || !limit_ppm)
+    return "n_widths outside 1..SA_SLO_MAX_WIDTHS or null widths or limit_ppm";
+  for (uint32_t w = 0; w < n_widths; ++w)
+    if (limit_ppm[w] > 1000000u) return "a limit_ppm above 1000000";
+  if (!threshold_ns) return "null threshold_ns";
+  return select_services(n_services, services, n_sel, n_services, sel);
+}
+
+// its span rule: every width passes `span` against first..last, so every
+// window first - max(widths) + 1 .. last is resident
+inline const char *slo_span(uint64_t first, uint64_t last, const uint32_t *widths, uint32_t n_widths, uint64_t win_base,
+                            uint32_t n_windows) {
+  for (uint32_t w = 0; w < n_widths; ++w)
+    if (const char *bad = span(first, last, widths[w], win_base, n_windows)) return bad;
+  return nullptr;
+}
+
+// its size rule, once the spans are known to be resident: n_out * n_sel <= 2^20
+inline const char *slo_rows(uint64_t n_out, uint64_t n_sel) {
+  return n_out * n_sel > 1ull << 20 ? "n_out * n_sel above 2^20" : nullptr;
+}
+
 }  // namespace sa_args
 #pragma GCC visibility pop

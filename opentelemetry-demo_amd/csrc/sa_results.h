@@ -233,6 +233,38 @@ struct latency_movers_holder {
   }
 };
 
+struct slo_holder {
+  sa_slo_result r;
+  std::vector<uint32_t> services, widths, limit_ppm;
+  std::vector<uint64_t> threshold_ns, effective_ns;
+  std::vector<uint8_t> threshold_bin;
+  // The device's answers as it lays them out, so that one copy brings them: total and slow [cells] u64
+  // each, cells = n_out * n_widths * n_sel, then alert_outputs [n_sel] u32 in alert_words words and
+  // burning [n_out][n_sel] u8 in burn_words words.
+  std::vector<uint64_t> answers;
+  size_t cells = 0, alert_words = 0, burn_words = 0;
+  // the columns sized for outputs first..last of the selection sel and n_widths widths, and r pointing at
+  // them; bins [sel.size()]: every threshold's bin
+  __attribute__((visibility("hidden"))) void shape(uint64_t first, uint64_t last, const uint32_t *w,
+                                                   const uint32_t *limits, uint32_t n_widths,
+                                                   const std::vector<uint32_t> &sel, const uint64_t *thresholds,
+                                                   const std::vector<uint8_t> &bins, uint64_t min_count) {
+    const size_t n_out = (size_t)(last - first + 1), n_sel = sel.size();
+    services = sel, threshold_bin = bins;
+    widths.assign(w, w + n_widths), limit_ppm.assign(limits, limits + n_widths);
+    threshold_ns.assign(thresholds, thresholds + n_sel), effective_ns.resize(n_sel);
+    cells = n_out * n_widths * n_sel, alert_words = (n_sel + 1) / 2, burn_words = (n_out * n_sel + 7) / 8;
+    answers.resize(2 * cells + alert_words + burn_words);
+    r.first_window = first, r.last_window = last, r.n_out = (uint32_t)n_out, r.n_sel = (uint32_t)n_sel;
+    r.n_widths = n_widths, r.pad = 0, r.min_count = min_count;
+    r.services = services.data(), r.widths = widths.data(), r.limit_ppm = limit_ppm.data();
+    r.threshold_ns = threshold_ns.data(), r.threshold_bin = threshold_bin.data(), r.effective_ns = effective_ns.data();
+    r.total = answers.data(), r.slow = r.total + cells;
+    r.alert_outputs = reinterpret_cast<const uint32_t *>(r.slow + cells);
+    r.burning = reinterpret_cast<const uint8_t *>(r.slow + cells + alert_words);
+  }
+};
+
 struct sketch_holder {
   sa_sketch_result r;
   std::vector<uint8_t> hll;

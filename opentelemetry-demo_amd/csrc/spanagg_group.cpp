@@ -314,6 +314,7 @@ struct sa_group {
   std::vector<Buf> keys, gath, uni, rows, hll, cms;
   std::vector<Buf> cms_base;  // sa_group_window_movers: the baseline range's cells beside cms (the current range's)
   std::vector<Buf> lat;       // sa_group_window_latency: every member's sliding sums [n_out][n_sel][SA_LAT_BINS]
+                              // (the movers' two ranges' sums, sa_group_window_slo's pairs)
   std::vector<Buf> srt, ucnt;  // device key union (sa::key_union): its scratch and the distinct count
   std::vector<uint64_t *> big;  // key_union's scratch for oversized buckets (per member)
   std::vector<size_t> big_bytes;
@@ -1333,6 +1334,43 @@ int sa_group_window_latency_movers(sa_group *g, uint64_t base_first, uint64_t ba
                                                      buf<uint64_t>(g->lat, 0), g->st[0], out))
       rc = member_error(g, 0, f, what);
   return end_query(g, what, rc, merged, out, sa_latency_movers_result_free);
+}
+
+// Each member cuts the covered rows of its own ring to (total, slow) pairs, the
+// transport adds the members' pairs -- as it adds sa_group_window_latency's
+// sums, 16 bytes a row for 2 KiB -- and member 0's device slides every width
+// over the sums and judges.
+int sa_group_window_slo(sa_group *g, uint64_t first, uint64_t last, const uint32_t *widths, const uint32_t *limit_ppm,
+                        uint32_t n_widths, const uint32_t *services, uint32_t n_sel, const uint64_t *threshold_ns,
+                        uint64_t min_count, uint32_t flags, sa_slo_result **out) {
+  if (!g || !out) return SA_EINVAL;
+  *out = nullptr;
+  const char *const what = "window slo";
+  if (const char *bad = sa_args::latency_option(g->cfg.options)) return bad_args(g, SA_ESTATE, what, bad);
+  std::vector<uint32_t> sel;
+  if (const char *bad = sa_args::slo_args(g->cfg.n_services, widths, limit_ppm, n_widths, services, n_sel, threshold_ns,
+                                          flags, &sel))
+    return bad_args(g, SA_EINVAL, what, bad);
+  std::vector<uint8_t> bins(sel.size());
+  for (size_t i = 0; i < sel.size(); ++i) bins[i] = (uint8_t)sa_latency_bin(threshold_ns[i]);
+  // (the members check the spans against their rings; spans that pass have n_out and every width <= n_windows)
+  const uint64_t mw = *std::max_element(widths, widths + n_widths);
+  const uint64_t n_out = first <= last && last - first < g->cfg.n_windows && mw <= g->cfg.n_windows ? last - first + 1 : 0;
+  if (n_out)
+    if (const char *bad = sa_args::slo_rows(n_out, sel.size())) return bad_args(g, SA_EINVAL, what, bad);
+  // every member's pairs [n_sel][n_cov][2]
+  const std::vector<Part> parts = {{&g->lat, n_out && mw ? sel.size() * (n_out + mw - 1) * 2 : 1, false}};
+  if (int rc = ensure_parts(g, parts)) return rc;
+  int rc = each_member(g, what, [&](uint32_t i) {  // (the copies out of `sel` and `bins` end before end_query returns)
+    return sa_grp::window_slo_export_async(g->eng[i], first, last, widths, n_widths, sel, bins, buf<uint64_t>(g->lat, i),
+                                           g->st[i]);
+  });
+  const int merged = rc ? SA_OK : reduce_members(g, parts);
+  if (!rc && !merged)
+    if (int f = sa_grp::window_slo_finish(g->eng[0], first, last, widths, limit_ppm, n_widths, sel, threshold_ns,
+                                          min_count, buf<uint64_t>(g->lat, 0), g->st[0], out))
+      rc = member_error(g, 0, f, what);
+  return end_query(g, what, rc, merged, out, sa_slo_result_free);
 }
 
 int sa_group_window_advance(sa_group *g, uint64_t new_base) {

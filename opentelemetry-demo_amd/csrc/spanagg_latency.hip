@@ -21,6 +21,12 @@
 //                      scored by the shift of its ranking quantile's bin --
 //                      the select and the sort are the heavy hitters' -- and
 //                      the selected services' counts and bins.
+//   slo_pairs_kernel, slo_slide_kernel
+//                      sa_window_slo: every covered (window, service) row cut
+//                      to a (total, slow) pair at the service's threshold bin
+//                      -- the ring read once whatever the widths -- then
+//                      prefix sums along the windows, every width's sums as
+//                      the difference of two prefixes, and the burn rule.
 //
 // The two query stages are apart because a group adds its members' sums
 // between them.  Every cell is an integer sum, so the order of the atomics
@@ -436,6 +442,114 @@ __global__ __launch_bounds__(kLatQueryBlock) void lat_mov_rows_kernel(const unsi
   }
 }
 
+// ---- latency SLO burn (sa_window_slo): every covered row cut to a (total,
+// slow) pair at its service's threshold bin, then -- after a group has added
+// its members' pairs -- prefix sums along the windows, every width's
+// difference of two prefixes, and the burn rule ----
+constexpr uint32_t kSloSlideBlock = 64;  // one wave: a service's scan carries from chunk to chunk
+
+struct SloRule {
+  uint32_t n, max_width;  // the widths asked for, the longest
+  uint32_t width[SA_SLO_MAX_WIDTHS], limit_ppm[SA_SLO_MAX_WIDTHS];
+  unsigned long long min_count;  // >= 1
+};
+
+// Wave r serves covered window k = r / n_sel (window a + k of the ring
+// [win_mask + 1][n_services][256]; a + n_cov - 1 resident: the caller checked)
+// and selected service i = r % n_sel, so neighbouring waves read neighbouring
+// rows of one window.  Lane l holds bins 4l .. 4l + 3 -- the row is one
+// coalesced 2 KiB read -- and counts as slow those above thr_bin[i]; lane 0
+// writes pairs[i][k] = {total, slow}, pairs [n_sel][n_cov]: a service's
+// windows lie side by side for the scan.  The ring index stays below (win_mask
+// + 1) * n_services * 256 (sel[i] < n_services: the host checked; 4l + 3 <
+// 256), the pairs index below n_sel * n_cov (r < n_cov * n_sel).
+__global__ __launch_bounds__(kLatQueryBlock) void slo_pairs_kernel(const unsigned long long *__restrict__ ring,
+                                                                   uint32_t n_services, uint32_t win_mask,
+                                                                   const uint32_t *__restrict__ sel,
+                                                                   const uint8_t *__restrict__ thr_bin, uint32_t n_sel,
+                                                                   uint64_t a, uint32_t n_cov,
+                                                                   ulonglong2 *__restrict__ pairs) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t r = (uint64_t)blockIdx.x * (kLatQueryBlock / 64) + (threadIdx.x >> 6);
+  if (r >= (uint64_t)n_cov * n_sel) return;  // (wave-uniform)
+  const uint32_t k = (uint32_t)(r / n_sel), i = (uint32_t)(r % n_sel);
+  const U64x4 v = lat_row(ring + (((((a + k) & win_mask) * n_services) + sel[i]) << 8) + lane * 4);
+  const uint32_t tb = thr_bin[i];
+  unsigned long long total = 0, slow = 0;
+#pragma unroll
+  for (uint32_t j = 0; j < 4; ++j) {
+    total += v.v[j];
+    slow += lane * 4 + j > tb ? v.v[j] : 0ULL;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    total += __shfl_xor(total, o);
+    slow += __shfl_xor(slow, o);
+  }
+  if (lane == 0) pairs[(uint64_t)i * n_cov + k] = ulonglong2{total, slow};
+}
+
+// One wave (a workgroup of its own) a selected service i.  The scan: 64 windows
+// of pairs [n_sel][n_cov] a step -- one coalesced 1 KiB read -- a wave scan
+// and the carry of the steps before give P[i][k + 1] = pairs[i][0..k] summed,
+// P [n_sel][n_cov + 1] with P[i][0] = 0.  Then, once the barrier has made the
+// wave's own stores visible to all its lanes, 64 outputs a step: output o ends
+// at covered window R.max_width - 1 + o, so width w covers P[i][e] - P[i][e -
+// R.width[w]] with e = R.max_width + o -- e <= R.max_width + n_out - 1 = n_cov,
+// and e - width >= 0 as width <= max_width -- written to total and slow
+// [n_out][R.n][n_sel]; bit w of burning [n_out][n_sel] is the burn rule
+// (strict, both products in u64), and alert[i] counts the outputs whose R.n
+// bits are all set.  Every sum is an integer: neither the split into steps nor
+// a group's order of adding shows.
+__global__ __launch_bounds__(kSloSlideBlock) void slo_slide_kernel(const ulonglong2 *__restrict__ pairs, uint32_t n_sel,
+                                                                   uint32_t n_cov, uint32_t n_out, SloRule R,
+                                                                   ulonglong2 *P_all,
+                                                                   unsigned long long *__restrict__ total,
+                                                                   unsigned long long *__restrict__ slow,
+                                                                   uint8_t *__restrict__ burning,
+                                                                   uint32_t *__restrict__ alert) {
+  const uint32_t lane = threadIdx.x, i = blockIdx.x;
+  const ulonglong2 *p = pairs + (uint64_t)i * n_cov;
+  ulonglong2 *P = P_all + (uint64_t)i * (n_cov + 1ull);
+  if (lane == 0) P[0] = ulonglong2{0, 0};
+  unsigned long long carry_t = 0, carry_s = 0;
+  for (uint32_t k0 = 0; k0 < n_cov; k0 += 64) {  // (the same trips for every lane)
+    const uint32_t k = k0 + lane;
+    const ulonglong2 v = k < n_cov ? p[k] : ulonglong2{0, 0};
+    unsigned long long t = v.x, s = v.y;
+#pragma unroll
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+      const unsigned long long ut = __shfl_up(t, d), us = __shfl_up(s, d);
+      if (lane >= d) t += ut, s += us;
+    }
+    t += carry_t, s += carry_s;
+    if (k < n_cov) P[k + 1] = ulonglong2{t, s};
+    carry_t = __shfl(t, 63), carry_s = __shfl(s, 63);
+  }
+  __threadfence_block();
+  __syncthreads();
+  const uint32_t all = (1u << R.n) - 1u;
+  uint32_t alerts = 0;
+  for (uint32_t o0 = 0; o0 < n_out; o0 += 64) {
+    const uint32_t o = o0 + lane;
+    uint32_t bits = 0;
+    if (o < n_out) {
+      const uint32_t e = R.max_width + o;
+      const ulonglong2 hi = P[e];
+      for (uint32_t w = 0; w < R.n; ++w) {
+        const ulonglong2 lo = P[e - R.width[w]];
+        const unsigned long long t = hi.x - lo.x, s = hi.y - lo.y;
+        const uint64_t at = ((uint64_t)o * R.n + w) * n_sel + i;
+        total[at] = t, slow[at] = s;
+        if (t >= R.min_count && s * 1000000ULL > (unsigned long long)R.limit_ppm[w] * t) bits |= 1u << w;
+      }
+      burning[(uint64_t)o * n_sel + i] = (uint8_t)bits;
+    }
+    alerts += (uint32_t)__popcll(__ballot(o < n_out && bits == all));
+  }
+  if (lane == 0) alert[i] = alerts;
+}
+
 }  // namespace
 
 hipError_t prepare_lat_ingest(size_t lds_bytes) {
@@ -517,6 +631,32 @@ hipError_t launch_lat_movers(const unsigned long long *sums, uint32_t n_services
   const uint32_t rows_per = kLatQueryBlock / 64;
   hipLaunchKernelGGL(lat_mov_rows_kernel, dim3((k + rows_per - 1) / rows_per), dim3(kLatQueryBlock), 0, s, sums,
                      n_services, Q, T, O);
+  return hipGetLastError();
+}
+
+hipError_t launch_slo_pairs(const unsigned long long *ring, uint32_t n_services, uint32_t n_windows, const uint32_t *sel,
+                            const uint8_t *thr_bin, uint32_t n_sel, uint64_t a, uint32_t n_cov,
+                            unsigned long long *pairs, hipStream_t s) {
+  const uint64_t waves = (uint64_t)n_cov * n_sel, per = kLatQueryBlock / 64;
+  hipLaunchKernelGGL(slo_pairs_kernel, dim3((uint32_t)((waves + per - 1) / per)), dim3(kLatQueryBlock), 0, s, ring,
+                     n_services, n_windows - 1, sel, thr_bin, n_sel, a, n_cov, reinterpret_cast<ulonglong2 *>(pairs));
+  return hipGetLastError();
+}
+
+hipError_t launch_slo_slide(const unsigned long long *pairs, uint32_t n_sel, uint32_t n_out, const uint32_t *widths,
+                            const uint32_t *limit_ppm, uint32_t n_widths, unsigned long long min_count,
+                            unsigned long long *prefix, unsigned long long *total, unsigned long long *slow,
+                            uint8_t *burning, uint32_t *alert, hipStream_t s) {
+  SloRule R{};
+  R.n = std::min<uint32_t>(n_widths, SA_SLO_MAX_WIDTHS);
+  for (uint32_t w = 0; w < R.n; ++w) {
+    R.width[w] = widths[w], R.limit_ppm[w] = limit_ppm[w];
+    R.max_width = std::max(R.max_width, widths[w]);
+  }
+  R.min_count = min_count;
+  hipLaunchKernelGGL(slo_slide_kernel, dim3(n_sel), dim3(kSloSlideBlock), 0, s,
+                     reinterpret_cast<const ulonglong2 *>(pairs), n_sel, n_out + R.max_width - 1, n_out, R,
+                     reinterpret_cast<ulonglong2 *>(prefix), total, slow, burning, alert);
   return hipGetLastError();
 }
 

@@ -163,6 +163,18 @@ class sa_latency_movers_result(C.Structure):
     ]
 
 
+SA_SLO_MAX_WIDTHS = SLO_MAX_WIDTHS = 4
+
+
+class sa_slo_result(C.Structure):
+    _fields_ = [
+        ("first_window", C.c_uint64), ("last_window", C.c_uint64), ("n_out", C.c_uint32), ("n_sel", C.c_uint32),
+        ("n_widths", C.c_uint32), ("pad", C.c_uint32), ("min_count", C.c_uint64),
+        ("services", u32p), ("widths", u32p), ("limit_ppm", u32p), ("threshold_ns", u64p), ("threshold_bin", u8p),
+        ("effective_ns", u64p), ("total", u64p), ("slow", u64p), ("burning", u8p), ("alert_outputs", u32p),
+    ]
+
+
 class sa_stats(C.Structure):
     _fields_ = [
         ("spans", C.c_uint64), ("zero_key", C.c_uint64), ("invalid_service", C.c_uint64),
@@ -252,6 +264,11 @@ SIGNATURES = [
                                                  C.c_uint32, C.c_uint64, C.c_uint32, u32p, C.c_uint32, C.c_uint32,
                                                  C.POINTER(C.POINTER(sa_latency_movers_result))]),
     ("sa_latency_movers_result_free", None, [C.POINTER(sa_latency_movers_result)]),
+    ("sa_window_slo", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, u32p, u32p, C.c_uint32, u32p, C.c_uint32, u64p,
+                                C.c_uint64, C.c_uint32, C.POINTER(C.POINTER(sa_slo_result))]),
+    ("sa_group_window_slo", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, u32p, u32p, C.c_uint32, u32p, C.c_uint32,
+                                      u64p, C.c_uint64, C.c_uint32, C.POINTER(C.POINTER(sa_slo_result))]),
+    ("sa_slo_result_free", None, [C.POINTER(sa_slo_result)]),
     ("sa_latency_bin", C.c_uint32, [C.c_uint64]),
     ("sa_latency_bin_bounds", C.c_int, [C.c_uint32, u64p, u64p]),
     ("sa_hll_estimate_hist", C.c_double, [u32p, C.c_uint32]),

@@ -300,6 +300,28 @@ class LatencyMoversResult:
                                               self.q_bin_base, self.q_bin_cur)]
 
 
+@dataclass
+class SloResult:
+    """sa_slo_result: per output window, width and selected service the spans
+    of the covered windows and those slower than the service's threshold, and
+    whether each width burns its error budget -- slow * 10^6 > limit_ppm *
+    total with at least min_count spans.  "Slow" means a duration above
+    effective_ns, the upper bound of the threshold's histogram bin."""
+    first: int
+    last: int
+    min_count: int                # as applied: max(min_count, 1)
+    services: np.ndarray          # [n_sel] u32 service ids, in the caller's order
+    widths: np.ndarray            # [n_widths] u32 as given
+    limit_ppm: np.ndarray         # [n_widths] u32 as given
+    threshold_ns: np.ndarray      # [n_sel] u64 as given
+    threshold_bin: np.ndarray     # [n_sel] u8: sketch.latency_bin(threshold_ns)
+    effective_ns: np.ndarray      # [n_sel] u64: sketch.latency_bin_bounds(threshold_bin)[1]
+    total: np.ndarray             # [n_out, n_widths, n_sel] u64
+    slow: np.ndarray              # [n_out, n_widths, n_sel] u64
+    burning: np.ndarray           # [n_out, n_sel] u8: bit w set when width w burns
+    alert_outputs: np.ndarray     # [n_sel] u32: outputs at which every width burns
+
+
 def hll_estimate(regs: np.ndarray, p: int) -> float:
     lib = _lib.load()
     r = np.ascontiguousarray(regs, dtype=np.uint8)
@@ -498,6 +520,32 @@ def _window_latency_movers(obj, fn, what, base, cur, k, quantiles, min_count, mi
             int(r.n_matched), int(r.spans_base), int(r.spans_cur))
     finally:
         obj.lib.sa_latency_movers_result_free(out)
+
+
+def _window_slo(obj, fn, what, first, last, widths, limit_ppm, thresholds_ns, services, min_count) -> SloResult:
+    """sa_window_slo / sa_group_window_slo -> SloResult (copies), freeing the library's result."""
+    sv = None if services is None else np.ascontiguousarray(services, dtype=np.uint32).reshape(-1)
+    wd = np.ascontiguousarray(widths, dtype=np.uint32).reshape(-1)
+    lim = np.ascontiguousarray(limit_ppm, dtype=np.uint32).reshape(-1)
+    thr = np.ascontiguousarray(thresholds_ns, dtype=np.uint64).reshape(-1)
+    if len(lim) != len(wd):
+        raise ValueError(f"{what}: one limit_ppm a width")
+    if len(thr) != (obj.config.n_services if sv is None else len(sv)):
+        raise ValueError(f"{what}: one threshold a selected service")
+    out = C.POINTER(_lib.sa_slo_result)()
+    obj._check(fn(obj._h, int(first), int(last), wd.ctypes.data_as(_lib.u32p), lim.ctypes.data_as(_lib.u32p), len(wd),
+                  None if sv is None else sv.ctypes.data_as(_lib.u32p), 0 if sv is None else len(sv),
+                  thr.ctypes.data_as(_lib.u64p), int(min_count), 0, C.byref(out)), what)
+    try:
+        r = out.contents
+        n, S, W = int(r.n_out), int(r.n_sel), int(r.n_widths)
+        col = lambda p, *shape: np.ctypeslib.as_array(p, shape=shape).copy()
+        return SloResult(
+            int(r.first_window), int(r.last_window), int(r.min_count), col(r.services, S), col(r.widths, W),
+            col(r.limit_ppm, W), col(r.threshold_ns, S), col(r.threshold_bin, S), col(r.effective_ns, S),
+            col(r.total, n, W, S), col(r.slow, n, W, S), col(r.burning, n, S), col(r.alert_outputs, S))
+    finally:
+        obj.lib.sa_slo_result_free(out)
 
 
 _QUANTILES = (0.5, 0.95, 0.99)
@@ -737,6 +785,18 @@ class Engine:
         return _window_latency_movers(self, self.lib.sa_window_latency_movers, "sa_window_latency_movers", base, cur, k,
                                       quantiles, min_count, min_shift, fall)
 
+    def window_slo(self, first: int, last: int, widths, limit_ppm, thresholds_ns, services=None,
+                   min_count: int = 1) -> SloResult:
+        """sa_window_slo (OPT_WINDOW_LATENCY engines): for every window t of
+        first..last, every width of `widths` (at most SLO_MAX_WIDTHS) and every
+        service of `services` (ids; None: every service) the spans of windows
+        t - width + 1 .. t and those slower than the service's entry of
+        thresholds_ns, and whether width w burns: slow * 10^6 > limit_ppm[w] *
+        total with at least min_count spans.  The ring is read once whatever
+        the widths; only the sums and the verdicts cross the bus."""
+        return _window_slo(self, self.lib.sa_window_slo, "sa_window_slo", first, last, widths, limit_ppm, thresholds_ns,
+                           services, min_count)
+
     def flush_exp(self, allow_drops: bool = False) -> ExpoResult:
         out = C.POINTER(_lib.sa_exp_result)()
         rc = self.lib.sa_flush_exp(self._h, C.byref(out))
@@ -946,6 +1006,13 @@ class Group:
         the members' summed histograms."""
         return _window_latency_movers(self, self.lib.sa_group_window_latency_movers, "sa_group_window_latency_movers",
                                       base, cur, k, quantiles, min_count, min_shift, fall)
+
+    def window_slo(self, first: int, last: int, widths, limit_ppm, thresholds_ns, services=None,
+                   min_count: int = 1) -> SloResult:
+        """sa_group_window_slo: Engine.window_slo over the members' summed
+        (total, slow) pairs."""
+        return _window_slo(self, self.lib.sa_group_window_slo, "sa_group_window_slo", first, last, widths, limit_ppm,
+                           thresholds_ns, services, min_count)
 
     def window_advance(self, new_base: int):
         self._check(self.lib.sa_group_window_advance(self._h, int(new_base)), "sa_group_window_advance")

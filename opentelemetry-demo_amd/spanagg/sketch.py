@@ -125,6 +125,20 @@ def latency_movers(hist_base, hist_cur, q_ppm: Sequence[int], k: int, min_count:
     return rows[:k], n_eligible, len(rows)
 
 
+def slo_counts(hist, threshold_bin: int):
+    """sa_window_slo's counts of one summed 256-bin row: (total, slow), slow the
+    spans in bins above threshold_bin -- the threshold's own bin counts as fast."""
+    counts = [int(c) for c in hist]
+    return sum(counts), sum(counts[int(threshold_bin) + 1:])
+
+
+def slo_burning(total: int, slow: int, limit_ppm: int, min_count: int = 1) -> bool:
+    """sa_window_slo's burn rule for one width: at least max(min_count, 1)
+    spans, and slow * 10^6 > limit_ppm * total -- strictly, in integers."""
+    total, slow = int(total), int(slow)
+    return total >= max(int(min_count), 1) and slow * 1_000_000 > int(limit_ppm) * total
+
+
 def anomalous(series: Sequence[float], factor: float, min_base: float = 1.0) -> list:
     """Indices whose value exceeds `factor` x the series median (floor min_base)."""
     x = np.asarray(series, dtype=np.float64)
