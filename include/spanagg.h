@@ -25,6 +25,7 @@
  *   (new) duration quantiles per service and window sa_window_latency (log-linear histograms in the ring, SA_OPT_WINDOW_LATENCY)
  *   (new) services whose latency shifted most       sa_window_latency_movers (two ranges' histograms summed, scored and selected on the device)
  *   (new) latency SLO burn over sliding widths      sa_window_slo (rows cut to (total, slow) pairs at a threshold, prefix sums on the device)
+ *   (new) when each service's latency shifted       sa_window_latency_onset (the pairs' change point per service, a 128-bit CUSUM on the device)
  *
  * Boundary rules (mirroring the connector's contracts):
  *  - Ownership: batches are borrowed for the duration of the call (page-locked
@@ -720,6 +721,81 @@ int sa_window_slo(sa_engine *e, uint64_t first, uint64_t last, const uint32_t *w
                   const uint64_t *threshold_ns, uint64_t min_count, uint32_t flags, sa_slo_result **out);
 void sa_slo_result_free(sa_slo_result *r);
 
+/* ---- latency onset over the window ring (SA_OPT_WINDOW_LATENCY) ----
+ * "Since when": sa_window_latency_movers and sa_window_slo need the caller to
+ * know where "before" ends and "after" begins; this call finds that window for
+ * every service -- the change point of its slow share over first..last, the
+ * maximum of a CUSUM over the prefix sums of its (total, slow) pairs -- and
+ * returns the k services whose slow share changed most, each with the window
+ * to hold against the deploy log.  One call, the ring read at most twice.  No
+ * state beyond sa_window_latency's. */
+#define SA_ONSET_FALL 1u   /* rank speed-ups: the slow share fell */
+typedef struct {
+    uint64_t first_window, last_window;   /* the range searched, inclusive */
+    uint32_t k, n;                        /* asked for; returned (n <= k) */
+    uint32_t flags, q_ppm;                /* q_ppm as given (0 when threshold_ns was given) */
+    uint64_t min_count;                   /* as applied: max(min_count, 1) */
+    uint64_t n_services, n_eligible, n_matched;
+    uint64_t spans;                       /* every service's count over the range, exact */
+    const uint32_t *services;       /* [n] */
+    const uint64_t *onset_window;   /* [n] the first window of "after" */
+    const int32_t  *delta_ppm;      /* [n] >= 1 */
+    const uint8_t  *threshold_bin;  /* [n] */
+    const uint64_t *effective_ns;   /* [n] that bin's upper bound */
+    const uint64_t *total_before, *slow_before, *total_after, *slow_after;  /* [n] */
+} sa_onset_result;
+
+/* Threshold: every service s is cut at a bin b_s.  With threshold_ns != NULL
+ * the array has n_services entries, any u64 passes, and b_s =
+ * sa_latency_bin(threshold_ns[s]) -- sa_window_slo's rule; q_ppm must then be
+ * 0.  With threshold_ns == NULL, q_ppm must be in 1..10^6 and b_s is the
+ * quantile bin of the service's rows summed over first..last by
+ * sa_window_latency's rule: the smallest bin whose cumulative count reaches
+ * max(1, ceil(count * q_ppm / 10^6)) (0 for a service without spans) -- the
+ * pooled quantile: no prior is needed.  A span is slow when its bin is > b_s;
+ * effective_ns is the upper bound of bin b_s.
+ * Pairs and splits: n_cov = last - first + 1, and window first + j gives
+ * (tot_j, slow_j).  A split is t in 1 .. n_cov - 1: before is windows first ..
+ * first + t - 1, after is first + t .. last.  N_b, S_b, N_a, S_a are the sums
+ * of the two sides, N and S those of the whole range.  A split is eligible when
+ * N_b >= mc and N_a >= mc, mc = max(min_count, 1).  A range of one window is
+ * valid and has no split: n_eligible == 0.
+ * Statistic: D(t) = S_a * N_b - S_b * N_a (= S * N_b - N * S_b), negated under
+ * SA_ONSET_FALL, taken as a signed 128-bit integer: exact while a service's
+ * count over the range stays below 2^44, sa_window_latency's bound (the
+ * products reach 2^88).
+ * Best split: the eligible split with the largest D; among equal D the latest
+ * split wins -- deterministic, and it puts the onset on the first non-empty
+ * window after a run of empty ones.  onset_window = first + t.
+ * Delta: delta_ppm = floor(S_a * 10^6 / N_a) - floor(S_b * 10^6 / N_b) at the
+ * best split, negated under SA_ONSET_FALL; both quotients are taken in u64.
+ * Counters: a service is eligible when it has at least one eligible split
+ * (n_eligible), and matched when it is eligible, its best D > 0 and delta_ppm
+ * >= max(min_delta_ppm, 1) (n_matched).  A min_delta_ppm above 10^6 matches
+ * nothing.  spans sums N over every service.
+ * Order: the matched services sorted by delta_ppm descending, then N
+ * descending (clamped at 2^44 - 1 for ordering), then service id ascending: a
+ * total order.  The first n = min(k, n_matched) are returned, in that order.
+ * Consistency with sa_window_slo: a row's total_before and slow_before are bit
+ * for bit the total and slow of sa_window_slo(e, onset - 1, onset - 1, {onset -
+ * first}, .., &service, 1, &effective_ns, ..), and total_after and slow_after
+ * those of the call at (last, last, {last - onset + 1}).
+ * Ordering and waiting as sa_window_latency_movers: joins every launch in
+ * flight, runs on the engine stream, waits once, clears nothing (two calls
+ * give equal bits).  Works on every ingest path: only the latency ring is read.
+ * SA_ESTATE on an engine without SA_OPT_WINDOW_LATENCY; SA_ERANGE as
+ * sa_window_range; SA_EINVAL for a null `out`, k == 0, k > SA_TOP_MAX_K, flag
+ * bits other than SA_ONSET_FALL, threshold_ns == NULL with q_ppm outside
+ * 1..10^6, threshold_ns != NULL with q_ppm != 0; SA_ENOMEM when the device
+ * scratch (the pooled sums, n_services x 2 KiB, the pairs, 16 B a window and
+ * service, 40 B and a candidate a service, and the select's state, allocated by
+ * the first call) or the result cannot be allocated.  The engine stays usable
+ * after any error.  Free with sa_onset_result_free. */
+int sa_window_latency_onset(sa_engine *e, uint64_t first, uint64_t last, uint32_t k, uint32_t q_ppm,
+                            const uint64_t *threshold_ns, uint64_t min_count, uint32_t min_delta_ppm,
+                            uint32_t flags, sa_onset_result **out);
+void sa_onset_result_free(sa_onset_result *r);
+
 int sa_get_stats(sa_engine *e, sa_stats *out);
 
 /* ---- multi-GPU merge hooks (device pointers on this engine's device) ----
@@ -861,6 +937,17 @@ int sa_group_window_latency_movers(sa_group *g, uint64_t base_first, uint64_t ba
 int sa_group_window_slo(sa_group *g, uint64_t first, uint64_t last, const uint32_t *widths,
                         const uint32_t *limit_ppm, uint32_t n_widths, const uint32_t *services, uint32_t n_sel,
                         const uint64_t *threshold_ns, uint64_t min_count, uint32_t flags, sa_slo_result **out);
+/* sa_window_latency_onset of a group, in two rounds of the transport.  With a
+ * pooled threshold every member first sums the range of its own ring per
+ * service, the transport adds the members' sums and leaves them on every
+ * member, and each member takes the same threshold bins from them (with
+ * threshold_ns given this round is skipped).  Then every member cuts its rows
+ * to (total, slow) pairs, the transport adds the pairs, and member 0's device
+ * scans, selects and reads the rows.  Results equal those of one engine fed
+ * every span, bit for bit. */
+int sa_group_window_latency_onset(sa_group *g, uint64_t first, uint64_t last, uint32_t k, uint32_t q_ppm,
+                                  const uint64_t *threshold_ns, uint64_t min_count, uint32_t min_delta_ppm,
+                                  uint32_t flags, sa_onset_result **out);
 /* Counters summed over members (n_keys and table_capacity too; window_base and
  * small_table from member 0). */
 int sa_group_get_stats(sa_group *g, sa_stats *out);

@@ -35,6 +35,18 @@ int sa_expo_fast_probe(sa_engine *e, const uint64_t *d_ns, const int32_t *scale,
  * in[0 .. n) ascending (host arrays; out holds n; n <= 2^28). */
 int sa_key_union_probe(sa_engine *e, const uint64_t *in, uint64_t n, uint64_t *out, uint64_t *n_out);
 
+/* Diagnostic: sa_window_latency_onset's scan, select and rows on the caller's
+ * own pairs (host, [n_sel][n_cov][2] u64: service i's window j as {total,
+ * slow}) instead of a ring's: the only way to reach the 128-bit arithmetic --
+ * counts near 2^43 -- in a test that takes seconds.  The result reads as
+ * sa_window_latency_onset's with first_window 0, last_window n_cov - 1,
+ * n_services n_sel and q_ppm 0; threshold_bin and effective_ns come back 0.
+ * Any engine serves (the ring is not read).  SA_EINVAL for a null pointer,
+ * n_sel or n_cov of 0, n_sel * n_cov > 2^18, and k and flags as
+ * sa_window_latency_onset.  Free with sa_onset_result_free. */
+int sa_onset_probe(sa_engine *e, const uint64_t *pairs, uint32_t n_sel, uint32_t n_cov, uint32_t k,
+                   uint64_t min_count, uint32_t min_delta_ppm, uint32_t flags, sa_onset_result **out);
+
 /* Diagnostic only: per-workgroup s_memrealtime stamps (100 MHz) of the last
  * small-table ingest launch, [G][136] = {start, after LDS setup, after the span
  * loop, after the slab flush, 0 x 4, then per wave 8 segment cycle sums};

@@ -1,8 +1,10 @@
 // engine_latency.cpp -- the queries over the ring of latency histograms of an
-// SA_OPT_WINDOW_LATENCY engine: sa_window_latency, sa_window_latency_movers and
-// sa_window_slo (kernels in spanagg_latency.hip, the movers' select in spanagg_range.hip),
-// each with the asynchronous halves the engine group runs per member (sa_grp,
-// sa_group_hooks.h) and its result's free.  Arguments: sa_query_args.h.
+// SA_OPT_WINDOW_LATENCY engine: sa_window_latency, sa_window_latency_movers,
+// sa_window_slo and sa_window_latency_onset (kernels in spanagg_latency.hip, the
+// movers' and the onset's select in spanagg_range.hip), each with the
+// asynchronous halves the engine group runs per member (sa_grp,
+// sa_group_hooks.h) and its result's free; and sa_onset_probe (spanagg_diag.h),
+// the onset's scan on a caller's pairs.  Arguments: sa_query_args.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -16,6 +18,7 @@
 #include "sa_engine.h"
 #include "sa_group_hooks.h"
 #include "sa_results.h"
+#include "spanagg_diag.h"
 
 namespace {
 
@@ -159,6 +162,95 @@ hipError_t slo_pairs_on(sa_engine *e, const std::vector<uint32_t> &sel, const st
                               n_cov, d_pairs, s);
   if (st != hipSuccess) (void)hipStreamSynchronize(s);
   return st;
+}
+
+// ---- latency onset (sa_window_latency_onset) ----
+const char *const kOnset = "window latency onset";
+
+// Room for every service's threshold bin, and for what the stages after the
+// pairs work in -- n_sel services' best splits and candidates, the rows, and
+// sa_window_top's control block.
+int onset_buffers(sa_engine *e, uint64_t n_sel) {
+  sa_engine::Latency &L = e->lat;
+  const uint64_t want = std::max<uint64_t>(n_sel, 64);
+  if (int rc = lazy(e, e->top.ctl, 1, "window latency onset: control block hipMalloc failed")) return rc;
+  if (int rc = lazy(e, L.onset_out, 1, "window latency onset: row buffer hipMalloc failed")) return rc;
+  if (int rc = grow(e, L.onset_thr, L.onset_thr_cap, want, "window latency onset: threshold buffer hipMalloc failed"))
+    return rc;
+  if (int rc = grow(e, L.onset_rec, L.onset_rec_cap, want, "window latency onset: split buffer hipMalloc failed")) return rc;
+  return grow(e, L.onset_cand, L.onset_cand_cap, want, "window latency onset: candidate buffer hipMalloc failed");
+}
+
+// A member's pairs stage on `s`: its threshold bins -- `bins` (host, one a
+// service) copied, or the bins of quantile q_ppm of d_sums -- then d_pairs
+// [n_services][n_cov][2] from window `first` on, every service selected.  The
+// copy reads the caller's pageable `bins` asynchronously: as latency_sums_on's.
+hipError_t onset_pairs_on(sa_engine *e, const uint8_t *bins, const unsigned long long *d_sums, uint32_t q_ppm,
+                          uint64_t first, uint32_t n_cov, unsigned long long *d_pairs, hipStream_t s) {
+  const sa_engine::Latency &L = e->lat;
+  const uint32_t S = e->cfg.n_services, W = e->cfg.n_windows;
+  hipError_t st = bins ? hipMemcpyAsync(L.onset_thr, bins, S, hipMemcpyHostToDevice, s)
+                       : sa::launch_onset_thr(nullptr, S, W, first, n_cov, q_ppm,
+                                              const_cast<unsigned long long *>(d_sums), L.onset_thr, s);
+  if (st == hipSuccess) st = sa::launch_slo_pairs(L.ring, S, W, nullptr, L.onset_thr, S, first, n_cov, d_pairs, s);
+  if (st != hipSuccess) (void)hipStreamSynchronize(s);
+  return st;
+}
+
+// The stages after the pairs on `s` -- the scan, the select and the sort, the
+// selected rows -- the copies, the call's one wait and the result: d_pairs
+// [n_sel][n_cov][2] with n_cov = last - first + 1, d_thr [n_sel] the services'
+// threshold bins (nullptr: the probe's, 0).  onset_buffers(e, n_sel) made room.
+int onset_collect(sa_engine *e, uint64_t first, uint64_t last, uint32_t n_sel, uint32_t k, uint32_t q_ppm,
+                  const uint8_t *d_thr, uint64_t min_count, uint32_t min_delta_ppm, uint32_t flags,
+                  const unsigned long long *d_pairs, hipStream_t s, sa_onset_result **out) {
+  const sa_engine::Latency &L = e->lat;
+  sa::TopCtl *T = e->top.ctl;
+  const uint64_t mc = std::max<uint64_t>(min_count, 1);
+  unsigned long long head[4] = {};
+  std::vector<ulonglong2> sel;
+  std::vector<unsigned char> rows;  // OnsetOut's head and its first k rows
+  try {
+    sel.resize(k);
+    rows.resize(offsetof(sa::OnsetOut, row) + (size_t)k * sizeof(sa::OnsetRow));
+  } catch (const std::bad_alloc &) {
+    return fail(e, SA_ENOMEM, "window latency onset: the rows do not fit in host memory");
+  }
+  // (the scratch is the engine's: after its own earlier use, before its next)
+  if (int rc = hop_to(e, s)) return rc;
+  hipError_t st = sa::launch_onset(d_pairs, n_sel, (uint32_t)(last - first + 1), k, mc, std::max(min_delta_ppm, 1u),
+                                   flags & SA_ONSET_FALL ? 1u : 0u, d_thr, L.onset_rec, L.onset_cand, T, L.onset_out, s);
+  if (st == hipSuccess) st = copy_top(T, k, head, sel.data(), s);
+  if (st == hipSuccess) st = hipMemcpyAsync(rows.data(), L.onset_out, rows.size(), hipMemcpyDeviceToHost, s);
+  const hipError_t waited = hipStreamSynchronize(s);  // the call's one wait (also after a failure: copies may be in flight)
+  if (st != hipSuccess || waited != hipSuccess)
+    return fail(e, SA_EDEVICE, std::string("window latency onset: ") + hipGetErrorString(st != hipSuccess ? st : waited));
+  const uint32_t n = (uint32_t)std::min<uint64_t>(k, head[0]);
+  std::unique_ptr<onset_holder> h;
+  try {
+    h.reset(new onset_holder());
+    h->shape(first, last, k, n, flags, q_ppm, mc, n_sel);
+  } catch (const std::bad_alloc &) {
+    return fail(e, SA_ENOMEM, "window latency onset: the result does not fit in host memory");
+  }
+  // (TopCtl's head: the matches, the eligible services, ..; OnsetOut's: the range's spans)
+  h->r.n_matched = head[0], h->r.n_eligible = head[1];
+  std::memcpy(&h->r.spans, rows.data(), 8);
+  for (uint32_t i = 0; i < n; ++i) {
+    sa::OnsetRow row;
+    std::memcpy(&row, rows.data() + offsetof(sa::OnsetOut, row) + (size_t)i * sizeof row, sizeof row);
+    h->services[i] = (uint32_t)sel[i].y;
+    h->delta_ppm[i] = (int32_t)(sel[i].x >> 44);
+    h->onset_window[i] = first + row.t;
+    h->total_before[i] = row.total_before, h->slow_before[i] = row.slow_before;
+    h->total_after[i] = row.total_after, h->slow_after[i] = row.slow_after;
+    h->threshold_bin[i] = (uint8_t)row.thr_bin;
+    uint64_t lo = 0, hi = 0;
+    if (d_thr) (void)sa_latency_bin_bounds((uint32_t)row.thr_bin, &lo, &hi);
+    h->effective_ns[i] = hi;
+  }
+  *out = &h.release()->r;
+  return SA_OK;
 }
 }  // namespace
 
@@ -324,6 +416,44 @@ int window_slo_finish(sa_engine *e, uint64_t first, uint64_t last, const uint32_
   *out = &h.release()->r;
   return SA_OK;
 }
+
+int window_onset_sums_export_async(sa_engine *e, uint64_t first, uint64_t last, uint64_t *d_sums, hipStream_t s) {
+  if (!e || !d_sums) return SA_EINVAL;
+  if (int rc = latency_enabled(e, kOnset)) return rc;
+  if (int rc = check_span(e, kOnset, first, last, 1)) return rc;
+  if (int rc = begin_read(e)) return rc;
+  if (int rc = hop_to(e, s)) return rc;
+  SA_HIP(e, sa::launch_onset_thr(e->lat.ring, e->cfg.n_services, e->cfg.n_windows, first, (uint32_t)(last - first + 1), 0,
+                                 reinterpret_cast<unsigned long long *>(d_sums), nullptr, s));
+  return hop_back(e, s);  // (a later launch that writes the ring orders after these reads)
+}
+
+int window_onset_pairs_export_async(sa_engine *e, uint64_t first, uint64_t last, const uint8_t *bins,
+                                    const uint64_t *d_sums, uint32_t q_ppm, uint64_t *d_pairs, hipStream_t s) {
+  if (!e || !d_pairs || (!bins && !d_sums)) return SA_EINVAL;
+  if (int rc = latency_enabled(e, kOnset)) return rc;
+  if (int rc = check_span(e, kOnset, first, last, 1)) return rc;
+  if (int rc = begin_read(e)) return rc;
+  if (int rc = onset_buffers(e, e->cfg.n_services)) return rc;
+  if (int rc = hop_to(e, s)) return rc;
+  SA_HIP(e, onset_pairs_on(e, bins, reinterpret_cast<const unsigned long long *>(d_sums), q_ppm, first,
+                           (uint32_t)(last - first + 1), reinterpret_cast<unsigned long long *>(d_pairs), s));
+  if (int rc = hop_back(e, s)) {  // (the threshold buffer is the engine's)
+    (void)hipStreamSynchronize(s);
+    return rc;
+  }
+  return SA_OK;
+}
+
+int window_onset_finish(sa_engine *e, uint64_t first, uint64_t last, uint32_t k, uint32_t q_ppm, bool pooled,
+                        uint64_t min_count, uint32_t min_delta_ppm, uint32_t flags, const uint64_t *d_pairs,
+                        hipStream_t s, sa_onset_result **out) {
+  if (!e || !out || !d_pairs || first > last) return SA_EINVAL;
+  if (int rc = set_dev(e)) return rc;
+  if (int rc = onset_buffers(e, e->cfg.n_services)) return rc;  // (the pairs stage made them: nothing grows)
+  return onset_collect(e, first, last, e->cfg.n_services, k, pooled ? q_ppm : 0, e->lat.onset_thr, min_count,
+                       min_delta_ppm, flags, reinterpret_cast<const unsigned long long *>(d_pairs), s, out);
+}
 }  // namespace sa_grp
 
 extern "C" {
@@ -426,5 +556,68 @@ int sa_window_slo(sa_engine *e, uint64_t first, uint64_t last, const uint32_t *w
 }
 
 void sa_slo_result_free(sa_slo_result *r) { delete reinterpret_cast<slo_holder *>(r); }
+
+int sa_window_latency_onset(sa_engine *e, uint64_t first, uint64_t last, uint32_t k, uint32_t q_ppm,
+                            const uint64_t *threshold_ns, uint64_t min_count, uint32_t min_delta_ppm, uint32_t flags,
+                            sa_onset_result **out) {
+  if (!e || !out) return SA_EINVAL;
+  *out = nullptr;
+  if (int rc = latency_enabled(e, kOnset)) return rc;
+  if (const char *bad = sa_args::onset_args(k, q_ppm, threshold_ns, flags)) return bad_args(e, SA_EINVAL, kOnset, bad);
+  if (int rc = check_span(e, kOnset, first, last, 1)) return rc;
+  const uint32_t S = e->cfg.n_services, n_cov = (uint32_t)(last - first + 1);
+  std::vector<uint8_t> bins;
+  if (threshold_ns) {
+    try {
+      bins.resize(S);
+    } catch (const std::bad_alloc &) {
+      return fail(e, SA_ENOMEM, "window latency onset: the thresholds do not fit in host memory");
+    }
+    for (uint32_t i = 0; i < S; ++i) bins[i] = (uint8_t)sa_latency_bin(threshold_ns[i]);
+  }
+  if (int rc = begin_read(e)) return rc;
+  sa_engine::Latency &L = e->lat;
+  if (int rc = onset_buffers(e, S)) return rc;
+  if (int rc = grow(e, L.onset_pairs, L.onset_pairs_cap, (uint64_t)S * n_cov * 2,
+                    "window latency onset: pair buffer hipMalloc failed"))
+    return rc;
+  if (!threshold_ns) {  // the pooled threshold: the range's rows of the engine's own ring summed
+    if (int rc = grow(e, L.onset_sums, L.onset_sums_cap, (uint64_t)S * SA_LAT_BINS,
+                      "window latency onset: sum buffer hipMalloc failed"))
+      return rc;
+    SA_HIP(e, sa::launch_onset_thr(L.ring, S, e->cfg.n_windows, first, n_cov, 0, L.onset_sums, nullptr, e->stream));
+  }
+  // (the pairs of the engine's own ring, then the stages a group runs on its member 0 after adding the
+  // members' pairs; a failed launch has waited for the copy out of bins)
+  SA_HIP(e, onset_pairs_on(e, threshold_ns ? bins.data() : nullptr, L.onset_sums, q_ppm, first, n_cov, L.onset_pairs,
+                           e->stream));
+  const int rc = onset_collect(e, first, last, S, k, q_ppm, L.onset_thr, min_count, min_delta_ppm, flags, L.onset_pairs,
+                               e->stream, out);
+  if (rc != SA_OK) (void)hipStreamSynchronize(e->stream);  // (a collect that failed early: the copy may be in flight)
+  return rc;
+}
+
+void sa_onset_result_free(sa_onset_result *r) { delete reinterpret_cast<onset_holder *>(r); }
+
+int sa_onset_probe(sa_engine *e, const uint64_t *pairs, uint32_t n_sel, uint32_t n_cov, uint32_t k, uint64_t min_count,
+                   uint32_t min_delta_ppm, uint32_t flags, sa_onset_result **out) {
+  if (!e || !out) return SA_EINVAL;
+  *out = nullptr;
+  if (!pairs || !n_sel || !n_cov || (uint64_t)n_sel * n_cov > (1ull << 18))
+    return bad_args(e, SA_EINVAL, "onset probe", "null pairs, or n_sel * n_cov outside 1..2^18");
+  if (const char *bad = sa_args::top_k(k)) return bad_args(e, SA_EINVAL, "onset probe", bad);
+  if (const char *bad = sa_args::flags(flags, SA_ONSET_FALL)) return bad_args(e, SA_EINVAL, "onset probe", bad);
+  if (int rc = begin_read(e)) return rc;
+  sa_engine::Latency &L = e->lat;
+  if (int rc = onset_buffers(e, n_sel)) return rc;
+  if (int rc = grow(e, L.onset_pairs, L.onset_pairs_cap, (uint64_t)n_sel * n_cov * 2, "onset probe: pair buffer hipMalloc failed"))
+    return rc;
+  // (the copy reads the caller's pageable pairs asynchronously: the collect waits for the stream)
+  SA_HIP(e, hipMemcpyAsync(L.onset_pairs, pairs, (size_t)n_sel * n_cov * 16, hipMemcpyHostToDevice, e->stream));
+  const int rc = onset_collect(e, 0, n_cov - 1, n_sel, k, 0, nullptr, min_count, min_delta_ppm, flags, L.onset_pairs,
+                               e->stream, out);
+  if (rc != SA_OK) (void)hipStreamSynchronize(e->stream);
+  return rc;
+}
 
 }  // extern "C"

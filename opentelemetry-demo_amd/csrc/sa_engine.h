@@ -4,7 +4,8 @@
 // engine_read.cpp (flush, reclamation, stats, sa_bind_ids, the probes, one
 // window's sketches and the merge hooks), engine_window.cpp (the queries over
 // the sketch ring: range, series, top, movers, overlap) and engine_latency.cpp
-// (latency and latency movers).  One engine owns one gfx950 device.
+// (latency, latency movers, SLO burn and latency onset).  One engine owns one
+// gfx950 device.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -263,6 +264,19 @@ struct sa_engine {
     uint8_t *slo_thr = nullptr;
     unsigned long long *slo_pairs = nullptr, *slo_prefix = nullptr, *slo_out = nullptr;
     uint64_t slo_thr_cap = 0, slo_pairs_cap = 0, slo_prefix_cap = 0, slo_out_cap = 0;
+    // sa_window_latency_onset and sa_onset_probe, grown like sums by the first
+    // call (the probe's services need not be the engine's): every service's
+    // threshold bin [onset_thr_cap], the engine's own pooled sums
+    // [onset_sums_cap] u64 ([n_services][SA_LAT_BINS]) and pairs
+    // [onset_pairs_cap] u64 ([n_services][n_cov][2]), every service's best
+    // split [onset_rec_cap] and the candidates [onset_cand_cap]; the selected
+    // rows onset_out; the select works in sa_window_top's control block
+    uint8_t *onset_thr = nullptr;
+    unsigned long long *onset_sums = nullptr, *onset_pairs = nullptr;
+    sa::OnsetRow *onset_rec = nullptr;
+    ulonglong2 *onset_cand = nullptr;
+    sa::OnsetOut *onset_out = nullptr;
+    uint64_t onset_thr_cap = 0, onset_sums_cap = 0, onset_pairs_cap = 0, onset_rec_cap = 0, onset_cand_cap = 0;
   } lat;
   // sa_ingest: two pinned host slots and their HBM copies; a slot is refilled
   // once its event (H2D copy + aggregation of the previous use) has passed

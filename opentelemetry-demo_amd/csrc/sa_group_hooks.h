@@ -97,6 +97,26 @@ int window_slo_export_async(sa_engine *e, uint64_t first, uint64_t last, const u
 int window_slo_finish(sa_engine *e, uint64_t first, uint64_t last, const uint32_t *widths, const uint32_t *limit_ppm,
                       uint32_t n_widths, const std::vector<uint32_t> &sel, const uint64_t *threshold_ns,
                       uint64_t min_count, const uint64_t *d_pairs, hipStream_t s, sa_slo_result **out);
+// sa_window_latency_onset's pooled sums for one member, without the wait:
+// d_sums [n_services][SA_LAT_BINS] = every service's rows summed over
+// first..last, on `s`.  SA_ESTATE without the option, SA_ERANGE as
+// sa_window_range.
+int window_onset_sums_export_async(sa_engine *e, uint64_t first, uint64_t last, uint64_t *d_sums, hipStream_t s);
+// its pairs stage for one member, without the wait: the member's threshold
+// bins -- bins [n_services] (host; must stay until `s` has been waited for),
+// or with bins == nullptr the bins of quantile q_ppm of d_sums (the members'
+// summed rows, on this member's device) -- then d_pairs [n_services][n_cov]
+// [2], n_cov = last - first + 1, cut at them, on `s`.  Errors as the sums'.
+int window_onset_pairs_export_async(sa_engine *e, uint64_t first, uint64_t last, const uint8_t *bins,
+                                    const uint64_t *d_sums, uint32_t q_ppm, uint64_t *d_pairs, hipStream_t s);
+// the rest of the query, on `e` (a group's member 0, whose device holds the
+// members' summed d_pairs and, from its own pairs stage, the threshold bins)
+// and on `s`: the scan, the select and the sort, the selected rows, the copies
+// and the wait.  The arguments (sa_args::onset_args passed them; pooled: no
+// threshold_ns was given) and *out as sa_window_latency_onset.
+int window_onset_finish(sa_engine *e, uint64_t first, uint64_t last, uint32_t k, uint32_t q_ppm, bool pooled,
+                        uint64_t min_count, uint32_t min_delta_ppm, uint32_t flags, const uint64_t *d_pairs,
+                        hipStream_t s, sa_onset_result **out);
 // What one engine's heavy-hitter scan leaves on the host once its stream
 // passes the copies: head = the matches, the resident keys, the largest
 // estimate, error_spans; rows [k] = (estimate, key) pairs, the first

@@ -584,8 +584,8 @@ hipError_t launch_lat_movers(const unsigned long long *sums, uint32_t n_services
                              hipStream_t s);
 // latency SLO burn (sa_window_slo; DESIGN.md section 4, "Latency SLO burn
 // over sliding widths").  pairs [n_sel][n_cov][2] u64: covered window k =
-// window a + k of the ring, service sel[i] (device): {its row's spans, those
-// in bins above thr_bin[i] (device)}
+// window a + k of the ring, service sel[i] (device; nullptr: service i, n_sel
+// <= n_services): {its row's spans, those in bins above thr_bin[i] (device)}
 hipError_t launch_slo_pairs(const unsigned long long *ring, uint32_t n_services, uint32_t n_windows, const uint32_t *sel,
                             const uint8_t *thr_bin, uint32_t n_sel, uint64_t a, uint32_t n_cov,
                             unsigned long long *pairs, hipStream_t s);
@@ -597,6 +597,36 @@ hipError_t launch_slo_slide(const unsigned long long *pairs, uint32_t n_sel, uin
                             const uint32_t *limit_ppm, uint32_t n_widths, unsigned long long min_count,
                             unsigned long long *prefix, unsigned long long *total, unsigned long long *slow,
                             uint8_t *burning, uint32_t *alert, hipStream_t s);
+// latency onset (sa_window_latency_onset; DESIGN.md section 4, "Latency onset
+// over the window ring").  A service's best split: t (the first window of
+// "after", counted from the range's first; 0: no eligible split), the two
+// sides' (total, slow) sums, and in a returned row its threshold bin.
+struct OnsetRow {
+  unsigned long long t, total_before, slow_before, total_after, slow_after, thr_bin;
+};
+// What the call leaves beside TopCtl: the range's spans and the selected rows
+// in T->sel's order (192 KiB; the head and the first k rows are one copy).
+struct OnsetOut {
+  unsigned long long spans, pad;
+  OnsetRow row[kTopSel];
+};
+// The pooled threshold's two steps on `s`, either left out by a null pointer:
+// ring != nullptr: sums [n_services][SA_LAT_BINS] = every service's rows summed
+// over windows first .. first + len - 1 (1 <= len <= n_windows); thr_bin !=
+// nullptr: thr_bin [n_services] = the bin of quantile q_ppm of each row of sums
+// (sa_window_latency's rule).  A group adds its members' sums between the two.
+hipError_t launch_onset_thr(const unsigned long long *ring, uint32_t n_services, uint32_t n_windows, uint64_t first,
+                            uint32_t len, uint32_t q_ppm, unsigned long long *sums, uint8_t *thr_bin, hipStream_t s);
+// The rest of the query on `s`, from pairs [n_sel][n_cov][2] (launch_slo_pairs
+// over every service): every service's best split into rec [n_sel] and its
+// candidate into cand [n_sel] (min_count >= 1, min_delta >= 1, fall 0 or 1),
+// the select and the sort -- T->sel[0 .. min(k, T->n_matched)) = (delta_ppm <<
+// 44 | min(count, 2^44 - 1), service) in the call's order, T->n_resident the
+// eligible services -- and O: the range's spans and the selected rows with
+// their threshold bins (thr_bin [n_sel], device; nullptr: 0).  k <= kTopSel.
+hipError_t launch_onset(const unsigned long long *pairs, uint32_t n_sel, uint32_t n_cov, uint32_t k,
+                        unsigned long long min_count, uint32_t min_delta, uint32_t fall, const uint8_t *thr_bin,
+                        OnsetRow *rec, ulonglong2 *cand, TopCtl *T, OnsetOut *O, hipStream_t s);
 // sorted union of series ids on the device (spanagg_union.hip): out = the
 // distinct non-zero ids of in[0..n) ascending, *d_total (device u32) their
 // count; scratch >= key_union_scratch_bytes(n); big_scratch / big_bytes: a

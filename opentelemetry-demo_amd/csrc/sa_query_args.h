@@ -135,5 +135,15 @@ inline const char *slo_rows(uint64_t n_out, uint64_t n_sel) {
   return n_out * n_sel > 1ull << 20 ? "n_out * n_sel above 2^20" : nullptr;
 }
 
+// sa_window_latency_onset's arguments, the range apart: k, the one flag, and
+// the threshold's two forms -- given (threshold_ns != nullptr, one a service,
+// any u64: q_ppm must be 0) or pooled (q_ppm in 1..10^6)
+inline const char *onset_args(uint32_t k, uint32_t q, const uint64_t *threshold_ns, uint32_t flag_bits) {
+  if (const char *bad = top_k(k)) return bad;
+  if (const char *bad = flags(flag_bits, SA_ONSET_FALL)) return bad;
+  if (threshold_ns) return q ? "q_ppm != 0 with threshold_ns given" : nullptr;
+  return q == 0 || q > 1000000u ? "null threshold_ns with q_ppm outside 1..1000000" : nullptr;
+}
+
 }  // namespace sa_args
 #pragma GCC visibility pop

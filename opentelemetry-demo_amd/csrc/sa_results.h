@@ -265,6 +265,26 @@ struct slo_holder {
   }
 };
 
+struct onset_holder {
+  sa_onset_result r;
+  std::vector<uint32_t> services;
+  std::vector<int32_t> delta_ppm;
+  std::vector<uint8_t> threshold_bin;
+  std::vector<uint64_t> onset_window, effective_ns, total_before, slow_before, total_after, slow_after;
+  // the columns sized for n rows, and r pointing at them
+  __attribute__((visibility("hidden"))) void shape(uint64_t first, uint64_t last, uint32_t k, uint32_t n, uint32_t flags,
+                                                   uint32_t q_ppm, uint64_t min_count, uint64_t n_services) {
+    services.resize(n), delta_ppm.resize(n), threshold_bin.resize(n), onset_window.resize(n), effective_ns.resize(n);
+    total_before.resize(n), slow_before.resize(n), total_after.resize(n), slow_after.resize(n);
+    r.first_window = first, r.last_window = last, r.k = k, r.n = n, r.flags = flags, r.q_ppm = q_ppm;
+    r.min_count = min_count, r.n_services = n_services, r.n_eligible = r.n_matched = r.spans = 0;
+    r.services = services.data(), r.onset_window = onset_window.data(), r.delta_ppm = delta_ppm.data();
+    r.threshold_bin = threshold_bin.data(), r.effective_ns = effective_ns.data();
+    r.total_before = total_before.data(), r.slow_before = slow_before.data();
+    r.total_after = total_after.data(), r.slow_after = slow_after.data();
+  }
+};
+
 struct sketch_holder {
   sa_sketch_result r;
   std::vector<uint8_t> hll;

@@ -314,7 +314,8 @@ struct sa_group {
   std::vector<Buf> keys, gath, uni, rows, hll, cms;
   std::vector<Buf> cms_base;  // sa_group_window_movers: the baseline range's cells beside cms (the current range's)
   std::vector<Buf> lat;       // sa_group_window_latency: every member's sliding sums [n_out][n_sel][SA_LAT_BINS]
-                              // (the movers' two ranges' sums, sa_group_window_slo's pairs)
+                              // (the movers' two ranges' sums, sa_group_window_slo's and the onset's pairs)
+  std::vector<Buf> lat_pool;  // sa_group_window_latency_onset: every service's pooled sums [n_services][SA_LAT_BINS]
   std::vector<Buf> srt, ucnt;  // device key union (sa::key_union): its scratch and the distinct count
   std::vector<uint64_t *> big;  // key_union's scratch for oversized buckets (per member)
   std::vector<size_t> big_bytes;
@@ -639,6 +640,7 @@ int sa_group_create(const sa_config *cfg, const int32_t *devices, uint32_t n, sa
   g->cms.resize(n);
   g->cms_base.resize(n);
   g->lat.resize(n);
+  g->lat_pool.resize(n);
   g->dropped_seen.assign(n, 0);
   g->pcnt.resize(2 * n);
   g->hcol.resize(n);
@@ -690,7 +692,7 @@ void sa_group_destroy(sa_group *g) {
       (void)hipStreamSynchronize(g->st[i]);
       (void)hipStreamDestroy(g->st[i]);
     }
-    for (std::vector<Buf> *v : {&g->keys, &g->gath, &g->uni, &g->rows, &g->hll, &g->cms, &g->cms_base, &g->lat, &g->srt, &g->ucnt})
+    for (std::vector<Buf> *v : {&g->keys, &g->gath, &g->uni, &g->rows, &g->hll, &g->cms, &g->cms_base, &g->lat, &g->lat_pool, &g->srt, &g->ucnt})
       if (i < v->size() && (*v)[i].p) (void)hipFree((*v)[i].p);
     if (i < g->big.size() && g->big[i]) (void)hipFree(g->big[i]);
     for (size_t k = 0; k < 2; ++k)
@@ -1371,6 +1373,54 @@ int sa_group_window_slo(sa_group *g, uint64_t first, uint64_t last, const uint32
                                           min_count, buf<uint64_t>(g->lat, 0), g->st[0], out))
       rc = member_error(g, 0, f, what);
   return end_query(g, what, rc, merged, out, sa_slo_result_free);
+}
+
+// Two rounds of the transport.  Pooled threshold: each member sums the range of
+// its own ring per service, the transport adds the members' sums and leaves
+// them on every member -- as it leaves the movers' cells -- and each member
+// takes the same threshold bins from them.  Then each member cuts its rows to
+// (total, slow) pairs at those bins (or at the caller's thresholds' bins: no
+// first round), the transport adds the pairs, and member 0's device scans,
+// selects and reads the rows.
+int sa_group_window_latency_onset(sa_group *g, uint64_t first, uint64_t last, uint32_t k, uint32_t q_ppm,
+                                  const uint64_t *threshold_ns, uint64_t min_count, uint32_t min_delta_ppm,
+                                  uint32_t flags, sa_onset_result **out) {
+  if (!g || !out) return SA_EINVAL;
+  *out = nullptr;
+  const char *const what = "window latency onset";
+  if (const char *bad = sa_args::latency_option(g->cfg.options)) return bad_args(g, SA_ESTATE, what, bad);
+  if (const char *bad = sa_args::onset_args(k, q_ppm, threshold_ns, flags)) return bad_args(g, SA_EINVAL, what, bad);
+  const uint64_t S = g->cfg.n_services;
+  const bool pooled = !threshold_ns;
+  std::vector<uint8_t> bins(pooled ? 0 : S);
+  for (size_t i = 0; i < bins.size(); ++i) bins[i] = (uint8_t)sa_latency_bin(threshold_ns[i]);
+  // (the members check the range against their rings; a range that passes has n_cov <= n_windows)
+  const uint64_t n_cov = first <= last && last - first < g->cfg.n_windows ? last - first + 1 : 0;
+  // every member's pooled sums [n_services][SA_LAT_BINS] and pairs [n_services][n_cov][2]
+  const std::vector<Part> pool = {{&g->lat_pool, pooled ? S * SA_LAT_BINS : 1, false}};
+  const std::vector<Part> pairs = {{&g->lat, n_cov ? S * n_cov * 2 : 1, false}};
+  if (int rc = ensure_parts(g, pool)) return rc;
+  if (int rc = ensure_parts(g, pairs)) return rc;
+  int rc = SA_OK, merged = SA_OK;
+  if (pooled) {
+    rc = each_member(g, what, [&](uint32_t i) {
+      return sa_grp::window_onset_sums_export_async(g->eng[i], first, last, buf<uint64_t>(g->lat_pool, i), g->st[i]);
+    });
+    merged = rc ? SA_OK : sum_cells_everywhere(g, pool);
+  }
+  if (!rc && !merged) {
+    rc = each_member(g, what, [&](uint32_t i) {  // (the copy out of `bins` ends before end_query returns)
+      return sa_grp::window_onset_pairs_export_async(g->eng[i], first, last, pooled ? nullptr : bins.data(),
+                                                     buf<uint64_t>(g->lat_pool, i), q_ppm, buf<uint64_t>(g->lat, i),
+                                                     g->st[i]);
+    });
+    merged = rc ? SA_OK : reduce_members(g, pairs);
+  }
+  if (!rc && !merged)
+    if (int f = sa_grp::window_onset_finish(g->eng[0], first, last, k, q_ppm, pooled, min_count, min_delta_ppm, flags,
+                                            buf<uint64_t>(g->lat, 0), g->st[0], out))
+      rc = member_error(g, 0, f, what);
+  return end_query(g, what, rc, merged, out, sa_onset_result_free);
 }
 
 int sa_group_window_advance(sa_group *g, uint64_t new_base) {

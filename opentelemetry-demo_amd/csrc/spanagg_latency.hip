@@ -27,7 +27,17 @@
 //                      -- the ring read once whatever the widths -- then
 //                      prefix sums along the windows, every width's sums as
 //                      the difference of two prefixes, and the burn rule.
+//   onset_thr_kernel, onset_scan_kernel, onset_rows_kernel
+//                      sa_window_latency_onset: every service's pooled quantile
+//                      bin from its rows summed over the range (the movers'
+//                      sums kernel, one range), its (total, slow) pairs (the
+//                      SLO's pairs kernel), then per service the split of the
+//                      range with the largest D = S_a N_b - S_b N_a in 128
+//                      bits, the change of the slow share as the score -- the
+//                      select and the sort are the heavy hitters' -- and the
+//                      selected services' records.
 //
+
 // The two query stages are apart because a group adds its members' sums
 // between them.  Every cell is an integer sum, so the order of the atomics
 // does not show: two calls, and one engine against a group, give the same bits.
@@ -274,30 +284,32 @@ constexpr uint32_t kLatScoreGrid = 512;    // the score stage's workgroups, whil
 constexpr uint32_t kLatScoreIters = 8;     // ... this many services (65,536 services: exactly both)
 constexpr uint32_t kLatScoreList = kLatScoreBlock / 64 * kLatScoreIters;  // a workgroup's matches in LDS
 
-// Unit u = r * n_services + s is service s over range r (0 the baseline, 1 the
-// current one): windows first[r] .. first[r] + len[r] - 1.  A unit is `stripes`
+// Unit u = r * n_services + s is service s over range r < n_ranges (0 the
+// baseline, 1 the current one; sa_window_latency_onset sums one range):
+// windows first[r] .. first[r] + len[r] - 1.  A unit is `stripes`
 // waves (1, 2 or a multiple of 4, so the waves of a workgroup that share a
 // unit are `grp` = min(stripes, 4) neighbours); stripe t sums the t-th run of
 // ceil(len / stripes) consecutive windows of the unit (interleaved stripes
 // took 8 % longer on a 1,024-window ring) -- lane l bins 4l .. 4l + 3, a row
 // one coalesced 2 KiB read, four rows in flight -- and the grp waves add up
 // through LDS.
-// Up to 4 stripes the first wave stores the unit's row of sums [2][n_services]
-// [256]; above, the workgroups of a unit add theirs to the row (zeroed by the
+// Up to 4 stripes the first wave stores the unit's row of sums [n_ranges]
+// [n_services][256]; above, the workgroups of a unit add theirs to the row (zeroed by the
 // launcher) -- integer adds, so neither the split nor the order shows.  The
 // ring index stays below (win_mask + 1) * n_services * 256: s < n_services, and
 // k < len[r] <= win_mask + 1.
 __global__ __launch_bounds__(kLatPairBlock) void lat_pair_sums_kernel(const unsigned long long *__restrict__ ring,
                                                                       uint32_t n_services, uint32_t win_mask,
                                                                       uint64_t first_b, uint32_t len_b, uint64_t first_c,
-                                                                      uint32_t len_c, uint32_t stripes, uint32_t grp,
+                                                                      uint32_t len_c, uint32_t n_ranges,
+                                                                      uint32_t stripes, uint32_t grp,
                                                                       unsigned long long *__restrict__ sums) {
   __shared__ unsigned long long part[kLatPairBlock / 64][SA_LAT_BINS];
   const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
   const uint64_t gw = (uint64_t)blockIdx.x * (kLatPairBlock / 64) + wv;
   const uint64_t u = gw / stripes;
   const uint32_t t = (uint32_t)(gw % stripes);
-  const bool live = u < 2ull * n_services;  // (wave-uniform; a dead wave still meets the barrier)
+  const bool live = u < (uint64_t)n_ranges * n_services;  // (wave-uniform; a dead wave still meets the barrier)
   U64x4 acc{{0, 0, 0, 0}};
   if (live) {
     const uint32_t r = u >= n_services ? 1u : 0u, s = (uint32_t)(u - (uint64_t)r * n_services);
@@ -457,7 +469,8 @@ struct SloRule {
 // Wave r serves covered window k = r / n_sel (window a + k of the ring
 // [win_mask + 1][n_services][256]; a + n_cov - 1 resident: the caller checked)
 // and selected service i = r % n_sel, so neighbouring waves read neighbouring
-// rows of one window.  Lane l holds bins 4l .. 4l + 3 -- the row is one
+// rows of one window (sel == nullptr: service i itself, n_sel <= n_services --
+// sa_window_latency_onset's every service).  Lane l holds bins 4l .. 4l + 3 -- the row is one
 // coalesced 2 KiB read -- and counts as slow those above thr_bin[i]; lane 0
 // writes pairs[i][k] = {total, slow}, pairs [n_sel][n_cov]: a service's
 // windows lie side by side for the scan.  The ring index stays below (win_mask
@@ -473,7 +486,7 @@ __global__ __launch_bounds__(kLatQueryBlock) void slo_pairs_kernel(const unsigne
   const uint64_t r = (uint64_t)blockIdx.x * (kLatQueryBlock / 64) + (threadIdx.x >> 6);
   if (r >= (uint64_t)n_cov * n_sel) return;  // (wave-uniform)
   const uint32_t k = (uint32_t)(r / n_sel), i = (uint32_t)(r % n_sel);
-  const U64x4 v = lat_row(ring + (((((a + k) & win_mask) * n_services) + sel[i]) << 8) + lane * 4);
+  const U64x4 v = lat_row(ring + (((((a + k) & win_mask) * n_services) + (sel ? sel[i] : i)) << 8) + lane * 4);
   const uint32_t tb = thr_bin[i];
   unsigned long long total = 0, slow = 0;
 #pragma unroll
@@ -550,6 +563,165 @@ __global__ __launch_bounds__(kSloSlideBlock) void slo_slide_kernel(const ulonglo
   if (lane == 0) alert[i] = alerts;
 }
 
+// ---- latency onset (sa_window_latency_onset): every service's threshold bin
+// -- given, or the pooled quantile's of its rows summed over the range -- its
+// (total, slow) pairs by slo_pairs_kernel, then -- after a group has added its
+// members' pairs -- per service the split of the range with the largest D, the
+// candidates' select and sort (the heavy hitters'), and the selected rows ----
+
+// One wave a row of sums [n_services][256] (the range's rows summed,
+// lat_pair_sums_kernel with one range): thr_bin[s] = lat_quantile_bin of ppm,
+// sa_window_latency's rule, 0 for a service without spans.  s < n_services.
+__global__ __launch_bounds__(kLatQueryBlock) void onset_thr_kernel(const unsigned long long *__restrict__ sums,
+                                                                   uint32_t n_services, uint32_t ppm,
+                                                                   uint8_t *__restrict__ thr_bin) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t s = blockIdx.x * (kLatQueryBlock / 64) + (threadIdx.x >> 6);
+  if (s >= n_services) return;  // (wave-uniform)
+  const uint32_t bin = lat_quantile_bin(lat_row_scan(lat_row(sums + ((uint64_t)s << 8) + lane * 4), lane), ppm);
+  if (lane == 0) thr_bin[s] = (uint8_t)bin;
+}
+
+struct OnsetParams {
+  unsigned long long min_count;  // >= 1
+  uint32_t min_delta;            // >= 1 (above 10^6: nothing matches)
+  uint32_t fall;
+};
+constexpr unsigned long long kOnsetCountTop = (1ULL << 44) - 1;  // a candidate's count, clamped for the order
+
+// One wave a service s of pairs [n_sel][n_cov] at a time, the waves of the grid
+// striding the services (lat_score_kernel's geometry).  First the range's sums
+// N and S, a lane every 64th window.  Then the prefix scan, 64 windows a step
+// with a carry as slo_slide_kernel's: lane l of step k0 holds N_b and S_b of
+// split t = k0 + l + 1 (before = windows 0 .. t - 1), a split while t <=
+// n_cov - 1; eligible with N_b and N_a = N - N_b both >= min_count; D = S_a N_b
+// - S_b N_a (negated when fall) as a signed 128-bit integer -- the products
+// reach 2^88 while N < 2^44.  A lane keeps the best of its own splits (>=: its
+// later split wins a tie), and after the steps a wave argmax takes (D, t), the
+// larger t among equal D: t differs from lane to lane, so every lane ends with
+// the same split.  t == 0: no eligible split.  Then delta_ppm = floor(S_a 10^6 /
+// N_a) - floor(S_b 10^6 / N_b) in u64 (negated when fall), a match when D > 0
+// and delta_ppm >= min_delta; it leaves as (score, s), score = (delta_ppm <<
+// 44) | min(N, 2^44 - 1) -- delta_ppm <= 10^6 < 2^20 -- ordered as the heavy
+// hitters' pairs.  rec[s] takes the split and its four sums (zeros without an
+// eligible split).  The matches gather in LDS and take one place range in cand
+// [n_sel], and one atomic each a workgroup goes to T->n_matched, T->n_resident
+// (the eligible), T->max_est and O->spans, as lat_score_kernel's.  The pairs
+// index stays below n_sel * n_cov (s < n_sel, k < n_cov), rec's below n_sel.
+__global__ __launch_bounds__(kLatScoreBlock) void onset_scan_kernel(const ulonglong2 *__restrict__ pairs,
+                                                                    uint32_t n_sel, uint32_t n_cov, OnsetParams M,
+                                                                    OnsetRow *__restrict__ rec,
+                                                                    ulonglong2 *__restrict__ cand, TopCtl *T,
+                                                                    OnsetOut *O) {
+  constexpr uint32_t kWaves = kLatScoreBlock / 64;
+  __shared__ ulonglong2 s_cand[kLatScoreList];
+  __shared__ unsigned long long s_largest[kWaves], s_spans[kWaves];
+  __shared__ uint32_t s_elig[kWaves], s_n;
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  if (threadIdx.x == 0) s_n = 0;
+  __syncthreads();
+  unsigned long long largest = 0, spans = 0;  // (the wave's own, the same in every lane)
+  uint32_t ne = 0;
+  for (uint32_t s = blockIdx.x * kWaves + wv; s < n_sel; s += gridDim.x * kWaves) {  // (wave-uniform)
+    const ulonglong2 *p = pairs + (uint64_t)s * n_cov;
+    unsigned long long N = 0, S = 0;
+    for (uint32_t k = lane; k < n_cov; k += 64) {
+      const ulonglong2 v = p[k];
+      N += v.x, S += v.y;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) N += __shfl_xor(N, o), S += __shfl_xor(S, o);
+    __int128 best_d = 0;
+    unsigned long long best_nb = 0, best_sb = 0, carry_n = 0, carry_s = 0;
+    uint32_t best_t = 0;
+    for (uint32_t k0 = 0; k0 + 1 < n_cov; k0 += 64) {  // (the same trips for every lane; the last window ends no split)
+      const uint32_t k = k0 + lane;
+      const ulonglong2 v = k < n_cov ? p[k] : ulonglong2{0, 0};
+      unsigned long long nb = v.x, sb = v.y;
+#pragma unroll
+      for (uint32_t d = 1; d < 64; d <<= 1) {
+        const unsigned long long un = __shfl_up(nb, d), us = __shfl_up(sb, d);
+        if (lane >= d) nb += un, sb += us;
+      }
+      nb += carry_n, sb += carry_s;
+      carry_n = __shfl(nb, 63), carry_s = __shfl(sb, 63);
+      const unsigned long long na = N - nb, sa = S - sb;
+      if (k + 1 < n_cov && nb >= M.min_count && na >= M.min_count) {
+        __int128 d = (__int128)sa * (__int128)nb - (__int128)sb * (__int128)na;
+        if (M.fall) d = -d;
+        if (best_t == 0 || d >= best_d) best_d = d, best_t = k + 1, best_nb = nb, best_sb = sb;
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const uint32_t ot = __shfl_xor(best_t, o);
+      const unsigned long long lo = __shfl_xor((unsigned long long)best_d, o);
+      const long long hi = __shfl_xor((long long)(best_d >> 64), o);
+      const unsigned long long onb = __shfl_xor(best_nb, o), osb = __shfl_xor(best_sb, o);
+      const __int128 od = (__int128)(((unsigned __int128)(unsigned long long)hi << 64) | lo);
+      if (ot && (best_t == 0 || od > best_d || (od == best_d && ot > best_t)))
+        best_d = od, best_t = ot, best_nb = onb, best_sb = osb;
+    }
+    spans += N;
+    const bool elig = best_t != 0;
+    ne += elig ? 1u : 0u;
+    const unsigned long long na = elig ? N - best_nb : 0, sa = elig ? S - best_sb : 0;
+    long long delta = 0;
+    if (elig) {  // (N_b, N_a >= min_count >= 1; S 10^6 < 2^64 while S < 2^44)
+      delta = (long long)(sa * 1000000ULL / na) - (long long)(best_sb * 1000000ULL / best_nb);
+      if (M.fall) delta = -delta;
+    }
+    if (lane == 0) rec[s] = OnsetRow{best_t, best_nb, best_sb, na, sa, 0};
+    if (elig && best_d > 0 && delta >= 1 && delta >= (long long)M.min_delta) {
+      const unsigned long long score = ((unsigned long long)delta << 44) | (N < kOnsetCountTop ? N : kOnsetCountTop);
+      largest = score > largest ? score : largest;
+      if (lane == 0) {
+        const uint32_t at = atomicAdd(&s_n, 1u);
+        if (at < kLatScoreList) s_cand[at] = ulonglong2{score, (unsigned long long)s};
+      }
+    }
+  }
+  if (lane == 0) s_largest[wv] = largest, s_spans[wv] = spans, s_elig[wv] = ne;
+  __syncthreads();
+  if (wv) return;
+  const uint32_t n = min(s_n, kLatScoreList);
+  if (n) {
+    unsigned long long pos = 0;
+    if (lane == 0) pos = atomicAdd(&T->n_matched, (unsigned long long)n);
+    pos = __shfl(pos, 0);
+    for (uint32_t i = lane; i < n; i += 64)
+      if (pos + i < n_sel) cand[pos + i] = s_cand[i];
+  }
+  const bool mine = lane < kWaves;
+  spans = mine ? s_spans[lane] : 0, largest = mine ? s_largest[lane] : 0, ne = mine ? s_elig[lane] : 0;
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) {  // (lanes 0..15 hold everything)
+    const unsigned long long os = __shfl_xor(spans, o), ol = __shfl_xor(largest, o);
+    spans += os;
+    largest = ol > largest ? ol : largest;
+    ne += __shfl_xor(ne, o);
+  }
+  if (lane == 0) {
+    if (ne) atomicAdd(&T->n_resident, (unsigned long long)ne);
+    if (largest) atomicMax(&T->max_est, largest);
+    if (spans) atomicAdd(&O->spans, spans);
+  }
+}
+
+// After the sort, one thread a row i < T->want of T->sel: the service's record
+// with its threshold bin (thr_bin == nullptr: 0) -- O->row[i].  i < kTopSel.
+__global__ __launch_bounds__(kLatQueryBlock) void onset_rows_kernel(const OnsetRow *__restrict__ rec,
+                                                                    const uint8_t *__restrict__ thr_bin,
+                                                                    uint32_t n_sel, const TopCtl *T, OnsetOut *O) {
+  const uint32_t i = blockIdx.x * kLatQueryBlock + threadIdx.x;
+  if (i >= T->want || i >= kTopSel) return;
+  const uint64_t s = T->sel[i].y;
+  if (s >= n_sel) return;  // (a candidate is a service id: never taken)
+  OnsetRow r = rec[s];
+  r.thr_bin = thr_bin ? thr_bin[s] : 0;
+  O->row[i] = r;
+}
+
 }  // namespace
 
 hipError_t prepare_lat_ingest(size_t lds_bytes) {
@@ -606,7 +778,7 @@ hipError_t launch_lat_pair_sums(const unsigned long long *ring, uint32_t n_servi
   if (stripes > 4)  // (the workgroups of a unit add to its row)
     if (hipError_t e = hipMemsetAsync(sums, 0, 2ull * n_services * SA_LAT_BINS * 8, s); e != hipSuccess) return e;
   hipLaunchKernelGGL(lat_pair_sums_kernel, dim3((uint32_t)((waves + per - 1) / per)), dim3(kLatPairBlock), 0, s, ring,
-                     n_services, n_windows - 1, first_b, len_b, first_c, len_c, stripes, std::min(stripes, 4u), sums);
+                     n_services, n_windows - 1, first_b, len_b, first_c, len_c, 2u, stripes, std::min(stripes, 4u), sums);
   return hipGetLastError();
 }
 
@@ -657,6 +829,45 @@ hipError_t launch_slo_slide(const unsigned long long *pairs, uint32_t n_sel, uin
   hipLaunchKernelGGL(slo_slide_kernel, dim3(n_sel), dim3(kSloSlideBlock), 0, s,
                      reinterpret_cast<const ulonglong2 *>(pairs), n_sel, n_out + R.max_width - 1, n_out, R,
                      reinterpret_cast<ulonglong2 *>(prefix), total, slow, burning, alert);
+  return hipGetLastError();
+}
+
+hipError_t launch_onset_thr(const unsigned long long *ring, uint32_t n_services, uint32_t n_windows, uint64_t first,
+                            uint32_t len, uint32_t q_ppm, unsigned long long *sums, uint8_t *thr_bin, hipStream_t s) {
+  if (ring) {  // the range's rows summed per service: the movers' kernel over one range
+    const uint32_t stripes = lat_pair_stripes(n_services, len);
+    const uint64_t waves = (uint64_t)n_services * stripes, per = kLatPairBlock / 64;
+    if (stripes > 4)  // (the workgroups of a unit add to its row)
+      if (hipError_t e = hipMemsetAsync(sums, 0, (size_t)n_services * SA_LAT_BINS * 8, s); e != hipSuccess) return e;
+    hipLaunchKernelGGL(lat_pair_sums_kernel, dim3((uint32_t)((waves + per - 1) / per)), dim3(kLatPairBlock), 0, s, ring,
+                       n_services, n_windows - 1, first, len, first, 0u, 1u, stripes, std::min(stripes, 4u), sums);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  }
+  if (!thr_bin) return hipSuccess;
+  const uint32_t per = kLatQueryBlock / 64;
+  hipLaunchKernelGGL(onset_thr_kernel, dim3((n_services + per - 1) / per), dim3(kLatQueryBlock), 0, s, sums, n_services,
+                     q_ppm, thr_bin);
+  return hipGetLastError();
+}
+
+hipError_t launch_onset(const unsigned long long *pairs, uint32_t n_sel, uint32_t n_cov, uint32_t k,
+                        unsigned long long min_count, uint32_t min_delta, uint32_t fall, const uint8_t *thr_bin,
+                        OnsetRow *rec, ulonglong2 *cand, TopCtl *T, OnsetOut *O, hipStream_t s) {
+  if (hipError_t e = hipMemsetAsync(T, 0, offsetof(TopCtl, sel), s); e != hipSuccess) return e;
+  if (hipError_t e = hipMemsetAsync(O, 0, offsetof(OnsetOut, row), s); e != hipSuccess) return e;
+  // lat_score_kernel's grid: a service a wave up to kLatScoreGrid workgroups, then several -- no more than a
+  // workgroup's list holds
+  const uint32_t per = kLatScoreBlock / 64;
+  const uint32_t grid = std::max(std::min((n_sel + per - 1) / per, kLatScoreGrid),
+                                 (n_sel + kLatScoreList - 1) / kLatScoreList);
+  hipLaunchKernelGGL(onset_scan_kernel, dim3(grid), dim3(kLatScoreBlock), 0, s,
+                     reinterpret_cast<const ulonglong2 *>(pairs), n_sel, n_cov, OnsetParams{min_count, min_delta, fall},
+                     rec, cand, T, O);
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  // (no row to sum: the scan took the range's spans)
+  if (hipError_t e = launch_top_select(pairs, 0, k, n_sel, cand, T, s); e != hipSuccess) return e;
+  hipLaunchKernelGGL(onset_rows_kernel, dim3((k + kLatQueryBlock - 1) / kLatQueryBlock), dim3(kLatQueryBlock), 0, s, rec,
+                     thr_bin, n_sel, T, O);
   return hipGetLastError();
 }
 

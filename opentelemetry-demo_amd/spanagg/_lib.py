@@ -175,6 +175,19 @@ class sa_slo_result(C.Structure):
     ]
 
 
+SA_ONSET_FALL = 1
+
+
+class sa_onset_result(C.Structure):
+    _fields_ = [
+        ("first_window", C.c_uint64), ("last_window", C.c_uint64), ("k", C.c_uint32), ("n", C.c_uint32),
+        ("flags", C.c_uint32), ("q_ppm", C.c_uint32), ("min_count", C.c_uint64),
+        ("n_services", C.c_uint64), ("n_eligible", C.c_uint64), ("n_matched", C.c_uint64), ("spans", C.c_uint64),
+        ("services", u32p), ("onset_window", u64p), ("delta_ppm", i32p), ("threshold_bin", u8p), ("effective_ns", u64p),
+        ("total_before", u64p), ("slow_before", u64p), ("total_after", u64p), ("slow_after", u64p),
+    ]
+
+
 class sa_stats(C.Structure):
     _fields_ = [
         ("spans", C.c_uint64), ("zero_key", C.c_uint64), ("invalid_service", C.c_uint64),
@@ -269,6 +282,14 @@ SIGNATURES = [
     ("sa_group_window_slo", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, u32p, u32p, C.c_uint32, u32p, C.c_uint32,
                                       u64p, C.c_uint64, C.c_uint32, C.POINTER(C.POINTER(sa_slo_result))]),
     ("sa_slo_result_free", None, [C.POINTER(sa_slo_result)]),
+    ("sa_window_latency_onset", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, u64p, C.c_uint64,
+                                          C.c_uint32, C.c_uint32, C.POINTER(C.POINTER(sa_onset_result))]),
+    ("sa_group_window_latency_onset", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, u64p,
+                                                C.c_uint64, C.c_uint32, C.c_uint32,
+                                                C.POINTER(C.POINTER(sa_onset_result))]),
+    ("sa_onset_result_free", None, [C.POINTER(sa_onset_result)]),
+    ("sa_onset_probe", C.c_int, [C.c_void_p, u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32,
+                                 C.c_uint32, C.POINTER(C.POINTER(sa_onset_result))]),
     ("sa_latency_bin", C.c_uint32, [C.c_uint64]),
     ("sa_latency_bin_bounds", C.c_int, [C.c_uint32, u64p, u64p]),
     ("sa_hll_estimate_hist", C.c_double, [u32p, C.c_uint32]),

@@ -322,6 +322,38 @@ class SloResult:
     alert_outputs: np.ndarray     # [n_sel] u32: outputs at which every width burns
 
 
+@dataclass
+class OnsetResult:
+    """sa_onset_result: the services whose share of slow spans changed most
+    inside first..last, each with the window at which "after" begins.  A span is
+    slow above its service's threshold bin -- the given threshold's, or the bin
+    of the pooled quantile q_ppm of the service's spans over the whole range."""
+    first: int
+    last: int
+    fall: bool
+    q_ppm: int                    # as given; 0 when thresholds were given
+    min_count: int                # as applied: max(min_count, 1)
+    services: np.ndarray          # [n] u32, by delta_ppm descending, spans descending, id ascending
+    onset_window: np.ndarray      # [n] u64: the first window of "after"
+    delta_ppm: np.ndarray         # [n] i32: the slow share after minus before in ppm (negated when fall), >= 1
+    threshold_bin: np.ndarray     # [n] u8
+    effective_ns: np.ndarray      # [n] u64: sketch.latency_bin_bounds(threshold_bin)[1]
+    total_before: np.ndarray      # [n] u64: spans of first .. onset_window - 1
+    slow_before: np.ndarray       # [n] u64
+    total_after: np.ndarray       # [n] u64: spans of onset_window .. last
+    slow_after: np.ndarray        # [n] u64
+    n_services: int               # the candidates: every service
+    n_eligible: int               # services with a split that leaves max(min_count, 1) spans on both sides
+    n_matched: int                # eligible services whose slow share changed by at least max(min_delta_ppm, 1)
+    spans: int                    # spans of every service over the range, exact
+
+    def items(self):
+        """[(service, onset_window, delta_ppm, total_before, slow_before, total_after, slow_after)]."""
+        return [tuple(int(v) for v in row) for row in zip(self.services, self.onset_window, self.delta_ppm,
+                                                          self.total_before, self.slow_before, self.total_after,
+                                                          self.slow_after)]
+
+
 def hll_estimate(regs: np.ndarray, p: int) -> float:
     lib = _lib.load()
     r = np.ascontiguousarray(regs, dtype=np.uint8)
@@ -546,6 +578,35 @@ def _window_slo(obj, fn, what, first, last, widths, limit_ppm, thresholds_ns, se
             col(r.total, n, W, S), col(r.slow, n, W, S), col(r.burning, n, S), col(r.alert_outputs, S))
     finally:
         obj.lib.sa_slo_result_free(out)
+
+
+def _onset_result(obj, out) -> OnsetResult:
+    """sa_onset_result -> OnsetResult (copies), freeing the library's result."""
+    try:
+        r = out.contents
+        n = int(r.n)
+        col = lambda p, dt: np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, dt)
+        return OnsetResult(
+            int(r.first_window), int(r.last_window), bool(r.flags & _lib.SA_ONSET_FALL), int(r.q_ppm), int(r.min_count),
+            col(r.services, np.uint32), col(r.onset_window, np.uint64), col(r.delta_ppm, np.int32),
+            col(r.threshold_bin, np.uint8), col(r.effective_ns, np.uint64), col(r.total_before, np.uint64),
+            col(r.slow_before, np.uint64), col(r.total_after, np.uint64), col(r.slow_after, np.uint64),
+            int(r.n_services), int(r.n_eligible), int(r.n_matched), int(r.spans))
+    finally:
+        obj.lib.sa_onset_result_free(out)
+
+
+def _window_latency_onset(obj, fn, what, first, last, k, quantile, thresholds_ns, min_count, min_delta_ppm,
+                          fall) -> OnsetResult:
+    """sa_window_latency_onset / sa_group_window_latency_onset -> OnsetResult."""
+    thr = None if thresholds_ns is None else np.ascontiguousarray(thresholds_ns, dtype=np.uint64).reshape(-1)
+    if thr is not None and len(thr) != obj.config.n_services:
+        raise ValueError(f"{what}: one threshold a service")
+    ppm = 0 if thr is not None else int(round(float(quantile) * 1e6))
+    out = C.POINTER(_lib.sa_onset_result)()
+    obj._check(fn(obj._h, int(first), int(last), int(k), ppm, None if thr is None else thr.ctypes.data_as(_lib.u64p),
+                  int(min_count), int(min_delta_ppm), _lib.SA_ONSET_FALL if fall else 0, C.byref(out)), what)
+    return _onset_result(obj, out)
 
 
 _QUANTILES = (0.5, 0.95, 0.99)
@@ -797,6 +858,33 @@ class Engine:
         return _window_slo(self, self.lib.sa_window_slo, "sa_window_slo", first, last, widths, limit_ppm, thresholds_ns,
                            services, min_count)
 
+    def window_latency_onset(self, first: int, last: int, k: int = 10, quantile: float = 0.95, thresholds_ns=None,
+                             min_count: int = 1, min_delta_ppm: int = 1, fall: bool = False) -> OnsetResult:
+        """sa_window_latency_onset (OPT_WINDOW_LATENCY engines): for every
+        service the window inside first..last at which its share of slow spans
+        changed -- the split with the largest S_after * N_before - S_before *
+        N_after among those with at least min_count spans on both sides, the
+        latest on ties -- and the k services whose share rose most (fall: fell),
+        by at least min_delta_ppm.  Slow: above the bin of the service's entry
+        of thresholds_ns (one a service), or with thresholds_ns None above the
+        bin of `quantile` of the service's spans over the whole range."""
+        return _window_latency_onset(self, self.lib.sa_window_latency_onset, "sa_window_latency_onset", first, last, k,
+                                     quantile, thresholds_ns, min_count, min_delta_ppm, fall)
+
+    def onset_probe(self, pairs, k: int = 10, min_count: int = 1, min_delta_ppm: int = 1, fall: bool = False) -> OnsetResult:
+        """Diagnostic (sa_onset_probe): window_latency_onset's scan and select
+        on `pairs` [n_sel][n_cov][2] u64 -- (total, slow) a service and window
+        -- instead of a ring's; windows count from 0, threshold_bin and
+        effective_ns come back 0."""
+        a = np.ascontiguousarray(pairs, dtype=np.uint64)
+        if a.ndim != 3 or a.shape[2] != 2:
+            raise ValueError("sa_onset_probe: pairs [n_sel][n_cov][2]")
+        out = C.POINTER(_lib.sa_onset_result)()
+        self._check(self.lib.sa_onset_probe(self._h, a.ctypes.data_as(_lib.u64p), a.shape[0], a.shape[1], int(k),
+                                            int(min_count), int(min_delta_ppm), _lib.SA_ONSET_FALL if fall else 0,
+                                            C.byref(out)), "sa_onset_probe")
+        return _onset_result(self, out)
+
     def flush_exp(self, allow_drops: bool = False) -> ExpoResult:
         out = C.POINTER(_lib.sa_exp_result)()
         rc = self.lib.sa_flush_exp(self._h, C.byref(out))
@@ -1013,6 +1101,13 @@ class Group:
         (total, slow) pairs."""
         return _window_slo(self, self.lib.sa_group_window_slo, "sa_group_window_slo", first, last, widths, limit_ppm,
                            thresholds_ns, services, min_count)
+
+    def window_latency_onset(self, first: int, last: int, k: int = 10, quantile: float = 0.95, thresholds_ns=None,
+                             min_count: int = 1, min_delta_ppm: int = 1, fall: bool = False) -> OnsetResult:
+        """sa_group_window_latency_onset: Engine.window_latency_onset over the
+        members' summed histograms (the pooled threshold) and summed pairs."""
+        return _window_latency_onset(self, self.lib.sa_group_window_latency_onset, "sa_group_window_latency_onset", first,
+                                     last, k, quantile, thresholds_ns, min_count, min_delta_ppm, fall)
 
     def window_advance(self, new_base: int):
         self._check(self.lib.sa_group_window_advance(self._h, int(new_base)), "sa_group_window_advance")

@@ -139,6 +139,32 @@ def slo_burning(total: int, slow: int, limit_ppm: int, min_count: int = 1) -> bo
     return total >= max(int(min_count), 1) and slow * 1_000_000 > int(limit_ppm) * total
 
 
+def latency_onset(pairs, min_count: int = 1, fall: bool = False):
+    """sa_window_latency_onset's rule on one service's (total, slow) pairs, a
+    window each: the split t in 1 .. len - 1 (before = windows 0 .. t - 1, after
+    = the rest) with at least max(min_count, 1) spans on both sides and the
+    largest D = S_after * N_before - S_before * N_after (negated when `fall`),
+    the latest among equal D.  None without such a split, else (t, D,
+    delta_ppm, N_before, S_before, N_after, S_after) with delta_ppm = S_after *
+    10^6 // N_after - S_before * 10^6 // N_before (negated when `fall`).  The
+    service matches when D > 0 and delta_ppm >= max(min_delta_ppm, 1)."""
+    pairs = [(int(t), int(s)) for t, s in pairs]
+    mc = max(int(min_count), 1)
+    n, s = sum(p[0] for p in pairs), sum(p[1] for p in pairs)
+    best, nb, sb = None, 0, 0
+    for t in range(1, len(pairs)):
+        nb, sb = nb + pairs[t - 1][0], sb + pairs[t - 1][1]
+        na, sa = n - nb, s - sb
+        if nb < mc or na < mc:
+            continue
+        d = sa * nb - sb * na
+        d = -d if fall else d
+        if best is None or d >= best[1]:
+            delta = sa * 1_000_000 // na - sb * 1_000_000 // nb
+            best = (t, d, -delta if fall else delta, nb, sb, na, sa)
+    return best
+
+
 def anomalous(series: Sequence[float], factor: float, min_base: float = 1.0) -> list:
     """Indices whose value exceeds `factor` x the series median (floor min_base)."""
     x = np.asarray(series, dtype=np.float64)
