@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdlib>
 #include <memory>
 #include <new>
@@ -20,9 +21,19 @@
 #include "sa_group_hooks.h"
 #include "sa_results.h"
 
-hipError_t copy_top(const sa::TopCtl *ctl, uint32_t k, unsigned long long head[4], ulonglong2 *rows, hipStream_t s) {
+// sa::TopCtl's head and its first k selected rows to the host, on `s`
+static hipError_t copy_top(const sa::TopCtl *ctl, uint32_t k, unsigned long long head[4], ulonglong2 *rows, hipStream_t s) {
   const hipError_t st = hipMemcpyAsync(head, ctl, 4 * sizeof head[0], hipMemcpyDeviceToHost, s);
   return st != hipSuccess ? st : hipMemcpyAsync(rows, ctl->sel, (size_t)k * 16, hipMemcpyDeviceToHost, s);
+}
+
+static_assert(offsetof(sa::MoversOut, est) == 16 && offsetof(sa::LatMovOut, row) == 16 && offsetof(sa::OnsetOut, row) == 16,
+              "a ranked block's head");
+hipError_t copy_ranked(hipError_t st, const sa::TopCtl *ctl, uint32_t k, unsigned long long head[4], ulonglong2 *sel,
+                       const void *d_out, size_t row_bytes, void *block, hipStream_t s) {
+  if (st == hipSuccess) st = copy_top(ctl, k, head, sel, s);
+  if (st == hipSuccess) st = hipMemcpyAsync(block, d_out, 16 + (size_t)k * row_bytes, hipMemcpyDeviceToHost, s);
+  return st;
 }
 
 namespace {
@@ -38,11 +49,8 @@ int range_buffers(sa_engine *e, uint64_t n_keys, bool regs, bool cells) {
     if (int rc = lazy(e, R.regs, e->hll_slot_bytes, "window range: register buffer hipMalloc failed")) return rc;
   if (cells)
     if (int rc = lazy(e, R.cells, e->cms_slot_elems, "window range: cell buffer hipMalloc failed")) return rc;
-  if (n_keys <= R.key_cap) return SA_OK;
-  uint64_t both = 2 * R.key_cap;  // (the keys and their answers: the two halves of one allocation)
-  const int rc = grow(e, R.keys, both, 2 * std::max<uint64_t>(n_keys, 1u << 10), "window range: key buffer hipMalloc failed");
-  R.key_cap = both / 2;
-  return rc;
+  if (2 * n_keys <= R.keys.cap) return SA_OK;  // (the keys and their answers: the two halves of one allocation)
+  return grow(e, R.keys, 2 * std::max<uint64_t>(n_keys, 1u << 10), "window range: key buffer hipMalloc failed");
 }
 
 // On `s`: fold_window for every window of first..last, with the windows'
@@ -81,7 +89,7 @@ int range_result(sa_engine *e, uint64_t first, uint64_t last, const uint32_t *d_
   h->shape(first, last, e->cfg, n_keys, flags);
   hipError_t st = hipSuccess;
   if (n_keys) {
-    uint64_t *dk = e->range.keys, *de = dk + e->range.key_cap;
+    uint64_t *dk = e->range.keys.p, *de = dk + e->range.keys.cap / 2;
     st = hipMemcpyAsync(dk, keys, n_keys * 8, hipMemcpyHostToDevice, s);
     if (st == hipSuccess)
       st = sa::launch_range_query(d_cells, e->cfg.cms_d, e->cfg.cms_w, 64 - sa::log2u(e->cfg.cms_w), e->d_seeds, dk,
@@ -93,9 +101,7 @@ int range_result(sa_engine *e, uint64_t first, uint64_t last, const uint32_t *d_
     st = hipMemcpyAsync(h->hll.data(), d_regs, h->hll.size(), hipMemcpyDeviceToHost, s);
   if (st == hipSuccess && (flags & SA_RANGE_CELLS))
     st = hipMemcpyAsync(h->cms.data(), d_cells, h->cms.size() * 8, hipMemcpyDeviceToHost, s);
-  const hipError_t waited = hipStreamSynchronize(s);  // (also after a failure: a copy into h may be in flight)
-  if (st != hipSuccess || waited != hipSuccess)
-    return fail(e, SA_EDEVICE, std::string("window range: ") + hipGetErrorString(st != hipSuccess ? st : waited));
+  if (int rc = wait_or_fail(e, st, s, "window range")) return rc;
   for (uint32_t sv = 0; sv < e->cfg.n_services; ++sv)
     h->distinct[sv] = sa_hll_estimate_hist(h->hist.data() + (size_t)sv * SA_HLL_HIST_BINS, e->cfg.hll_p);
   *out = &h.release()->r;
@@ -105,14 +111,14 @@ int range_result(sa_engine *e, uint64_t first, uint64_t last, const uint32_t *d_
 // ---- sliding series (sa_window_series) ----
 int series_buffers(sa_engine *e, uint64_t n_out, uint64_t n_keys) {
   sa_engine::Series &S = e->series;
-  if (int rc = grow(e, S.hist, S.hist_cap, n_out * e->cfg.n_services * SA_HLL_HIST_BINS,
+  if (int rc = grow(e, S.hist, n_out * e->cfg.n_services * SA_HLL_HIST_BINS,
                     "window series: histogram hipMalloc failed"))
     return rc;
   if (int rc = lazy(e, S.row0, e->cfg.n_windows, "window series: row sum hipMalloc failed")) return rc;
-  if (int rc = grow(e, S.keys, S.key_cap, n_keys ? std::max<uint64_t>(n_keys, 1u << 10) : 0,
+  if (int rc = grow(e, S.keys, n_keys ? std::max<uint64_t>(n_keys, 1u << 10) : 0,
                     "window series: key buffer hipMalloc failed"))
     return rc;
-  return grow(e, S.errors, S.err_cap, n_out * n_keys, "window series: answer buffer hipMalloc failed");
+  return grow(e, S.errors, n_out * n_keys, "window series: answer buffer hipMalloc failed");
 }
 
 // ---- heavy hitters (sa_window_top) ----
@@ -135,9 +141,7 @@ int top_on(sa_engine *e, const unsigned long long *d_cells, uint32_t k, uint64_t
                                  64 - sa::log2u(e->cfg.cms_w), e->d_seeds, k, std::max<uint64_t>(min_count, 1), T.cand,
                                  T.ctl, s);
   if (st == hipSuccess) st = copy_top(T.ctl, k, h->head, h->rows.data(), s);
-  if (st == hipSuccess) return SA_OK;
-  (void)hipStreamSynchronize(s);  // (a copy into h may be in flight)
-  return fail(e, SA_EDEVICE, std::string("window top: ") + hipGetErrorString(st));
+  return st == hipSuccess ? SA_OK : wait_or_fail(e, st, s, "window top");  // (a copy into h may be in flight)
 }
 
 // ---- movers (sa_window_movers) ----
@@ -162,12 +166,8 @@ int movers_on(sa_engine *e, const unsigned long long *d_base, const unsigned lon
   hipError_t st = sa::launch_movers(e->gkeys, e->cap, e->binned.kinv, d_base, d_cur, e->cfg.cms_d, e->cfg.cms_w,
                                     64 - sa::log2u(e->cfg.cms_w), e->d_seeds, nb, nc, flags & SA_MOVERS_FALL ? 1u : 0u, k,
                                     std::max<uint64_t>(min_score, 1), T.cand, T.ctl, O, s);
-  if (st == hipSuccess) st = copy_top(T.ctl, k, h->top.head, h->top.rows.data(), s);
-  // (MoversOut: the 16-byte head, then the rows)
-  if (st == hipSuccess) st = hipMemcpyAsync(h->out.data(), O, ((size_t)k + 1) * 16, hipMemcpyDeviceToHost, s);
-  if (st == hipSuccess) return SA_OK;
-  (void)hipStreamSynchronize(s);  // (a copy into h may be in flight)
-  return fail(e, SA_EDEVICE, std::string("window movers: ") + hipGetErrorString(st));
+  st = copy_ranked(st, T.ctl, k, h->top.head, h->top.rows.data(), O, sizeof O->est[0], h->out.data(), s);
+  return st == hipSuccess ? SA_OK : wait_or_fail(e, st, s, "window movers");  // (a copy into h may be in flight)
 }
 
 // ---- service overlap (sa_window_overlap) ----
@@ -215,9 +215,7 @@ int overlap_on(sa_engine *e, uint64_t first, uint64_t last, const uint8_t *regs,
   if (st == hipSuccess) st = hipMemcpyAsync(h->hist.data(), O.hist, h->hist.size() * 4, hipMemcpyDeviceToHost, s);
   if (st == hipSuccess && h->r.n_pairs)
     st = hipMemcpyAsync(h->pair_hist.data(), O.pair_hist, h->pair_hist.size() * 4, hipMemcpyDeviceToHost, s);
-  const hipError_t waited = hipStreamSynchronize(s);  // the call's one wait (also after a failure: copies may be in flight)
-  if (st != hipSuccess || waited != hipSuccess)
-    return fail(e, SA_EDEVICE, std::string("window overlap: ") + hipGetErrorString(st != hipSuccess ? st : waited));
+  if (int rc = wait_or_fail(e, st, s, "window overlap")) return rc;
   for (uint32_t i = 0; i < n; ++i)
     h->distinct[i] = sa_hll_estimate_hist(h->hist.data() + (size_t)i * SA_HLL_HIST_BINS, p);
   size_t pair = 0;
@@ -414,21 +412,19 @@ int sa_window_series(sa_engine *e, uint64_t first, uint64_t last, uint32_t width
   hipStream_t s = e->stream;
   // every covered window folded before any cell is read
   if (int rc = range_fold_on(e, a, last, s)) return rc;
-  SA_HIP(e, sa::launch_series_hll(e->hll, W, e->cfg.n_services, e->cfg.hll_p, a, width, n_out, S.hist, s));
+  SA_HIP(e, sa::launch_series_hll(e->hll, W, e->cfg.n_services, e->cfg.hll_p, a, width, n_out, S.hist.p, s));
   SA_HIP(e, sa::launch_series_row0(e->cms, e->cms_slot_elems, W, a, n_in, e->cfg.cms_w, S.row0, s));
   hipError_t st = hipSuccess;
   if (n_keys) {
-    st = hipMemcpyAsync(S.keys, keys, n_keys * 8, hipMemcpyHostToDevice, s);
+    st = hipMemcpyAsync(S.keys.p, keys, n_keys * 8, hipMemcpyHostToDevice, s);
     if (st == hipSuccess)
       st = sa::launch_series_query(e->cms, e->cms_slot_elems, W, a, width, n_out, e->cfg.cms_d, e->cfg.cms_w,
-                                   64 - sa::log2u(e->cfg.cms_w), e->d_seeds, S.keys, n_keys, S.errors, s);
-    if (st == hipSuccess) st = hipMemcpyAsync(h->errors.data(), S.errors, h->errors.size() * 8, hipMemcpyDeviceToHost, s);
+                                   64 - sa::log2u(e->cfg.cms_w), e->d_seeds, S.keys.p, n_keys, S.errors.p, s);
+    if (st == hipSuccess) st = hipMemcpyAsync(h->errors.data(), S.errors.p, h->errors.size() * 8, hipMemcpyDeviceToHost, s);
   }
-  if (st == hipSuccess) st = hipMemcpyAsync(h->hist.data(), S.hist, h->hist.size() * 4, hipMemcpyDeviceToHost, s);
+  if (st == hipSuccess) st = hipMemcpyAsync(h->hist.data(), S.hist.p, h->hist.size() * 4, hipMemcpyDeviceToHost, s);
   if (st == hipSuccess) st = hipMemcpyAsync(row0.data(), S.row0, (size_t)n_in * 8, hipMemcpyDeviceToHost, s);
-  const hipError_t waited = hipStreamSynchronize(s);  // (also after a failure: a copy into h may be in flight)
-  if (st != hipSuccess || waited != hipSuccess)
-    return fail(e, SA_EDEVICE, std::string("window series: ") + hipGetErrorString(st != hipSuccess ? st : waited));
+  if (int rc = wait_or_fail(e, st, s, "window series")) return rc;
   uint64_t run = 0;  // the sliding sum of the windows' row-0 sums
   for (uint32_t k = 0; k < n_in; ++k) {
     run += row0[k];

@@ -2,7 +2,8 @@
 // (spanagg_kernels.hip: the small-table path; spanagg_part.hip: the HBM-table
 // and round-1 partitioned paths; spanagg_table.hip: the flush-time table
 // kernels; spanagg_binned.hip, spanagg_dense.hip: the binned-table
-// high-cardinality path and its dense-index form).
+// high-cardinality path and its dense-index form; spanagg_range.hip,
+// spanagg_latency.hip: the ranked window queries' candidate frame).
 #pragma once
 #include "sa_internal.h"
 
@@ -555,6 +556,133 @@ __device__ __forceinline__ unsigned long long wave_ticket(unsigned long long *co
   base = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(base >> 32), leader) << 32) |
          (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)base, leader);
   return base + lane_rank(m);
+}
+
+// ---- the candidate frame of the ranked window queries: a scan leaves (score,
+// id) candidates in cand and tallies into TopCtl (the select: spanagg_range.hip) ----
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long other = __shfl_xor(v, o, 64);
+    v = other > v ? other : v;
+  }
+  return v;
+}
+
+// A key-table scan (sa_window_top, sa_window_movers), kBlock threads a
+// workgroup: walks gkeys[0..cap) once.  A slot's key is recovered as
+// fold_errcnt_slots does (stored id * kinv; a dense engine's bound hash, 0 when
+// unbound); score_of(key, score): whether it matches, and its score (>= 1).
+// The matches leave as (score, key) into cand [cap] through one returning
+// atomic per wave (compact_kernel's idiom); T counts the resident keys, the
+// matches and the largest score.
+template <uint32_t kBlock, class Score>
+__device__ __forceinline__ void table_scan(const unsigned long long *gkeys, uint64_t cap, uint64_t kinv, ulonglong2 *cand,
+                                           TopCtl *T, Score score_of) {
+  uint32_t resident = 0;
+  unsigned long long largest = 0;
+  for (uint64_t s = blockIdx.x * (uint64_t)kBlock + threadIdx.x; s < cap; s += (uint64_t)gridDim.x * kBlock) {
+    const uint64_t key = gkeys[s] * kinv;
+    if (!key) continue;
+    ++resident;
+    unsigned long long score;
+    if (!score_of(key, score)) continue;
+    largest = score > largest ? score : largest;
+    const unsigned long long pos = wave_ticket(&T->n_matched, __ballot(true));
+    if (pos < cap) cand[pos] = ulonglong2{score, key};  // (a table holds a key once: at most cap matches)
+  }
+  resident = wave_sum(resident);
+  largest = wave_max_u64(largest);
+  if ((threadIdx.x & 63u) == 0) {
+    if (resident) atomicAdd(&T->n_resident, (unsigned long long)resident);
+    if (largest) atomicMax(&T->max_est, largest);
+  }
+}
+
+// A service-ranking scan (sa_window_latency_movers, sa_window_latency_onset):
+// sixteen waves a workgroup, a service each at a time.  A wave has one
+// candidate at a time, so the workgroup gathers its matches in LDS -- at most
+// kLatScoreList: the launcher's grid leaves a wave no more than kLatScoreIters
+// services -- and publish() takes one place range in cand for all of them and
+// one atomic each for the counters: 65,536 services are 512 workgroups'
+// atomics on those words, not 4,096's.
+constexpr uint32_t kLatScoreBlock = 1024;  // sixteen waves: one set of atomics a workgroup
+constexpr uint32_t kLatScoreIters = 8;     // services a wave, at most
+constexpr uint32_t kLatScoreList = kLatScoreBlock / 64 * kLatScoreIters;  // a workgroup's matches in LDS
+template <uint32_t kSpans>  // the span sums the scan takes beside the counters (1 or 2)
+struct RankList {
+  static constexpr uint32_t kWaves = kLatScoreBlock / 64;
+  static_assert(kWaves <= 16, "publish reduces over lanes 0..15");
+  ulonglong2 list[kLatScoreList];
+  unsigned long long largest[kWaves], spans[kSpans][kWaves];
+  uint32_t elig[kWaves], n;
+
+  __device__ __forceinline__ void init() {
+    if (threadIdx.x == 0) n = 0;
+    __syncthreads();
+  }
+  // lane 0 of a wave: one match
+  __device__ __forceinline__ void push(unsigned long long score, unsigned long long id) {
+    const uint32_t at = atomicAdd(&n, 1u);
+    if (at < kLatScoreList) list[at] = ulonglong2{score, id};
+  }
+  // Every thread, after its wave's last push, with the wave's own tallies (the
+  // same in every lane): the list into cand [n_ids] behind T->n_matched, then
+  // one add or max each into T->n_resident (the eligible), T->max_est and *span_out[i].
+  __device__ __forceinline__ void publish(unsigned long long wave_largest, uint32_t wave_elig,
+                                          const unsigned long long (&wave_spans)[kSpans], uint32_t n_ids,
+                                          ulonglong2 *cand, TopCtl *T, unsigned long long *const (&span_out)[kSpans]) {
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    if (lane == 0) {
+      largest[wv] = wave_largest, elig[wv] = wave_elig;
+      for (uint32_t i = 0; i < kSpans; ++i) spans[i][wv] = wave_spans[i];
+    }
+    __syncthreads();
+    if (wv) return;
+    const uint32_t m = min(n, kLatScoreList);
+    if (m) {
+      unsigned long long pos = 0;
+      if (lane == 0) pos = atomicAdd(&T->n_matched, (unsigned long long)m);
+      pos = __shfl(pos, 0);
+      for (uint32_t i = lane; i < m; i += 64)
+        if (pos + i < n_ids) cand[pos + i] = list[i];
+    }
+    const bool mine = lane < kWaves;
+    unsigned long long sp[kSpans], lg = mine ? largest[lane] : 0;
+    uint32_t ne = mine ? elig[lane] : 0;
+    for (uint32_t i = 0; i < kSpans; ++i) sp[i] = mine ? spans[i][lane] : 0;
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) {  // (lanes 0..15 hold everything)
+      for (uint32_t i = 0; i < kSpans; ++i) sp[i] += __shfl_xor(sp[i], o);
+      const unsigned long long ol = __shfl_xor(lg, o);
+      lg = ol > lg ? ol : lg;
+      ne += __shfl_xor(ne, o);
+    }
+    if (lane == 0) {
+      if (ne) atomicAdd(&T->n_resident, (unsigned long long)ne);
+      if (lg) atomicMax(&T->max_est, lg);
+      for (uint32_t i = 0; i < kSpans; ++i)
+        if (sp[i]) atomicAdd(span_out[i], sp[i]);
+    }
+  }
+};
+
+// One step of a wave's running sums over (x, y) pairs, 64 a step: lane l takes
+// p[k] (zeros from n on), k = the step's first + l, and gets p[0..k] summed --
+// the wave's inclusive scan plus `carry`, the sum of the steps before, which
+// then takes this step's too.  Every lane of the wave calls it.
+__device__ __forceinline__ ulonglong2 pair_scan_step(const ulonglong2 *p, uint32_t k, uint32_t n, uint32_t lane,
+                                                     ulonglong2 &carry) {
+  const ulonglong2 v = k < n ? p[k] : ulonglong2{0, 0};
+  unsigned long long x = v.x, y = v.y;
+#pragma unroll
+  for (uint32_t d = 1; d < 64; d <<= 1) {
+    const unsigned long long ux = __shfl_up(x, d), uy = __shfl_up(y, d);
+    if (lane >= d) x += ux, y += uy;
+  }
+  x += carry.x, y += carry.y;
+  carry = ulonglong2{__shfl(x, 63), __shfl(y, 63)};
+  return ulonglong2{x, y};
 }
 
 __device__ __forceinline__ void cold_cms_add(uint32_t ws, uint64_t key) {

@@ -71,6 +71,13 @@ struct Resources {
   }
 };
 
+// A query's growing device buffer: p holds cap elements (grow, below).
+template <class T>
+struct DevBuf {
+  T *p = nullptr;
+  uint64_t cap = 0;
+};
+
 struct sa_engine {
   sa_config cfg{};
   sa::Hist hist;  // cfg.bounds points into it
@@ -195,24 +202,22 @@ struct sa_engine {
   size_t hll_slot_bytes = 0, cms_slot_elems = 0;
   // sa_window_range (allocated by its first call): the histogram
   // [n_services][SA_HLL_HIST_BINS], the merged registers (SA_RANGE_REGISTERS
-  // only), the summed cells, and the keys with their answers [2][key_cap];
-  // cells_base: a second [d][w], the baseline range's sum (sa_window_movers only)
+  // only), the summed cells, and the keys with their answers (the two halves of
+  // keys); cells_base: a second [d][w], the baseline range's sum (sa_window_movers only)
   struct Range {
     uint32_t *hist = nullptr;
     uint8_t *regs = nullptr;
     unsigned long long *cells = nullptr, *cells_base = nullptr;
-    uint64_t *keys = nullptr;
-    uint64_t key_cap = 0;
+    DevBuf<uint64_t> keys;
   } range;
   // sa_window_series (grown by the calls that need more): every output's
   // histogram [n_out][n_services][SA_HLL_HIST_BINS], the windows' row-0 sums
   // [n_windows], the keys and their answers [n_out][n_keys]
   struct Series {
-    uint32_t *hist = nullptr;
-    uint64_t hist_cap = 0;
-    unsigned long long *row0 = nullptr, *errors = nullptr;
-    uint64_t *keys = nullptr;
-    uint64_t key_cap = 0, err_cap = 0;
+    DevBuf<uint32_t> hist;
+    unsigned long long *row0 = nullptr;
+    DevBuf<unsigned long long> errors;
+    DevBuf<uint64_t> keys;
   } series;
   // sa_window_top (allocated by its first call): the matches as (estimate,
   // key) pairs [cap] -- 16 bytes a table slot -- and the counters, the
@@ -237,46 +242,35 @@ struct sa_engine {
   } overlap;
   // SA_OPT_WINDOW_LATENCY (spanagg_latency.hip; nullptr without the option):
   // ring [n_windows][n_services][SA_LAT_BINS] u64, the ring slots the ingest
-  // kernel holds in LDS (0: the HBM form) and its largest grid; and sa_window_latency's
-  // scratch, grown by the calls that need more: the selection [sel_cap], one
-  // tile of sliding sums [sums_cap rows][SA_LAT_BINS], every row's count
-  // [row_cap] and quantile bins [row_cap][SA_LAT_MAX_Q].
-  // sa_window_latency_movers (allocated by its first call): both ranges' sums
-  // mov_sums [2][n_services][SA_LAT_BINS], their counts mov_counts [2]
-  // [n_services], the candidates mov_cand [n_services] -- its own: sa_window_top's
-  // buffer holds a table's slots, which can be fewer -- and the rows' counts
-  // and bins mov_out; the select works in sa_window_top's control block
-  // (calls are serialised)
+  // kernel holds in LDS (0: the HBM form) and its largest grid; and the scratch
+  // of the four queries over it, one buffer a role, grown (DevBuf) or allocated
+  // (lazy) by the calls that need it.  The queries share them because calls on
+  // an engine are serialised, and a group query runs export -> reduce -> finish
+  // on one engine without another query between: what a stage leaves (the
+  // onset's thr from its pairs stage to its finish) is still there, and a
+  // finish asks for no more than its export did, so nothing it needs is regrown.
+  // The select works in sa_window_top's control block.
   struct Latency {
     unsigned long long *ring = nullptr;
     uint32_t k_slots = 0, grid_max = 0;
-    uint32_t *sel = nullptr;
-    unsigned long long *sums = nullptr, *count = nullptr;
-    uint8_t *q_bin = nullptr;
-    uint64_t sel_cap = 0, sums_cap = 0, row_cap = 0, qbin_cap = 0;
-    unsigned long long *mov_sums = nullptr, *mov_counts = nullptr;
-    ulonglong2 *mov_cand = nullptr;
-    sa::LatMovOut *mov_out = nullptr;
-    // sa_window_slo, grown like sums: the selection's threshold bins
-    // [slo_thr_cap], the engine's own pairs [slo_pairs_cap] u64 ([n_sel]
-    // [n_cov][2]), their prefix sums [slo_prefix_cap] u64 ([n_sel][n_cov + 1]
-    // [2]) and the answers [slo_out_cap] u64: total, slow, alert, burning
-    uint8_t *slo_thr = nullptr;
-    unsigned long long *slo_pairs = nullptr, *slo_prefix = nullptr, *slo_out = nullptr;
-    uint64_t slo_thr_cap = 0, slo_pairs_cap = 0, slo_prefix_cap = 0, slo_out_cap = 0;
-    // sa_window_latency_onset and sa_onset_probe, grown like sums by the first
-    // call (the probe's services need not be the engine's): every service's
-    // threshold bin [onset_thr_cap], the engine's own pooled sums
-    // [onset_sums_cap] u64 ([n_services][SA_LAT_BINS]) and pairs
-    // [onset_pairs_cap] u64 ([n_services][n_cov][2]), every service's best
-    // split [onset_rec_cap] and the candidates [onset_cand_cap]; the selected
-    // rows onset_out; the select works in sa_window_top's control block
-    uint8_t *onset_thr = nullptr;
-    unsigned long long *onset_sums = nullptr, *onset_pairs = nullptr;
-    sa::OnsetRow *onset_rec = nullptr;
-    ulonglong2 *onset_cand = nullptr;
-    sa::OnsetOut *onset_out = nullptr;
-    uint64_t onset_thr_cap = 0, onset_sums_cap = 0, onset_pairs_cap = 0, onset_rec_cap = 0, onset_cand_cap = 0;
+    DevBuf<uint32_t> sel;  // a selection's service ids (latency, SLO)
+    DevBuf<uint8_t> thr;   // threshold bins, one an id (SLO: the selection's; onset: every service's)
+    DevBuf<unsigned long long> pairs;    // the engine's own (total, slow) pairs [ids][n_cov][2] (SLO, onset, the probe)
+    DevBuf<unsigned long long> prefix;   // the SLO's prefix sums [n_sel][n_cov + 1][2]
+    DevBuf<unsigned long long> slo_out;  // the SLO's answers: total, slow, alert, burning
+    unsigned long long *range_sums = nullptr;  // the engine's own [2][n_services][SA_LAT_BINS] (movers; onset: the first)
+    unsigned long long *counts = nullptr;      // the movers' [2][n_services]
+    // the ranking scans' candidates and the onset's best splits, one an id (the probe's ids need not be the
+    // engine's) -- cand its own: sa_window_top's holds a table's slots, which can be fewer
+    DevBuf<ulonglong2> cand;
+    DevBuf<sa::OnsetRow> rec;
+    union Ranked {  // the ranked rows: a 16-byte head, then kTopSel rows
+      sa::LatMovOut mov;
+      sa::OnsetOut onset;
+    } *ranked = nullptr;
+    // sa_window_latency's own: one tile of sliding sums [rows][SA_LAT_BINS], every row's count and quantile bins
+    DevBuf<unsigned long long> sums, count;
+    DevBuf<uint8_t> q_bin;
   } lat;
   // sa_ingest: two pinned host slots and their HBM copies; a slot is refilled
   // once its event (H2D copy + aggregation of the previous use) has passed
@@ -346,6 +340,17 @@ int grow(sa_engine *e, T *&p, uint64_t &cap, uint64_t want, const char *what) {
   cap = want;
   return SA_OK;
 }
+template <class T>
+int grow(sa_engine *e, DevBuf<T> &b, uint64_t want, const char *what) {
+  return grow(e, b.p, b.cap, want, what);
+}
+// The call's one wait on `s` -- also after a failure st of what was queued:
+// copies may be in flight -- and SA_EDEVICE "<query>: <error>" when either failed.
+inline int wait_or_fail(sa_engine *e, hipError_t st, hipStream_t s, const char *query) {
+  const hipError_t waited = hipStreamSynchronize(s);
+  if (st == hipSuccess && waited == hipSuccess) return SA_OK;
+  return fail(e, SA_EDEVICE, std::string(query) + ": " + hipGetErrorString(st != hipSuccess ? st : waited));
+}
 
 // An argument rule's verdict (sa_query_args.h) as the call's: "<query>: <what is wrong>"
 inline int bad_args(sa_engine *e, int code, const char *query, const char *bad) {
@@ -382,7 +387,10 @@ int hop_back(sa_engine *e, hipStream_t s);
 int fold_errslab(sa_engine *e, uint64_t ws, hipStream_t s);
 
 // engine_window.cpp
-// sa::TopCtl's head and its first k selected rows to the host, on `s`
-hipError_t copy_top(const sa::TopCtl *ctl, uint32_t k, unsigned long long head[4], ulonglong2 *rows, hipStream_t s);
+// After a ranked launch (st: what it returned) on `s`, not waited for: sa::TopCtl's
+// head and its first k selected pairs, and the out block's 16-byte head with
+// its first k rows of row_bytes each (sa::MoversOut, LatMovOut, OnsetOut) into `block`.
+hipError_t copy_ranked(hipError_t st, const sa::TopCtl *ctl, uint32_t k, unsigned long long head[4], ulonglong2 *sel,
+                       const void *d_out, size_t row_bytes, void *block, hipStream_t s);
 
 #pragma GCC visibility pop

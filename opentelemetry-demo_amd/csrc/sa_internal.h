@@ -487,8 +487,10 @@ hipError_t launch_top(const unsigned long long *gkeys, uint64_t cap, uint64_t ki
 // cand and T->n_matched, T->max_est (the largest x) and T->n_resident in a T
 // whose first offsetof(TopCtl, sel) bytes were zeroed before it, T->sel[0 ..
 // min(k, T->n_matched)) = the first k by (x descending, y ascending) and
-// T->error_spans = the sum of cells[0 .. w).  A key of 0 orders like any other.
-hipError_t launch_top_select(const unsigned long long *cells, uint32_t w, uint32_t k, uint64_t cap,
+// T->error_spans = the sum of row0[0 .. w).  row0 == nullptr with w == 0: no
+// row to sum, T->error_spans stays 0 (the service-ranking scans, which take
+// their spans themselves).  A key of 0 orders like any other.
+hipError_t launch_top_select(const unsigned long long *row0, uint32_t w, uint32_t k, uint64_t cap,
                              const ulonglong2 *cand, TopCtl *T, hipStream_t s);
 // movers between two ranges' summed cells (sa_window_movers; DESIGN.md section
 // 4, "Movers between two ranges").  kMoversCellsLds: the scan stages both
@@ -562,16 +564,12 @@ struct LatMovOut {
   unsigned long long spans_base, spans_cur;
   LatMovRow row[kTopSel];
 };
-// The stripes a (range, service) unit's windows are split into for the longer
-// range `len` (1, 2 or a multiple of 4): a power of two, no more than fill
-// about 4,096 waves over the 2 * n_services units, none finer than 8 windows.
-uint32_t lat_pair_stripes(uint32_t n_services, uint32_t len);
-// sums [2][n_services][SA_LAT_BINS]: every service's rows summed over windows
-// first_b .. first_b + len_b - 1 (sums[0]) and first_c .. first_c + len_c - 1
-// (sums[1]), 1 <= len <= n_windows
-hipError_t launch_lat_pair_sums(const unsigned long long *ring, uint32_t n_services, uint32_t n_windows,
-                                uint64_t first_b, uint32_t len_b, uint64_t first_c, uint32_t len_c,
-                                unsigned long long *sums, hipStream_t s);
+// Range sums over n_ranges in {1, 2}: sums [n_ranges][n_services][SA_LAT_BINS]
+// = every service's rows summed over windows range[2r] .. range[2r + 1] (host;
+// first and last, at most n_windows of them) -- the movers' baseline and
+// current range, or the onset's one range for its pooled threshold.
+hipError_t launch_lat_range_sums(const unsigned long long *ring, uint32_t n_services, uint32_t n_windows,
+                                 const uint64_t *range, uint32_t n_ranges, unsigned long long *sums, hipStream_t s);
 // The rest of the query on `s`, from sums [2][n_services][SA_LAT_BINS]: every
 // service scored by q_ppm[0] (min_count >= 1, min_shift >= 1, fall 0 or 1)
 // into counts [2][n_services] and cand [n_services], the select and the sort
@@ -610,13 +608,11 @@ struct OnsetOut {
   unsigned long long spans, pad;
   OnsetRow row[kTopSel];
 };
-// The pooled threshold's two steps on `s`, either left out by a null pointer:
-// ring != nullptr: sums [n_services][SA_LAT_BINS] = every service's rows summed
-// over windows first .. first + len - 1 (1 <= len <= n_windows); thr_bin !=
-// nullptr: thr_bin [n_services] = the bin of quantile q_ppm of each row of sums
-// (sa_window_latency's rule).  A group adds its members' sums between the two.
-hipError_t launch_onset_thr(const unsigned long long *ring, uint32_t n_services, uint32_t n_windows, uint64_t first,
-                            uint32_t len, uint32_t q_ppm, unsigned long long *sums, uint8_t *thr_bin, hipStream_t s);
+// The pooled threshold's bins: thr_bin [n_services] = the bin of quantile q_ppm
+// of each row of sums [n_services][SA_LAT_BINS] (launch_lat_range_sums over one
+// range, a group's members' added up; sa_window_latency's rule).
+hipError_t launch_onset_thr(const unsigned long long *sums, uint32_t n_services, uint32_t q_ppm, uint8_t *thr_bin,
+                            hipStream_t s);
 // The rest of the query on `s`, from pairs [n_sel][n_cov][2] (launch_slo_pairs
 // over every service): every service's best split into rec [n_sel] and its
 // candidate into cand [n_sel] (min_count >= 1, min_delta >= 1, fall 0 or 1),

@@ -15,9 +15,10 @@
 //                      subtracted, one wave a (service, chunk of outputs).
 //   lat_scan_kernel    a summed row's count and quantile bins: lane-local
 //                      prefix, wave scan, ballot.
-//   lat_pair_sums_kernel, lat_score_kernel, lat_mov_rows_kernel
+//   lat_range_sums_kernel, lat_score_kernel, lat_mov_rows_kernel
 //                      sa_window_latency_movers: two ranges' rows summed per
-//                      service (a long range split over waves), every service
+//                      service (one range for the onset's pooled threshold; a
+//                      long range split over waves), every service
 //                      scored by the shift of its ranking quantile's bin --
 //                      the select and the sort are the heavy hitters' -- and
 //                      the selected services' counts and bins.
@@ -29,7 +30,7 @@
 //                      the difference of two prefixes, and the burn rule.
 //   onset_thr_kernel, onset_scan_kernel, onset_rows_kernel
 //                      sa_window_latency_onset: every service's pooled quantile
-//                      bin from its rows summed over the range (the movers'
+//                      bin from its rows summed over the range (the range
 //                      sums kernel, one range), its (total, slow) pairs (the
 //                      SLO's pairs kernel), then per service the split of the
 //                      range with the largest D = S_a N_b - S_b N_a in 128
@@ -37,7 +38,12 @@
 //                      select and the sort are the heavy hitters' -- and the
 //                      selected services' records.
 //
-
+// The two service-ranking scans (lat_score_kernel, onset_scan_kernel) share
+// sa_device.h's candidate frame -- a workgroup's matches in LDS, one place
+// range in cand and one set of atomics a workgroup (RankList) -- and one grid
+// rule; the SLO's and the onset's prefix over (total, slow) pairs is one
+// pair_scan_step; every wave read of a summed row is lat_sum_row.
+//
 // The two query stages are apart because a group adds its members' sums
 // between them.  Every cell is an integer sum, so the order of the atomics
 // does not show: two calls, and one engine against a group, give the same bits.
@@ -254,6 +260,10 @@ __device__ __forceinline__ uint32_t lat_quantile_bin(const LatRowScan &R, uint32
   }
   return bin;
 }
+// The wave's view of row `row` of sums [..][256]
+__device__ __forceinline__ LatRowScan lat_sum_row(const unsigned long long *sums, uint64_t row, uint32_t lane) {
+  return lat_row_scan(lat_row(sums + (row << 8) + lane * 4), lane);
+}
 
 // One wave a row of sums [n_rows][256]: count[row] = the row's total, q_bin[row]
 // [i] = lat_quantile_bin of ppm[i].
@@ -264,7 +274,7 @@ __global__ __launch_bounds__(kLatQueryBlock) void lat_scan_kernel(const unsigned
   const uint32_t lane = threadIdx.x & 63u;
   const uint64_t r = (uint64_t)blockIdx.x * (kLatQueryBlock / 64) + (threadIdx.x >> 6);
   if (r >= n_rows) return;  // (wave-uniform)
-  const LatRowScan R = lat_row_scan(lat_row(sums + (r << 8) + lane * 4), lane);
+  const LatRowScan R = lat_sum_row(sums, r, lane);
   if (lane == 0) count[r] = R.total;
   for (uint32_t i = 0; i < Q.n; ++i) {
     const uint32_t bin = lat_quantile_bin(R, Q.ppm[i]);
@@ -276,16 +286,16 @@ __global__ __launch_bounds__(kLatQueryBlock) void lat_scan_kernel(const unsigned
 // service, every service scored by the shift of its ranking quantile's bin,
 // the select and the sort the heavy hitters' (spanagg_range.hip), then the
 // selected services' rows ----
-constexpr uint32_t kLatPairBlock = 256;    // four waves: stripes of one unit, or one-stripe units
-constexpr uint32_t kLatPairWaves = 4096;   // the sums split units into stripes up to about this many waves
-constexpr uint32_t kLatStripeRows = 8;     // ... and no finer than this many windows a stripe
-constexpr uint32_t kLatScoreBlock = 1024;  // sixteen waves, a service each at a time: one set of atomics a workgroup
-constexpr uint32_t kLatScoreGrid = 512;    // the score stage's workgroups, while a wave then has no more than ...
-constexpr uint32_t kLatScoreIters = 8;     // ... this many services (65,536 services: exactly both)
-constexpr uint32_t kLatScoreList = kLatScoreBlock / 64 * kLatScoreIters;  // a workgroup's matches in LDS
+constexpr uint32_t kLatPairBlock = 256;   // four waves: stripes of one unit, or one-stripe units
+constexpr uint32_t kLatPairWaves = 4096;  // the sums split units into stripes up to about this many waves
+constexpr uint32_t kLatStripeRows = 8;    // ... and no finer than this many windows a stripe
+// the service-ranking scans' workgroups (RankList, sa_device.h), while a wave
+// then has no more than kLatScoreIters services (65,536 services: exactly both)
+constexpr uint32_t kLatScoreGrid = 512;
 
-// Unit u = r * n_services + s is service s over range r < n_ranges (0 the
-// baseline, 1 the current one; sa_window_latency_onset sums one range):
+// Range sums over n_ranges in {1, 2}.  Unit u = r * n_services + s is service
+// s over range r < n_ranges (sa_window_latency_movers: 0 the baseline, 1 the
+// current one; sa_window_latency_onset sums one range, first_c and len_c unread):
 // windows first[r] .. first[r] + len[r] - 1.  A unit is `stripes`
 // waves (1, 2 or a multiple of 4, so the waves of a workgroup that share a
 // unit are `grp` = min(stripes, 4) neighbours); stripe t sums the t-th run of
@@ -298,7 +308,7 @@ constexpr uint32_t kLatScoreList = kLatScoreBlock / 64 * kLatScoreIters;  // a w
 // launcher) -- integer adds, so neither the split nor the order shows.  The
 // ring index stays below (win_mask + 1) * n_services * 256: s < n_services, and
 // k < len[r] <= win_mask + 1.
-__global__ __launch_bounds__(kLatPairBlock) void lat_pair_sums_kernel(const unsigned long long *__restrict__ ring,
+__global__ __launch_bounds__(kLatPairBlock) void lat_range_sums_kernel(const unsigned long long *__restrict__ ring,
                                                                       uint32_t n_services, uint32_t win_mask,
                                                                       uint64_t first_b, uint32_t len_b, uint64_t first_c,
                                                                       uint32_t len_c, uint32_t n_ranges,
@@ -364,32 +374,24 @@ struct LatMovParams {
 // >= min_shift.  A match leaves as (score, s), score = (shift << 48) |
 // min(count_cur, 2^48 - 1): ordered as the heavy hitters' pairs -- score
 // descending, then id ascending -- that is (shift, count_cur) descending, then
-// id ascending.  A wave has one candidate at a time, so a workgroup gathers
-// its matches in LDS (at most kLatScoreList: the launcher's grid leaves a wave
-// no more than kLatScoreIters services) and takes one place range in cand
-// [n_services] for all of them (T->n_matched), and one add or max each for
-// T->n_resident (the eligible), T->max_est (the largest score) and
-// O->spans_base and O->spans_cur (the sums of the two counts): 65,536
-// services are 512 workgroups' atomics on those words, not 4,096's.
+// id ascending.  The matches and the tallies go through RankList (sa_device.h):
+// cand [n_services], T->n_resident the eligible, and O->spans_base and
+// O->spans_cur the sums of the two counts.
 __global__ __launch_bounds__(kLatScoreBlock) void lat_score_kernel(const unsigned long long *__restrict__ sums,
                                                                    uint32_t n_services, LatMovParams M,
                                                                    unsigned long long *__restrict__ counts,
                                                                    ulonglong2 *__restrict__ cand, TopCtl *T,
                                                                    LatMovOut *O) {
-  constexpr uint32_t kWaves = kLatScoreBlock / 64;
-  __shared__ ulonglong2 s_cand[kLatScoreList];
-  __shared__ unsigned long long s_largest[kWaves], s_base[kWaves], s_cur[kWaves];
-  __shared__ uint32_t s_elig[kWaves], s_n;
+  __shared__ RankList<2> list;
+  constexpr uint32_t kWaves = RankList<2>::kWaves;
   const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-  if (threadIdx.x == 0) s_n = 0;
-  __syncthreads();
-  unsigned long long largest = 0, base = 0, cur = 0;  // (the wave's own, the same in every lane)
+  list.init();
+  unsigned long long largest = 0, spans[2] = {0, 0};  // (the wave's own, the same in every lane: base, cur)
   uint32_t ne = 0;
   for (uint32_t s = blockIdx.x * kWaves + wv; s < n_services; s += gridDim.x * kWaves) {  // (wave-uniform)
-    const LatRowScan B = lat_row_scan(lat_row(sums + ((uint64_t)s << 8) + lane * 4), lane);
-    const LatRowScan C = lat_row_scan(lat_row(sums + (((uint64_t)n_services + s) << 8) + lane * 4), lane);
+    const LatRowScan B = lat_sum_row(sums, s, lane), C = lat_sum_row(sums, (uint64_t)n_services + s, lane);
     const uint32_t bb = lat_quantile_bin(B, M.ppm0), bc = lat_quantile_bin(C, M.ppm0);
-    base += B.total, cur += C.total;
+    spans[0] += B.total, spans[1] += C.total;
     const bool elig = B.total >= M.min_count && C.total >= M.min_count;
     ne += elig ? 1u : 0u;
     const int32_t shift = M.fall ? (int32_t)bb - (int32_t)bc : (int32_t)bc - (int32_t)bb;
@@ -398,39 +400,11 @@ __global__ __launch_bounds__(kLatScoreBlock) void lat_score_kernel(const unsigne
       const unsigned long long top = (1ULL << 48) - 1;
       const unsigned long long score = ((unsigned long long)(uint32_t)shift << 48) | (C.total < top ? C.total : top);
       largest = score > largest ? score : largest;
-      if (lane == 0) {
-        const uint32_t at = atomicAdd(&s_n, 1u);
-        if (at < kLatScoreList) s_cand[at] = ulonglong2{score, (unsigned long long)s};
-      }
+      if (lane == 0) list.push(score, s);
     }
   }
-  if (lane == 0) s_largest[wv] = largest, s_base[wv] = base, s_cur[wv] = cur, s_elig[wv] = ne;
-  __syncthreads();
-  if (wv) return;
-  const uint32_t n = min(s_n, kLatScoreList);
-  if (n) {
-    unsigned long long pos = 0;
-    if (lane == 0) pos = atomicAdd(&T->n_matched, (unsigned long long)n);
-    pos = __shfl(pos, 0);
-    for (uint32_t i = lane; i < n; i += 64)
-      if (pos + i < n_services) cand[pos + i] = s_cand[i];
-  }
-  const bool mine = lane < kWaves;
-  base = mine ? s_base[lane] : 0, cur = mine ? s_cur[lane] : 0, largest = mine ? s_largest[lane] : 0;
-  ne = mine ? s_elig[lane] : 0;
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) {  // (lanes 0..15 hold everything)
-    const unsigned long long ob = __shfl_xor(base, o), oc = __shfl_xor(cur, o), ol = __shfl_xor(largest, o);
-    base += ob, cur += oc;
-    largest = ol > largest ? ol : largest;
-    ne += __shfl_xor(ne, o);
-  }
-  if (lane == 0) {
-    if (ne) atomicAdd(&T->n_resident, (unsigned long long)ne);
-    if (largest) atomicMax(&T->max_est, largest);
-    if (base) atomicAdd(&O->spans_base, base);
-    if (cur) atomicAdd(&O->spans_cur, cur);
-  }
+  unsigned long long *const span_out[2] = {&O->spans_base, &O->spans_cur};
+  list.publish(largest, ne, spans, n_services, cand, T, span_out);
 }
 
 // After the sort, one wave a row i < T->want of T->sel: the service's two
@@ -445,7 +419,7 @@ __global__ __launch_bounds__(kLatQueryBlock) void lat_mov_rows_kernel(const unsi
   const uint64_t s = T->sel[i].y;
   if (s >= n_services) return;  // (a candidate is a service id: never taken)
   for (uint32_t r = 0; r < 2; ++r) {
-    const LatRowScan R = lat_row_scan(lat_row(sums + (((uint64_t)r * n_services + s) << 8) + lane * 4), lane);
+    const LatRowScan R = lat_sum_row(sums, (uint64_t)r * n_services + s, lane);
     if (lane == 0) O->row[i].count[r] = R.total;
     for (uint32_t q = 0; q < SA_LAT_MAX_Q; ++q) {  // (the unasked ones 0: the row is copied whole)
       const uint32_t bin = q < Q.n ? lat_quantile_bin(R, Q.ppm[q]) : 0u;
@@ -525,19 +499,11 @@ __global__ __launch_bounds__(kSloSlideBlock) void slo_slide_kernel(const ulonglo
   const ulonglong2 *p = pairs + (uint64_t)i * n_cov;
   ulonglong2 *P = P_all + (uint64_t)i * (n_cov + 1ull);
   if (lane == 0) P[0] = ulonglong2{0, 0};
-  unsigned long long carry_t = 0, carry_s = 0;
+  ulonglong2 carry{0, 0};
   for (uint32_t k0 = 0; k0 < n_cov; k0 += 64) {  // (the same trips for every lane)
     const uint32_t k = k0 + lane;
-    const ulonglong2 v = k < n_cov ? p[k] : ulonglong2{0, 0};
-    unsigned long long t = v.x, s = v.y;
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-      const unsigned long long ut = __shfl_up(t, d), us = __shfl_up(s, d);
-      if (lane >= d) t += ut, s += us;
-    }
-    t += carry_t, s += carry_s;
-    if (k < n_cov) P[k + 1] = ulonglong2{t, s};
-    carry_t = __shfl(t, 63), carry_s = __shfl(s, 63);
+    const ulonglong2 ts = pair_scan_step(p, k, n_cov, lane, carry);
+    if (k < n_cov) P[k + 1] = ts;
   }
   __threadfence_block();
   __syncthreads();
@@ -570,7 +536,7 @@ __global__ __launch_bounds__(kSloSlideBlock) void slo_slide_kernel(const ulonglo
 // candidates' select and sort (the heavy hitters'), and the selected rows ----
 
 // One wave a row of sums [n_services][256] (the range's rows summed,
-// lat_pair_sums_kernel with one range): thr_bin[s] = lat_quantile_bin of ppm,
+// lat_range_sums_kernel over one range): thr_bin[s] = lat_quantile_bin of ppm,
 // sa_window_latency's rule, 0 for a service without spans.  s < n_services.
 __global__ __launch_bounds__(kLatQueryBlock) void onset_thr_kernel(const unsigned long long *__restrict__ sums,
                                                                    uint32_t n_services, uint32_t ppm,
@@ -578,7 +544,7 @@ __global__ __launch_bounds__(kLatQueryBlock) void onset_thr_kernel(const unsigne
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t s = blockIdx.x * (kLatQueryBlock / 64) + (threadIdx.x >> 6);
   if (s >= n_services) return;  // (wave-uniform)
-  const uint32_t bin = lat_quantile_bin(lat_row_scan(lat_row(sums + ((uint64_t)s << 8) + lane * 4), lane), ppm);
+  const uint32_t bin = lat_quantile_bin(lat_sum_row(sums, s, lane), ppm);
   if (lane == 0) thr_bin[s] = (uint8_t)bin;
 }
 
@@ -592,7 +558,7 @@ constexpr unsigned long long kOnsetCountTop = (1ULL << 44) - 1;  // a candidate'
 // One wave a service s of pairs [n_sel][n_cov] at a time, the waves of the grid
 // striding the services (lat_score_kernel's geometry).  First the range's sums
 // N and S, a lane every 64th window.  Then the prefix scan, 64 windows a step
-// with a carry as slo_slide_kernel's: lane l of step k0 holds N_b and S_b of
+// with a carry (pair_scan_step, as slo_slide_kernel's): lane l of step k0 holds N_b and S_b of
 // split t = k0 + l + 1 (before = windows 0 .. t - 1), a split while t <=
 // n_cov - 1; eligible with N_b and N_a = N - N_b both >= min_count; D = S_a N_b
 // - S_b N_a (negated when fall) as a signed 128-bit integer -- the products
@@ -604,23 +570,19 @@ constexpr unsigned long long kOnsetCountTop = (1ULL << 44) - 1;  // a candidate'
 // and delta_ppm >= min_delta; it leaves as (score, s), score = (delta_ppm <<
 // 44) | min(N, 2^44 - 1) -- delta_ppm <= 10^6 < 2^20 -- ordered as the heavy
 // hitters' pairs.  rec[s] takes the split and its four sums (zeros without an
-// eligible split).  The matches gather in LDS and take one place range in cand
-// [n_sel], and one atomic each a workgroup goes to T->n_matched, T->n_resident
-// (the eligible), T->max_est and O->spans, as lat_score_kernel's.  The pairs
-// index stays below n_sel * n_cov (s < n_sel, k < n_cov), rec's below n_sel.
+// eligible split).  The matches and the tallies go through RankList as
+// lat_score_kernel's: cand [n_sel], T->n_resident the eligible, O->spans.  The
+// pairs index stays below n_sel * n_cov (s < n_sel, k < n_cov), rec's below n_sel.
 __global__ __launch_bounds__(kLatScoreBlock) void onset_scan_kernel(const ulonglong2 *__restrict__ pairs,
                                                                     uint32_t n_sel, uint32_t n_cov, OnsetParams M,
                                                                     OnsetRow *__restrict__ rec,
                                                                     ulonglong2 *__restrict__ cand, TopCtl *T,
                                                                     OnsetOut *O) {
-  constexpr uint32_t kWaves = kLatScoreBlock / 64;
-  __shared__ ulonglong2 s_cand[kLatScoreList];
-  __shared__ unsigned long long s_largest[kWaves], s_spans[kWaves];
-  __shared__ uint32_t s_elig[kWaves], s_n;
+  __shared__ RankList<1> list;
+  constexpr uint32_t kWaves = RankList<1>::kWaves;
   const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-  if (threadIdx.x == 0) s_n = 0;
-  __syncthreads();
-  unsigned long long largest = 0, spans = 0;  // (the wave's own, the same in every lane)
+  list.init();
+  unsigned long long largest = 0, spans[1] = {0};  // (the wave's own, the same in every lane)
   uint32_t ne = 0;
   for (uint32_t s = blockIdx.x * kWaves + wv; s < n_sel; s += gridDim.x * kWaves) {  // (wave-uniform)
     const ulonglong2 *p = pairs + (uint64_t)s * n_cov;
@@ -632,20 +594,13 @@ __global__ __launch_bounds__(kLatScoreBlock) void onset_scan_kernel(const ulongl
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) N += __shfl_xor(N, o), S += __shfl_xor(S, o);
     __int128 best_d = 0;
-    unsigned long long best_nb = 0, best_sb = 0, carry_n = 0, carry_s = 0;
+    unsigned long long best_nb = 0, best_sb = 0;
+    ulonglong2 carry{0, 0};
     uint32_t best_t = 0;
     for (uint32_t k0 = 0; k0 + 1 < n_cov; k0 += 64) {  // (the same trips for every lane; the last window ends no split)
       const uint32_t k = k0 + lane;
-      const ulonglong2 v = k < n_cov ? p[k] : ulonglong2{0, 0};
-      unsigned long long nb = v.x, sb = v.y;
-#pragma unroll
-      for (uint32_t d = 1; d < 64; d <<= 1) {
-        const unsigned long long un = __shfl_up(nb, d), us = __shfl_up(sb, d);
-        if (lane >= d) nb += un, sb += us;
-      }
-      nb += carry_n, sb += carry_s;
-      carry_n = __shfl(nb, 63), carry_s = __shfl(sb, 63);
-      const unsigned long long na = N - nb, sa = S - sb;
+      const ulonglong2 before = pair_scan_step(p, k, n_cov, lane, carry);
+      const unsigned long long nb = before.x, sb = before.y, na = N - nb, sa = S - sb;
       if (k + 1 < n_cov && nb >= M.min_count && na >= M.min_count) {
         __int128 d = (__int128)sa * (__int128)nb - (__int128)sb * (__int128)na;
         if (M.fall) d = -d;
@@ -662,7 +617,7 @@ __global__ __launch_bounds__(kLatScoreBlock) void onset_scan_kernel(const ulongl
       if (ot && (best_t == 0 || od > best_d || (od == best_d && ot > best_t)))
         best_d = od, best_t = ot, best_nb = onb, best_sb = osb;
     }
-    spans += N;
+    spans[0] += N;
     const bool elig = best_t != 0;
     ne += elig ? 1u : 0u;
     const unsigned long long na = elig ? N - best_nb : 0, sa = elig ? S - best_sb : 0;
@@ -675,37 +630,11 @@ __global__ __launch_bounds__(kLatScoreBlock) void onset_scan_kernel(const ulongl
     if (elig && best_d > 0 && delta >= 1 && delta >= (long long)M.min_delta) {
       const unsigned long long score = ((unsigned long long)delta << 44) | (N < kOnsetCountTop ? N : kOnsetCountTop);
       largest = score > largest ? score : largest;
-      if (lane == 0) {
-        const uint32_t at = atomicAdd(&s_n, 1u);
-        if (at < kLatScoreList) s_cand[at] = ulonglong2{score, (unsigned long long)s};
-      }
+      if (lane == 0) list.push(score, s);
     }
   }
-  if (lane == 0) s_largest[wv] = largest, s_spans[wv] = spans, s_elig[wv] = ne;
-  __syncthreads();
-  if (wv) return;
-  const uint32_t n = min(s_n, kLatScoreList);
-  if (n) {
-    unsigned long long pos = 0;
-    if (lane == 0) pos = atomicAdd(&T->n_matched, (unsigned long long)n);
-    pos = __shfl(pos, 0);
-    for (uint32_t i = lane; i < n; i += 64)
-      if (pos + i < n_sel) cand[pos + i] = s_cand[i];
-  }
-  const bool mine = lane < kWaves;
-  spans = mine ? s_spans[lane] : 0, largest = mine ? s_largest[lane] : 0, ne = mine ? s_elig[lane] : 0;
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) {  // (lanes 0..15 hold everything)
-    const unsigned long long os = __shfl_xor(spans, o), ol = __shfl_xor(largest, o);
-    spans += os;
-    largest = ol > largest ? ol : largest;
-    ne += __shfl_xor(ne, o);
-  }
-  if (lane == 0) {
-    if (ne) atomicAdd(&T->n_resident, (unsigned long long)ne);
-    if (largest) atomicMax(&T->max_est, largest);
-    if (spans) atomicAdd(&O->spans, spans);
-  }
+  unsigned long long *const span_out[1] = {&O->spans};
+  list.publish(largest, ne, spans, n_sel, cand, T, span_out);
 }
 
 // After the sort, one thread a row i < T->want of T->sel: the service's record
@@ -764,21 +693,33 @@ hipError_t launch_lat_scan(const unsigned long long *sums, uint64_t n_rows, cons
   return hipGetLastError();
 }
 
-uint32_t lat_pair_stripes(uint32_t n_services, uint32_t len) {
+// The stripes a (range, service) unit's windows are split into for the longest
+// range `len` (1, 2 or a multiple of 4): a power of two, no more than fill
+// about kLatPairWaves waves over two ranges' units, none finer than kLatStripeRows windows.
+static uint32_t lat_range_stripes(uint32_t n_services, uint32_t len) {
   uint32_t stripes = 1;
   while (2 * stripes * 2ull * n_services <= kLatPairWaves && stripes * kLatStripeRows < len) stripes *= 2;
   return stripes;
 }
 
-hipError_t launch_lat_pair_sums(const unsigned long long *ring, uint32_t n_services, uint32_t n_windows,
-                                uint64_t first_b, uint32_t len_b, uint64_t first_c, uint32_t len_c,
-                                unsigned long long *sums, hipStream_t s) {
-  const uint32_t stripes = lat_pair_stripes(n_services, std::max(len_b, len_c));
-  const uint64_t waves = 2ull * n_services * stripes, per = kLatPairBlock / 64;
+// The service-ranking scans' grid: a service a wave up to kLatScoreGrid
+// workgroups, then several -- no more than a workgroup's list holds
+static uint32_t lat_score_grid(uint32_t n) {
+  const uint32_t per = kLatScoreBlock / 64;
+  return std::max(std::min((n + per - 1) / per, kLatScoreGrid), (n + kLatScoreList - 1) / kLatScoreList);
+}
+
+hipError_t launch_lat_range_sums(const unsigned long long *ring, uint32_t n_services, uint32_t n_windows,
+                                 const uint64_t *range, uint32_t n_ranges, unsigned long long *sums, hipStream_t s) {
+  const uint64_t first_b = range[0], first_c = n_ranges > 1 ? range[2] : 0;
+  const uint32_t len_b = (uint32_t)(range[1] - range[0] + 1), len_c = n_ranges > 1 ? (uint32_t)(range[3] - range[2] + 1) : 0;
+  const uint32_t stripes = lat_range_stripes(n_services, std::max(len_b, len_c));
+  const uint64_t units = (uint64_t)n_ranges * n_services, waves = units * stripes, per = kLatPairBlock / 64;
   if (stripes > 4)  // (the workgroups of a unit add to its row)
-    if (hipError_t e = hipMemsetAsync(sums, 0, 2ull * n_services * SA_LAT_BINS * 8, s); e != hipSuccess) return e;
-  hipLaunchKernelGGL(lat_pair_sums_kernel, dim3((uint32_t)((waves + per - 1) / per)), dim3(kLatPairBlock), 0, s, ring,
-                     n_services, n_windows - 1, first_b, len_b, first_c, len_c, 2u, stripes, std::min(stripes, 4u), sums);
+    if (hipError_t e = hipMemsetAsync(sums, 0, units * SA_LAT_BINS * 8, s); e != hipSuccess) return e;
+  hipLaunchKernelGGL(lat_range_sums_kernel, dim3((uint32_t)((waves + per - 1) / per)), dim3(kLatPairBlock), 0, s, ring,
+                     n_services, n_windows - 1, first_b, len_b, first_c, len_c, n_ranges, stripes, std::min(stripes, 4u),
+                     sums);
   return hipGetLastError();
 }
 
@@ -791,15 +732,11 @@ hipError_t launch_lat_movers(const unsigned long long *sums, uint32_t n_services
   for (uint32_t i = 0; i < Q.n; ++i) Q.ppm[i] = q_ppm[i];
   if (hipError_t e = hipMemsetAsync(T, 0, offsetof(TopCtl, sel), s); e != hipSuccess) return e;
   if (hipError_t e = hipMemsetAsync(O, 0, offsetof(LatMovOut, row), s); e != hipSuccess) return e;
-  // a service a wave up to kLatScoreGrid workgroups, then several -- no more than a workgroup's list holds
-  const uint32_t per = kLatScoreBlock / 64;
-  const uint32_t score_grid = std::max(std::min((n_services + per - 1) / per, kLatScoreGrid),
-                                       (n_services + kLatScoreList - 1) / kLatScoreList);
-  hipLaunchKernelGGL(lat_score_kernel, dim3(score_grid), dim3(kLatScoreBlock), 0, s, sums, n_services,
+  hipLaunchKernelGGL(lat_score_kernel, dim3(lat_score_grid(n_services)), dim3(kLatScoreBlock), 0, s, sums, n_services,
                      LatMovParams{min_count, min_shift, fall, Q.ppm[0]}, counts, cand, T, O);
   if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
   // (no row to sum: the score kernel took both ranges' spans)
-  if (hipError_t e = launch_top_select(counts, 0, k, n_services, cand, T, s); e != hipSuccess) return e;
+  if (hipError_t e = launch_top_select(nullptr, 0, k, n_services, cand, T, s); e != hipSuccess) return e;
   const uint32_t rows_per = kLatQueryBlock / 64;
   hipLaunchKernelGGL(lat_mov_rows_kernel, dim3((k + rows_per - 1) / rows_per), dim3(kLatQueryBlock), 0, s, sums,
                      n_services, Q, T, O);
@@ -832,18 +769,8 @@ hipError_t launch_slo_slide(const unsigned long long *pairs, uint32_t n_sel, uin
   return hipGetLastError();
 }
 
-hipError_t launch_onset_thr(const unsigned long long *ring, uint32_t n_services, uint32_t n_windows, uint64_t first,
-                            uint32_t len, uint32_t q_ppm, unsigned long long *sums, uint8_t *thr_bin, hipStream_t s) {
-  if (ring) {  // the range's rows summed per service: the movers' kernel over one range
-    const uint32_t stripes = lat_pair_stripes(n_services, len);
-    const uint64_t waves = (uint64_t)n_services * stripes, per = kLatPairBlock / 64;
-    if (stripes > 4)  // (the workgroups of a unit add to its row)
-      if (hipError_t e = hipMemsetAsync(sums, 0, (size_t)n_services * SA_LAT_BINS * 8, s); e != hipSuccess) return e;
-    hipLaunchKernelGGL(lat_pair_sums_kernel, dim3((uint32_t)((waves + per - 1) / per)), dim3(kLatPairBlock), 0, s, ring,
-                       n_services, n_windows - 1, first, len, first, 0u, 1u, stripes, std::min(stripes, 4u), sums);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-  }
-  if (!thr_bin) return hipSuccess;
+hipError_t launch_onset_thr(const unsigned long long *sums, uint32_t n_services, uint32_t q_ppm, uint8_t *thr_bin,
+                            hipStream_t s) {
   const uint32_t per = kLatQueryBlock / 64;
   hipLaunchKernelGGL(onset_thr_kernel, dim3((n_services + per - 1) / per), dim3(kLatQueryBlock), 0, s, sums, n_services,
                      q_ppm, thr_bin);
@@ -855,17 +782,12 @@ hipError_t launch_onset(const unsigned long long *pairs, uint32_t n_sel, uint32_
                         OnsetRow *rec, ulonglong2 *cand, TopCtl *T, OnsetOut *O, hipStream_t s) {
   if (hipError_t e = hipMemsetAsync(T, 0, offsetof(TopCtl, sel), s); e != hipSuccess) return e;
   if (hipError_t e = hipMemsetAsync(O, 0, offsetof(OnsetOut, row), s); e != hipSuccess) return e;
-  // lat_score_kernel's grid: a service a wave up to kLatScoreGrid workgroups, then several -- no more than a
-  // workgroup's list holds
-  const uint32_t per = kLatScoreBlock / 64;
-  const uint32_t grid = std::max(std::min((n_sel + per - 1) / per, kLatScoreGrid),
-                                 (n_sel + kLatScoreList - 1) / kLatScoreList);
-  hipLaunchKernelGGL(onset_scan_kernel, dim3(grid), dim3(kLatScoreBlock), 0, s,
+  hipLaunchKernelGGL(onset_scan_kernel, dim3(lat_score_grid(n_sel)), dim3(kLatScoreBlock), 0, s,
                      reinterpret_cast<const ulonglong2 *>(pairs), n_sel, n_cov, OnsetParams{min_count, min_delta, fall},
                      rec, cand, T, O);
   if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
   // (no row to sum: the scan took the range's spans)
-  if (hipError_t e = launch_top_select(pairs, 0, k, n_sel, cand, T, s); e != hipSuccess) return e;
+  if (hipError_t e = launch_top_select(nullptr, 0, k, n_sel, cand, T, s); e != hipSuccess) return e;
   hipLaunchKernelGGL(onset_rows_kernel, dim3((k + kLatQueryBlock - 1) / kLatQueryBlock), dim3(kLatQueryBlock), 0, s, rec,
                      thr_bin, n_sel, T, O);
   return hipGetLastError();

@@ -28,8 +28,10 @@
 // summed cells among those resident in the key table:
 //
 //   top_scan_kernel      the key table against the cells: (estimate, key) of
-//                        every match, the resident keys, the largest estimate.
-//   top_prepare_kernel   error_spans and the select's first state.
+//                        every match, the resident keys, the largest estimate
+//                        (sa_device.h's table_scan, the estimate as its score).
+//   top_prepare_kernel   error_spans (a caller without a row to sum: 0) and
+//                        the select's first state.
 //   top_digit_kernel     one digit of the radix select over (estimate, ~key),
 //                        chosen on the device.
 //   top_gather_kernel    the selected pairs and the threshold's class.
@@ -39,7 +41,8 @@
 // rate changed most between two ranges, with the same select and sort:
 //
 //   movers_scan_kernel   the key table against both ranges' cells: (score,
-//                        key) of every match, the resident keys, the largest score.
+//                        key) of every match, the resident keys, the largest
+//                        score (table_scan again).
 //   movers_rows_kernel   the selected keys' estimates in both ranges, and the
 //                        baseline's error_spans.
 //
@@ -435,13 +438,10 @@ __device__ __forceinline__ uint32_t top_digit(unsigned long long est, unsigned l
   return (uint32_t)((level >= 8 ? est >> (8 * (level - 8)) : nkey >> (8 * level)) & 0xFFu);
 }
 
-// Walks gkeys[0..cap) once.  A slot's key is recovered as fold_errcnt_slots
-// does (stored id * kinv; a dense engine's bound hash, 0 when unbound); its
-// estimate is the minimum over the rows of cells [d][w] -- staged in LDS
-// (LDS = 1: d * w * 8 <= kTopCellsLds dynamic bytes) or read through global
-// memory.  Keys with an estimate >= min_count (>= 1) leave as (estimate, key)
-// into cand [cap] through one returning atomic per wave (compact_kernel's
-// idiom); T counts the resident keys, the matches and the largest estimate.
+// table_scan (sa_device.h) with a key's estimate as its score: the minimum
+// over the rows of cells [d][w] -- staged in LDS (LDS = 1: d * w * 8 <=
+// kTopCellsLds dynamic bytes) or read through global memory.  Keys with an
+// estimate >= min_count (>= 1) match.
 template <int LDS>
 __global__ __launch_bounds__(kTopScanBlock) void top_scan_kernel(const unsigned long long *gkeys, uint64_t cap,
                                                                  uint64_t kinv, const unsigned long long *cells,
@@ -458,14 +458,8 @@ __global__ __launch_bounds__(kTopScanBlock) void top_scan_kernel(const unsigned 
   uint64_t sd[8];  // (cms_d <= 8)
 #pragma unroll
   for (uint32_t r = 0; r < 8; ++r) sd[r] = r < d ? seeds[r] : 0;
-  uint32_t resident = 0;
-  unsigned long long largest = 0;
-  for (uint64_t s = blockIdx.x * (uint64_t)kTopScanBlock + threadIdx.x; s < cap;
-       s += (uint64_t)gridDim.x * kTopScanBlock) {
-    const uint64_t key = gkeys[s] * kinv;
-    if (!key) continue;
-    ++resident;
-    unsigned long long est = ~0ULL;
+  table_scan<kTopScanBlock>(gkeys, cap, kinv, cand, T, [&](uint64_t key, unsigned long long &est) {
+    est = ~0ULL;
 #pragma unroll
     for (uint32_t r = 0; r < 8; ++r) {
       if (r < d) {
@@ -474,33 +468,20 @@ __global__ __launch_bounds__(kTopScanBlock) void top_scan_kernel(const unsigned 
         est = v < est ? v : est;
       }
     }
-    if (est < min_count) continue;
-    largest = est > largest ? est : largest;
-    const unsigned long long pos = wave_ticket(&T->n_matched, __ballot(true));
-    if (pos < cap) cand[pos] = ulonglong2{est, key};  // (a table holds a key once: at most cap matches)
-  }
-  resident = wave_sum(resident);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long other = ((unsigned long long)(uint32_t)__shfl_xor((int)(uint32_t)(largest >> 32), o, 64) << 32) |
-                                     (uint32_t)__shfl_xor((int)(uint32_t)largest, o, 64);
-    largest = other > largest ? other : largest;
-  }
-  if ((threadIdx.x & 63u) == 0) {
-    if (resident) atomicAdd(&T->n_resident, (unsigned long long)resident);
-    if (largest) atomicMax(&T->max_est, largest);
-  }
+    return est >= min_count;
+  });
 }
 
-// After the scan (one workgroup): error_spans = the sum of row 0 of the
-// cells, and the select's first state.  At most kTopSel matches: nothing to
+// After the scan (one workgroup): error_spans = the sum of row0 [w], row 0 of
+// the cells (a scan with no row to sum passes w = 0: the loop never runs, so a
+// null row0 is not read), and the select's first state.  At most kTopSel matches: nothing to
 // select (level 16: no digit resolved, every match is in the class).
 // Otherwise the first digit is the top non-zero byte of the largest estimate.
-__global__ __launch_bounds__(kTopBlock) void top_prepare_kernel(const unsigned long long *cells, uint32_t w, uint32_t k,
+__global__ __launch_bounds__(kTopBlock) void top_prepare_kernel(const unsigned long long *row0, uint32_t w, uint32_t k,
                                                                 TopCtl *T) {
   __shared__ unsigned long long part[kTopBlock];
   unsigned long long acc = 0;
-  for (uint32_t i = threadIdx.x; i < w; i += kTopBlock) acc += cells[i];
+  for (uint32_t i = threadIdx.x; i < w; i += kTopBlock) acc += row0[i];
   part[threadIdx.x] = acc;
   __syncthreads();
   for (uint32_t s = kTopBlock / 2; s > 0; s >>= 1) {
@@ -651,13 +632,11 @@ __device__ __forceinline__ void movers_estimates(const unsigned long long *base,
   }
 }
 
-// top_scan_kernel over two arrays: a slot's key recovered the same way, its
-// estimates eb and ec taken from base and cur -- both staged in LDS (LDS = 1:
-// 2 * d * w * 8 <= kMoversCellsLds dynamic bytes, base first) or both read
-// through global memory -- and score = ec * nb - eb * nc as a signed number,
-// negated when `fall`.  Keys with score >= min_score (>= 1, so the score
-// orders as an unsigned number) leave as (score, key) into cand [cap]; T
-// counts the resident keys, the matches and the largest score (max_est).
+// top_scan_kernel over two arrays: a key's estimates eb and ec taken from base
+// and cur -- both staged in LDS (LDS = 1: 2 * d * w * 8 <= kMoversCellsLds
+// dynamic bytes, base first) or both read through global memory -- and score =
+// ec * nb - eb * nc as a signed number, negated when `fall`.  Keys with score
+// >= min_score (>= 1, so the score orders as an unsigned number) match.
 template <int LDS>
 __global__ __launch_bounds__(kTopScanBlock) void movers_scan_kernel(const unsigned long long *gkeys, uint64_t cap,
                                                                     uint64_t kinv, const unsigned long long *base,
@@ -677,33 +656,13 @@ __global__ __launch_bounds__(kTopScanBlock) void movers_scan_kernel(const unsign
   uint64_t sd[8];  // (cms_d <= 8)
 #pragma unroll
   for (uint32_t r = 0; r < 8; ++r) sd[r] = r < d ? seeds[r] : 0;
-  uint32_t resident = 0;
-  unsigned long long largest = 0;
-  for (uint64_t s = blockIdx.x * (uint64_t)kTopScanBlock + threadIdx.x; s < cap;
-       s += (uint64_t)gridDim.x * kTopScanBlock) {
-    const uint64_t key = gkeys[s] * kinv;
-    if (!key) continue;
-    ++resident;
+  table_scan<kTopScanBlock>(gkeys, cap, kinv, cand, T, [&](uint64_t key, unsigned long long &score) {
     unsigned long long eb, ec;
     movers_estimates(b, c, d, w, shift, sd, key, eb, ec);
-    unsigned long long score = ec * nb - eb * nc;  // (two's complement: the signed difference)
+    score = ec * nb - eb * nc;  // (two's complement: the signed difference)
     if (fall) score = 0ULL - score;
-    if ((long long)score < 1 || score < min_score) continue;
-    largest = score > largest ? score : largest;
-    const unsigned long long pos = wave_ticket(&T->n_matched, __ballot(true));
-    if (pos < cap) cand[pos] = ulonglong2{score, key};  // (a table holds a key once: at most cap matches)
-  }
-  resident = wave_sum(resident);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long other = ((unsigned long long)(uint32_t)__shfl_xor((int)(uint32_t)(largest >> 32), o, 64) << 32) |
-                                     (uint32_t)__shfl_xor((int)(uint32_t)largest, o, 64);
-    largest = other > largest ? other : largest;
-  }
-  if ((threadIdx.x & 63u) == 0) {
-    if (resident) atomicAdd(&T->n_resident, (unsigned long long)resident);
-    if (largest) atomicMax(&T->max_est, largest);
-  }
+    return (long long)score >= 1 && score >= min_score;
+  });
 }
 
 // After the sort: O->est[i] = the (baseline, current) estimates of row i of
@@ -743,11 +702,11 @@ static uint32_t top_scan_grid(uint64_t cap) {
   return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, (cap + 4 * kTopScanBlock - 1) / (4 * kTopScanBlock)), 512);
 }
 
-// After a scan left its matches in cand [cap] and its counters in T: the row-0
-// sum of cells [..][w] into T->error_spans, then the select and the sort.
-hipError_t launch_top_select(const unsigned long long *cells, uint32_t w, uint32_t k, uint64_t cap,
+// After a scan left its matches in cand [cap] and its counters in T: the sum of
+// row0 [w] into T->error_spans (nullptr, 0: none), then the select and the sort.
+hipError_t launch_top_select(const unsigned long long *row0, uint32_t w, uint32_t k, uint64_t cap,
                              const ulonglong2 *cand, TopCtl *T, hipStream_t s) {
-  hipLaunchKernelGGL(top_prepare_kernel, dim3(1), dim3(kTopBlock), 0, s, cells, w, k, T);
+  hipLaunchKernelGGL(top_prepare_kernel, dim3(1), dim3(kTopBlock), 0, s, row0, w, k, T);
   // the select's workgroups stride the matches (at most cap); every digit's
   // launch is enqueued, the device decides which ones work -- none does when
   // the matches cannot outnumber what the sort holds (the prepare kernel sets

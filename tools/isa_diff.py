@@ -41,6 +41,9 @@ RENAMED = {
     # (the laboratory build now takes the 512-thread kernel from the product's option set: LabV2<...> -> V2Lean)
     "_ZN2sa12_GLOBAL__N_116ingest_v2_kernelILi0ELi0ELi0ELb0ELj512ENS0_5LabV2ILi2ELi2ELi2ELb0ELin1ELb1ELi1ELb1ELb1ELb0ELb0EEEEEvNS_12IngestParamsE":
         "_ZN2sa12_GLOBAL__N_116ingest_v2_kernelILi0ELi0ELi0ELb0ELj512ENS0_6V2LeanEEEvNS_12IngestParamsE",
+    # the latency range sums, named for what they sum: n_ranges in {1, 2}
+    "_ZN2sa12_GLOBAL__N_120lat_pair_sums_kernelEPKyjjmjmjjjjPy":
+        "_ZN2sa12_GLOBAL__N_121lat_range_sums_kernelEPKyjjmjmjjjjPy",
 }
 # (the laboratory build's ablation instances: <MODE> -> <BtHashed, MODE>)
 for _m in (1, 2, 3, 4, 8, 16, 32, 64):

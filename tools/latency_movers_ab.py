@@ -40,7 +40,7 @@ sys.path.insert(0, ROOT)
 Q = (0.99, 0.5, 0.95)
 K = 10
 SHAPES = (("default", 64, 8, 4, 400_000), ("long", 32, 1024, 512, 4_000_000), ("wide", 65_536, 4, 2, 4_000_000))
-SUMS_KERNEL = "lat_pair_sums_kernel"
+SUMS_KERNEL = "lat_range_sums_kernel"
 
 
 def load(S, W, n):
