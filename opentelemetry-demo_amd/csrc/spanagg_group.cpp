@@ -26,7 +26,13 @@
 #include "sa_internal.h"
 #include "sa_query_args.h"
 #include "sa_results.h"
+#include "sa_shard.h"
 #include "spanagg.h"
+
+using sa::ExpoAcc;
+using sa::expo_fold;
+using sa::kMaxMembers;
+using sa::shard_of;
 
 namespace {
 
@@ -47,8 +53,6 @@ __global__ void max_slices_u8(uint8_t *dst, const uint8_t *src, uint32_t n, uint
 }
 
 uint32_t grid_for(uint64_t len) { return (uint32_t)std::min<uint64_t>((len + 255) / 256, 4096); }
-
-constexpr uint32_t kMaxMembers = 64;
 
 // Sum of members' dense rows that live on one device: dst[i] = sum_k src[k][i]
 // straight from each member's buffer (no stacking copy).
@@ -93,13 +97,7 @@ __global__ void finalize_rows_kernel(const unsigned long long *rows, uint64_t nu
   }
 }
 
-// ---- trace-id sharding (engine = trace_w1 % n) ------------------------------
-// trace_w1 % n from 32-bit remainders: w1 = hi * 2^32 + lo, so
-// w1 % n = ((hi % n) * (2^32 % n) + lo % n) % n (< n^2 <= 4096 before the
-// last remainder); no 64-bit division per span.
-__host__ __device__ inline uint32_t shard_of(uint64_t w1, uint32_t n, uint32_t r32) {
-  return (((uint32_t)(w1 >> 32) % n) * r32 + (uint32_t)w1 % n) % n;
-}
+// (the shard rule, engine = trace_w1 % n: sa::shard_of, sa_shard.h)
 
 // ---- device partition (sa_group_ingest_device) -------------------------------
 // Workgroup b of the partition owns the contiguous span range [b * per,
@@ -540,56 +538,7 @@ int union_count(sa_group *g, uint32_t i, uint64_t *nu) {
   return SA_OK;
 }
 
-// One series' exponential histogram while members' deltas are folded in.
-struct ExpoAcc {
-  uint64_t count = 0, zero = 0, sum_ns = 0;
-  double min = 0, max = 0;
-  int32_t scale = 20, offset = 0;  // go-expohisto's initial scale
-  std::vector<uint64_t> c;         // positive buckets offset .. offset + size - 1
-};
-
-inline int64_t shr_floor(int64_t v, int k) { return v >= 0 ? v >> k : -((-v - 1) >> k) - 1; }
-
-// Folds one member's histogram into a: go-expohisto's state depends only on
-// the values, and index(v) at scale s is index(v) at scale s + k shifted
-// right by k, so both go to the smaller scale, the index ranges unite and
-// the least further downscale that fits max_size applies (changeScale) --
-// exactly the histogram one engine fed both members' spans would hold.
-void expo_fold(ExpoAcc &a, const sa_exp_result &r, uint64_t j, uint32_t max_size) {
-  if (r.count[j] == 0) return;
-  if (a.count == 0) {
-    a.min = r.min[j];
-    a.max = r.max[j];
-  } else {
-    a.min = std::min(a.min, r.min[j]);
-    a.max = std::max(a.max, r.max[j]);
-  }
-  a.count += r.count[j];
-  a.zero += r.zero_count[j];
-  a.sum_ns += r.sum_ns[j];
-  const uint32_t nb = r.n_buckets[j];
-  const uint64_t *cnt = r.bucket_counts + j * r.max_size;
-  if (nb == 0) return;
-  if (a.c.empty()) {
-    a.scale = r.scale[j];
-    a.offset = r.offset[j];
-    a.c.assign(cnt, cnt + nb);
-    return;
-  }
-  int s = std::min(a.scale, r.scale[j]);
-  const int ka = a.scale - s, kd = r.scale[j] - s;
-  int64_t lo = std::min(shr_floor(a.offset, ka), shr_floor(r.offset[j], kd));
-  int64_t hi = std::max(shr_floor((int64_t)a.offset + (int64_t)a.c.size() - 1, ka),
-                        shr_floor((int64_t)r.offset[j] + nb - 1, kd));
-  int c = 0;
-  while (hi - lo >= (int64_t)max_size) lo = shr_floor(lo, 1), hi = shr_floor(hi, 1), ++c;
-  std::vector<uint64_t> out((size_t)(hi - lo + 1), 0);
-  for (size_t i = 0; i < a.c.size(); ++i) out[(size_t)(shr_floor((int64_t)a.offset + (int64_t)i, ka + c) - lo)] += a.c[i];
-  for (uint32_t i = 0; i < nb; ++i) out[(size_t)(shr_floor((int64_t)r.offset[j] + i, kd + c) - lo)] += cnt[i];
-  a.scale = s - c;
-  a.offset = (int32_t)lo;
-  a.c.swap(out);
-}
+// (the fold of the members' exponential histograms: sa::expo_fold, sa_shard.h)
 
 }  // namespace
 
