@@ -22,6 +22,7 @@
  *   (new) heavy hitters over a span of windows      sa_window_top (key table scanned on the device)
  *   (new) traces shared by pairs of services        sa_window_overlap (pairwise register maxima on the device)
  *   (new) series whose ERROR rate changed most      sa_window_movers (key table against two ranges' cells on the device)
+ *   (new) when each series began to fail            sa_window_error_onset (every split of a range per resident key, one walk over the ring's cells on the device)
  *   (new) duration quantiles per service and window sa_window_latency (log-linear histograms in the ring, SA_OPT_WINDOW_LATENCY)
  *   (new) services whose latency shifted most       sa_window_latency_movers (two ranges' histograms summed, scored and selected on the device)
  *   (new) latency SLO burn over sliding widths      sa_window_slo (rows cut to (total, slow) pairs at a threshold, prefix sums on the device)
@@ -482,6 +483,67 @@ int sa_window_movers(sa_engine *e, uint64_t base_first, uint64_t base_last, uint
                      sa_movers_result **out);
 void sa_movers_result_free(sa_movers_result *r);
 
+/* ---- error onset over the window ring ----
+ * "Since when has this series been failing": sa_window_movers needs the caller
+ * to know where "before" ends and "after" begins; this call tries every split
+ * of first..last for every candidate -- one walk over the range's windows with
+ * the prefix sums of the key's cells -- and returns the k series whose best
+ * split scores highest, each with the window to hold against the deploy log.
+ * No state beyond sa_window_top's. */
+#define SA_ERROR_ONSET_FALL 1u   /* rank recoveries: the split after which the errors fell most */
+typedef struct {
+    uint64_t first_window, last_window;   /* the range searched, inclusive */
+    uint32_t k, n;                        /* asked for; returned (n <= k) */
+    uint32_t flags, pad;
+    uint64_t n_resident;            /* candidates, as sa_top_result */
+    uint64_t n_eligible;            /* candidates with E >= max(min_count, 1) */
+    uint64_t n_matched;             /* eligible candidates whose best D >= max(min_score, 1) */
+    uint64_t error_spans;           /* row 0 of the summed cells, as sa_top_result */
+    const uint64_t *key_hash;       /* [n] */
+    const uint64_t *onset_window;   /* [n] the first window of "after" */
+    const int64_t  *score;          /* [n] the best split's D, >= 1 */
+    const uint64_t *errors_before;  /* [n] B at the best split */
+    const uint64_t *errors_after;   /* [n] A at the best split */
+} sa_error_onset_result;
+
+/* Candidates: exactly sa_window_top's -- every non-zero key resident in the
+ * key table when the call runs, on every ingest path; on an SA_OPT_DENSE_IDS
+ * engine the bound hash, unbound indices not being candidates.  Key 0 and
+ * series that got no slot are never candidates.  A reclaim empties the
+ * candidates and keeps the cells.
+ * Estimates: a key has column c_r = splitmix64(key ^ seed_r) >> shift in row r.
+ * With n = last - first + 1 and x_r[j] the cell of window first + j (every
+ * window of the range is folded before any cell is read), S_r = the sum of
+ * x_r[j] over j and E = min_r S_r: bit for bit what sa_window_range(e, first,
+ * last, &key, 1, 0, ..) returns.  A key is eligible when E >= max(min_count, 1).
+ * Splits: t in 1 .. n - 1; before is windows first .. first + t - 1, after is
+ * first + t .. last.  B(t) = min_r sum_{j<t} x_r[j] and A(t) = min_r (S_r -
+ * sum_{j<t} x_r[j]): both are minima of sums, each bit for bit sa_window_range
+ * over its side (the two minima may come from different rows).
+ * Score: D(t) = A(t) * t - B(t) * (n - t) as a signed 64-bit integer, negated
+ * under SA_ERROR_ONSET_FALL: bit for bit the score sa_window_movers gives the
+ * key for base = (first, first + t - 1) and cur = (first + t, last), with that
+ * call's exactness bound (estimates below 2^50, rings of at most 4,096 windows).
+ * Best split: the split with the largest D; among equal D the latest split
+ * wins -- deterministic, and it puts the onset on the first failing window
+ * after a run of empty ones.  onset_window = first + t.  A range of one window
+ * is valid and has no split: n_matched == 0 with the counters filled.
+ * Order: a key is matched when it is eligible and its best D >= max(min_score,
+ * 1); the matched keys sorted by D descending, then key_hash ascending (the
+ * movers' total order); the first n = min(k, n_matched) of them are returned,
+ * in that order.  min_score >= 2^63 matches nothing.
+ * Ordering and waiting as sa_window_top: joins every launch in flight, folds
+ * the range before any cell is read, runs on the engine stream, waits once,
+ * clears nothing (two calls give equal bits).
+ * SA_EINVAL for a null `out`, k == 0, k > SA_TOP_MAX_K, flag bits other than
+ * SA_ERROR_ONSET_FALL; SA_ERANGE as sa_window_range; SA_ENOMEM when the device
+ * scratch (sa_window_top's and the rows' splits, allocated by the first call)
+ * or the result cannot be allocated.  The engine stays usable after any error.
+ * Free with sa_error_onset_result_free. */
+int sa_window_error_onset(sa_engine *e, uint64_t first, uint64_t last, uint32_t k, uint64_t min_count,
+                          uint64_t min_score, uint32_t flags, sa_error_onset_result **out);
+void sa_error_onset_result_free(sa_error_onset_result *r);
+
 /* ---- service overlap over the window ring ----
  * "How many traces do two services share over these windows": every service's
  * registers are filled from the same hash of the trace id, so the register-wise
@@ -903,6 +965,16 @@ int sa_group_window_top(sa_group *g, uint64_t first, uint64_t last, uint32_t k, 
 int sa_group_window_movers(sa_group *g, uint64_t base_first, uint64_t base_last, uint64_t cur_first,
                            uint64_t cur_last, uint32_t k, uint64_t min_score, uint32_t flags,
                            sa_movers_result **out);
+/* sa_window_error_onset of a group: every member exports the cells of every
+ * window of the range -- not their sum: n x d x w x 8 bytes a member, SA_ENOMEM
+ * when that does not fit -- the transport sums the arrays across members and
+ * leaves the sums on every member, every member scans its own key table
+ * against the merged windows (a row depends on the key and the merged cells
+ * only), and the host drops the repeats and cuts to k in the same order.  The
+ * rows and error_spans equal those of one engine fed every span; n_resident,
+ * n_eligible and n_matched are summed over members, as in sa_group_window_top. */
+int sa_group_window_error_onset(sa_group *g, uint64_t first, uint64_t last, uint32_t k, uint64_t min_count,
+                                uint64_t min_score, uint32_t flags, sa_error_onset_result **out);
 /* sa_window_overlap of a group: every member max-merges its own windows on
  * its device, the group's transport merges the members' registers (max, every
  * service's rows as for sa_group_window_range), and member 0's device gathers

@@ -1,6 +1,6 @@
 // engine_window.cpp -- the queries over the ring of window sketches:
-// sa_window_range, _series, _top, _movers and _overlap (kernels in
-// spanagg_range.hip and spanagg_overlap.hip), each with the asynchronous
+// sa_window_range, _series, _top, _movers, _error_onset and _overlap (kernels
+// in spanagg_range.hip, spanagg_error_onset.hip and spanagg_overlap.hip), each with the asynchronous
 // halves the engine group runs per member (sa_grp, sa_group_hooks.h) and its
 // result's free.  Every query checks its arguments (sa_query_args.h), joins
 // the launches in flight (begin_read), sizes its scratch, queues its work on
@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstddef>
 #include <cstdlib>
@@ -27,7 +28,8 @@ static hipError_t copy_top(const sa::TopCtl *ctl, uint32_t k, unsigned long long
   return st != hipSuccess ? st : hipMemcpyAsync(rows, ctl->sel, (size_t)k * 16, hipMemcpyDeviceToHost, s);
 }
 
-static_assert(offsetof(sa::MoversOut, est) == 16 && offsetof(sa::LatMovOut, row) == 16 && offsetof(sa::OnsetOut, row) == 16,
+static_assert(offsetof(sa::MoversOut, est) == 16 && offsetof(sa::LatMovOut, row) == 16 && offsetof(sa::OnsetOut, row) == 16 &&
+                  offsetof(sa::ErrOnsetOut, row) == 16,
               "a ranked block's head");
 hipError_t copy_ranked(hipError_t st, const sa::TopCtl *ctl, uint32_t k, unsigned long long head[4], ulonglong2 *sel,
                        const void *d_out, size_t row_bytes, void *block, hipStream_t s) {
@@ -168,6 +170,44 @@ int movers_on(sa_engine *e, const unsigned long long *d_base, const unsigned lon
                                     std::max<uint64_t>(min_score, 1), T.cand, T.ctl, O, s);
   st = copy_ranked(st, T.ctl, k, h->top.head, h->top.rows.data(), O, sizeof O->est[0], h->out.data(), s);
   return st == hipSuccess ? SA_OK : wait_or_fail(e, st, s, "window movers");  // (a copy into h may be in flight)
+}
+
+// ---- error onset (sa_window_error_onset) ----
+// The scan's lane mapping: the laboratory build reads SPANAGG_EO_WAVE (0, 1) at
+// every call, the product holds variant 0 alone.
+uint32_t error_onset_variant() {
+#ifdef SPANAGG_AB
+  if (const char *v = ab_env("SPANAGG_EO_WAVE")) return (uint32_t)std::atoi(v);
+#endif
+  return 0;
+}
+
+int error_onset_buffers(sa_engine *e) {
+  if (int rc = top_buffers(e)) return rc;  // (the candidates and the select's state: calls are serialised)
+  return lazy(e, e->err_onset.out, 1, "window error onset: split buffer hipMalloc failed");
+}
+
+// On `s`, not waited for: e's key table scanned against d_sum [d][w] -- the
+// range's n windows summed -- and the windows themselves (window j at d_win +
+// ((first + j) & mask) * the slot's cells), the first k matches selected and
+// sorted, the counters, the k rows and their splits copied into *h.
+int error_onset_on(sa_engine *e, const unsigned long long *d_sum, const unsigned long long *d_win, uint64_t first,
+                   uint64_t mask, uint32_t n, uint32_t k, uint64_t min_count, uint64_t min_score, uint32_t flags,
+                   hipStream_t s, sa_grp::ErrOnsetHost *h) {
+  const sa_engine::Top &T = e->top;
+  sa::ErrOnsetOut *O = e->err_onset.out;
+  try {
+    h->top.rows.resize(k);
+    h->out.resize(2 + 3 * (size_t)k);
+  } catch (const std::bad_alloc &) {
+    return fail(e, SA_ENOMEM, "window error onset: the rows do not fit in host memory");
+  }
+  hipError_t st = sa::launch_error_onset(e->gkeys, e->cap, e->binned.kinv, d_sum, d_win, e->cms_slot_elems, first, mask, n,
+                                         e->cfg.cms_d, e->cfg.cms_w, 64 - sa::log2u(e->cfg.cms_w), e->d_seeds,
+                                         flags & SA_ERROR_ONSET_FALL ? 1u : 0u, k, std::max<uint64_t>(min_count, 1),
+                                         std::max<uint64_t>(min_score, 1), T.cand, T.ctl, O, error_onset_variant(), s);
+  st = copy_ranked(st, T.ctl, k, h->top.head, h->top.rows.data(), O, sizeof O->row[0], h->out.data(), s);
+  return st == hipSuccess ? SA_OK : wait_or_fail(e, st, s, "window error onset");  // (a copy into h may be in flight)
 }
 
 // ---- service overlap (sa_window_overlap) ----
@@ -346,6 +386,74 @@ int movers_result(const uint64_t range[4], uint32_t k, uint32_t flags, const Mov
   }
 }
 
+int window_cells_export_async(sa_engine *e, uint64_t first, uint64_t last, uint64_t *d_win, hipStream_t s) {
+  if (!e || !d_win) return SA_EINVAL;
+  if (int rc = check_span(e, "window error onset", first, last)) return rc;
+  if (int rc = begin_read(e)) return rc;
+  if (int rc = hop_to(e, s)) return rc;
+  if (int rc = range_fold_on(e, first, last, s)) return rc;
+  // the ring wraps: the slots from first's to the ring's end, then the ring's start
+  const uint64_t W = e->cfg.n_windows, n = last - first + 1, at = first & (W - 1), head = std::min(n, W - at);
+  const size_t slot = e->cms_slot_elems;
+  SA_HIP(e, hipMemcpyAsync(d_win, e->cms + at * slot, head * slot * 8, hipMemcpyDeviceToDevice, s));
+  if (n > head) SA_HIP(e, hipMemcpyAsync(d_win + head * slot, e->cms, (n - head) * slot * 8, hipMemcpyDeviceToDevice, s));
+  return hop_back(e, s);  // (the folds wrote this engine's cells and ERROR counts)
+}
+
+int window_error_onset_async(sa_engine *e, const uint64_t *d_win, uint32_t n, uint32_t k, uint64_t min_count,
+                             uint64_t min_score, uint32_t flags, hipStream_t s, ErrOnsetHost *out) {
+  if (!e || !d_win || !out || !n) return SA_EINVAL;
+  if (int rc = set_dev(e)) return rc;
+  if (int rc = range_buffers(e, 0, false, true)) return rc;
+  if (int rc = error_onset_buffers(e)) return rc;
+  // (the scratch is the engine's: after its own earlier use, before its next)
+  if (int rc = hop_to(e, s)) return rc;
+  const unsigned long long *win = reinterpret_cast<const unsigned long long *>(d_win);
+  uint32_t ring = 1;  // the unwrapped array as a ring that never wraps
+  while (ring < n) ring <<= 1;
+  SA_HIP(e, sa::launch_range_cells(win, e->cms_slot_elems, ring, 0, n, e->range.cells, s));
+  if (int rc = error_onset_on(e, e->range.cells, win, 0, ~0ULL, n, k, min_count, min_score, flags, s, out)) return rc;
+  return hop_back(e, s);
+}
+
+int error_onset_result(uint64_t first, uint64_t last, uint32_t k, uint32_t flags, const ErrOnsetHost *m,
+                       uint32_t n_members, sa_error_onset_result **out) {
+  try {
+    std::unique_ptr<error_onset_holder> h(new error_onset_holder());
+    // a row: key, D, t, B, A -- one member's as they are, the device's order; several members' merged as
+    // ranked_rows merges (a series on several members has the same row on each: once)
+    std::vector<std::array<uint64_t, 5>> all;
+    for (uint32_t j = 0; j < n_members; ++j) {
+      const size_t rows = (size_t)std::min<uint64_t>(k, m[j].top.head[0]);
+      const unsigned long long *split = m[j].out.data() + 2;
+      for (size_t i = 0; i < rows; ++i)
+        all.push_back({m[j].top.rows[i].y, m[j].top.rows[i].x, split[3 * i], split[3 * i + 1], split[3 * i + 2]});
+    }
+    if (n_members > 1) {
+      std::sort(all.begin(), all.end());
+      all.erase(std::unique(all.begin(), all.end()), all.end());
+      std::sort(all.begin(), all.end(), [](const std::array<uint64_t, 5> &a, const std::array<uint64_t, 5> &b) {
+        return a[1] != b[1] ? a[1] > b[1] : a[0] < b[0];
+      });
+      if (all.size() > k) all.resize(k);
+    }
+    h->shape(first, last, k, (uint32_t)all.size(), flags);
+    for (size_t i = 0; i < all.size(); ++i) {
+      h->keys[i] = all[i][0], h->score[i] = (int64_t)all[i][1];  // (a match's score is >= 1)
+      h->onset[i] = first + all[i][2], h->before[i] = all[i][3], h->after[i] = all[i][4];
+    }
+    for (uint32_t j = 0; j < n_members; ++j) {
+      h->r.n_matched += m[j].top.head[0], h->r.n_resident += m[j].top.head[1];
+      h->r.n_eligible += m[j].out[0];
+    }
+    h->r.error_spans = m[0].top.head[3];  // (the merged cells are the same on every member)
+    *out = &h.release()->r;
+    return SA_OK;
+  } catch (const std::bad_alloc &) {
+    return SA_ENOMEM;
+  }
+}
+
 int window_overlap_export_async(sa_engine *e, uint64_t first, uint64_t last, uint8_t *d_hll, hipStream_t s) {
   if (!e || !d_hll) return SA_EINVAL;
   if (int rc = check_span(e, "window overlap", first, last)) return rc;
@@ -487,6 +595,30 @@ int sa_window_movers(sa_engine *e, uint64_t base_first, uint64_t base_last, uint
 }
 
 void sa_movers_result_free(sa_movers_result *r) { delete reinterpret_cast<movers_holder *>(r); }
+
+int sa_window_error_onset(sa_engine *e, uint64_t first, uint64_t last, uint32_t k, uint64_t min_count,
+                          uint64_t min_score, uint32_t flags, sa_error_onset_result **out) {
+  if (!e || !out) return SA_EINVAL;
+  *out = nullptr;
+  if (const char *bad = sa_args::error_onset_args(k, flags)) return bad_args(e, SA_EINVAL, "window error onset", bad);
+  if (int rc = check_span(e, "window error onset", first, last)) return rc;
+  if (int rc = begin_read(e)) return rc;
+  if (int rc = range_buffers(e, 0, false, true)) return rc;
+  if (int rc = error_onset_buffers(e)) return rc;
+  unsigned long long *cells = e->range.cells;
+  // every window of the range folded and summed, then the walk over the ring's own cells
+  if (int rc = range_merge_on(e, first, last, nullptr, nullptr, cells, e->stream)) return rc;
+  sa_grp::ErrOnsetHost eh;
+  if (int rc = error_onset_on(e, cells, e->cms, first, e->cfg.n_windows - 1, (uint32_t)(last - first + 1), k, min_count,
+                              min_score, flags, e->stream, &eh))
+    return rc;
+  SA_HIP(e, hipStreamSynchronize(e->stream));  // the call's one wait
+  if (int rc = sa_grp::error_onset_result(first, last, k, flags, &eh, 1, out))
+    return fail(e, rc, "window error onset: the result does not fit in host memory");
+  return SA_OK;
+}
+
+void sa_error_onset_result_free(sa_error_onset_result *r) { delete reinterpret_cast<error_onset_holder *>(r); }
 
 int sa_window_overlap(sa_engine *e, uint64_t first, uint64_t last, const uint32_t *services, uint32_t n_sel,
                       uint32_t flags, sa_overlap_result **out) {

@@ -232,6 +232,12 @@ struct sa_engine {
   struct Movers {
     sa::MoversOut *out = nullptr;
   } movers;
+  // sa_window_error_onset (allocated by its first call) works in
+  // sa_window_top's scratch too, and leaves the eligible keys' count and the
+  // rows' splits here (sa::ErrOnsetOut, 96 KiB)
+  struct ErrOnset {
+    sa::ErrOnsetOut *out = nullptr;
+  } err_onset;
   // sa_window_overlap (allocated by its first call, for min(n_services,
   // SA_OVERLAP_MAX_SERVICES) = cap services): the selected ids [cap], their
   // merged registers [cap][2^p] and histograms [cap][SA_HLL_HIST_BINS], and

@@ -154,4 +154,26 @@ int window_movers_async(sa_engine *e, const uint64_t *d_base, const uint64_t *d_
 // last.  SA_ENOMEM when the result cannot be allocated.
 int movers_result(const uint64_t range[4], uint32_t k, uint32_t flags, const MoversHost *members, uint32_t n_members,
                   sa_movers_result **out);
+// sa_window_error_onset's export for one member, without the wait: every
+// window of first..last folded, then d_win [n][d * w] = the cells of window
+// first + j in row j (u64, unwrapped; n = last - first + 1), on `s`.  SA_ERANGE
+// as sa_window_range.
+int window_cells_export_async(sa_engine *e, uint64_t first, uint64_t last, uint64_t *d_win, hipStream_t s);
+// What one engine's error-onset scan leaves on the host: top as TopHost with
+// the best D for the estimate; out = {the eligible keys, -}, then the rows'
+// (t, B, A) in top.rows' order (sa::ErrOnsetOut's head and first k rows).
+struct ErrOnsetHost {
+  TopHost top;
+  std::vector<unsigned long long> out;
+};
+// sa_window_error_onset's device part for one member against the merged
+// windows d_win [n][d * w] on its device, on `s`, without the wait: fills *out
+// (which must stay until `s` has been waited for).  k, min_count, min_score and
+// flags as sa_window_error_onset.
+int window_error_onset_async(sa_engine *e, const uint64_t *d_win, uint32_t n, uint32_t k, uint64_t min_count,
+                             uint64_t min_score, uint32_t flags, hipStream_t s, ErrOnsetHost *out);
+// The sa_error_onset_result of n_members scans (each waited for), merged as
+// top_result merges.  SA_ENOMEM when the result cannot be allocated.
+int error_onset_result(uint64_t first, uint64_t last, uint32_t k, uint32_t flags, const ErrOnsetHost *members,
+                       uint32_t n_members, sa_error_onset_result **out);
 }  // namespace sa_grp

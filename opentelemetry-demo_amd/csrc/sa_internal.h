@@ -518,6 +518,36 @@ hipError_t launch_movers(const unsigned long long *gkeys, uint64_t cap, uint64_t
                          const unsigned long long *cur, uint32_t d, uint32_t w, uint32_t shift, const uint64_t *seeds,
                          uint64_t nb, uint64_t nc, uint32_t fall, uint32_t k, unsigned long long min_score,
                          ulonglong2 *cand, TopCtl *T, MoversOut *O, hipStream_t s);
+// error onset over the window ring (sa_window_error_onset; spanagg_error_onset.hip;
+// DESIGN.md section 4, "Error onset over the window ring").  A selected key's
+// best split: t (the first window of "after", counted from the range's first)
+// and the two sides' estimates B(t) and A(t).
+struct ErrOnsetRow {
+  unsigned long long t, before, after;
+};
+// What the call leaves beside TopCtl: the eligible keys and the selected rows'
+// splits, in T->sel's order (96 KiB; the head and the first k rows are one copy).
+struct ErrOnsetOut {
+  unsigned long long n_eligible, pad;
+  ErrOnsetRow row[kTopSel];
+};
+// The whole query on `s`: gkeys [cap] scanned against sum [d][w] -- the cells
+// of the range's n_win windows summed -- and against the windows themselves,
+// window j of the range at win_cells + ((first + j) & mask) * win_stride (the
+// engine's ring: mask = n_windows - 1; an unwrapped [n_win][d * w] array: first
+// 0, mask all ones).  Keys with E >= min_count are eligible (O->n_eligible);
+// every eligible key's best split scored (fall 0 or 1) into cand [cap], then
+// T->sel[0 .. min(k, T->n_matched)) = the first k of the keys with a best D >=
+// min_score as (D, key), by (D descending, key ascending), and O->row their
+// splits.  T->error_spans is sum's row-0 sum, T->max_est the largest D.  k <=
+// kTopSel, 1 <= min_count, 1 <= min_score.  variant: 0, a lane a candidate;
+// 1 (laboratory build only), a wave a candidate.
+hipError_t launch_error_onset(const unsigned long long *gkeys, uint64_t cap, uint64_t kinv,
+                              const unsigned long long *sum, const unsigned long long *win_cells, uint64_t win_stride,
+                              uint64_t first, uint64_t mask, uint32_t n_win, uint32_t d, uint32_t w, uint32_t shift,
+                              const uint64_t *seeds, uint32_t fall, uint32_t k, unsigned long long min_count,
+                              unsigned long long min_score, ulonglong2 *cand, TopCtl *T, ErrOnsetOut *O, uint32_t variant,
+                              hipStream_t s);
 // latency histograms over the window ring (spanagg_latency.hip; DESIGN.md
 // section 4, "Latency histograms over the window ring"): ring [n_windows]
 // [n_services][SA_LAT_BINS] u64.  Up to kLatLdsServices services a workgroup

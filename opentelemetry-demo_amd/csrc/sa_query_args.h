@@ -145,5 +145,12 @@ inline const char *onset_args(uint32_t k, uint32_t q, const uint64_t *threshold_
   return q == 0 || q > 1000000u ? "null threshold_ns with q_ppm outside 1..1000000" : nullptr;
 }
 
+// sa_window_error_onset's arguments, the range apart: k and the one flag
+// (min_count and min_score: any u64)
+inline const char *error_onset_args(uint32_t k, uint32_t flag_bits) {
+  if (const char *bad = top_k(k)) return bad;
+  return flags(flag_bits, SA_ERROR_ONSET_FALL);
+}
+
 }  // namespace sa_args
 #pragma GCC visibility pop

@@ -168,6 +168,20 @@ struct movers_holder {
   }
 };
 
+struct error_onset_holder {
+  sa_error_onset_result r;
+  std::vector<uint64_t> keys, onset, before, after;
+  std::vector<int64_t> score;
+  // the columns sized for n rows, and r pointing at them
+  __attribute__((visibility("hidden"))) void shape(uint64_t first, uint64_t last, uint32_t k, uint32_t n, uint32_t flags) {
+    keys.resize(n), onset.resize(n), score.resize(n), before.resize(n), after.resize(n);
+    r.first_window = first, r.last_window = last, r.k = k, r.n = n, r.flags = flags, r.pad = 0;
+    r.n_resident = r.n_eligible = r.n_matched = r.error_spans = 0;
+    r.key_hash = keys.data(), r.onset_window = onset.data(), r.score = score.data();
+    r.errors_before = before.data(), r.errors_after = after.data();
+  }
+};
+
 struct overlap_holder {
   sa_overlap_result r;
   std::vector<uint32_t> services, hist, pair_hist;

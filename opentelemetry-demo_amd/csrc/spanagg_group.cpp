@@ -311,6 +311,7 @@ struct sa_group {
   std::vector<ncclComm_t> comm;
   std::vector<Buf> keys, gath, uni, rows, hll, cms;
   std::vector<Buf> cms_base;  // sa_group_window_movers: the baseline range's cells beside cms (the current range's)
+  std::vector<Buf> cms_win;   // sa_group_window_error_onset: every window's cells of the range [n][d][w]
   std::vector<Buf> lat;       // sa_group_window_latency: every member's sliding sums [n_out][n_sel][SA_LAT_BINS]
                               // (the movers' two ranges' sums, sa_group_window_slo's and the onset's pairs)
   std::vector<Buf> lat_pool;  // sa_group_window_latency_onset: every service's pooled sums [n_services][SA_LAT_BINS]
@@ -588,6 +589,7 @@ int sa_group_create(const sa_config *cfg, const int32_t *devices, uint32_t n, sa
   g->hll.resize(n);
   g->cms.resize(n);
   g->cms_base.resize(n);
+  g->cms_win.resize(n);
   g->lat.resize(n);
   g->lat_pool.resize(n);
   g->dropped_seen.assign(n, 0);
@@ -641,7 +643,7 @@ void sa_group_destroy(sa_group *g) {
       (void)hipStreamSynchronize(g->st[i]);
       (void)hipStreamDestroy(g->st[i]);
     }
-    for (std::vector<Buf> *v : {&g->keys, &g->gath, &g->uni, &g->rows, &g->hll, &g->cms, &g->cms_base, &g->lat, &g->lat_pool, &g->srt, &g->ucnt})
+    for (std::vector<Buf> *v : {&g->keys, &g->gath, &g->uni, &g->rows, &g->hll, &g->cms, &g->cms_base, &g->cms_win, &g->lat, &g->lat_pool, &g->srt, &g->ucnt})
       if (i < v->size() && (*v)[i].p) (void)hipFree((*v)[i].p);
     if (i < g->big.size() && g->big[i]) (void)hipFree(g->big[i]);
     for (size_t k = 0; k < 2; ++k)
@@ -1201,6 +1203,36 @@ int sa_group_window_movers(sa_group *g, uint64_t base_first, uint64_t base_last,
   const uint64_t range[4] = {base_first, base_last, cur_first, cur_last};
   if (int rc2 = sa_grp::movers_result(range, k, flags, mh.data(), (uint32_t)mh.size(), out))
     return gfail(g, rc2, "window movers: the result does not fit in host memory");
+  return SA_OK;
+}
+
+// As sa_group_window_top with every window's cells instead of their sum:
+// every member exports the range's windows unwrapped into cms_win, the
+// transport sums the arrays and leaves the sums on every member, and every
+// member sums the merged windows and walks them for the keys of its own table.
+int sa_group_window_error_onset(sa_group *g, uint64_t first, uint64_t last, uint32_t k, uint64_t min_count,
+                                uint64_t min_score, uint32_t flags, sa_error_onset_result **out) {
+  if (!g || !out) return SA_EINVAL;
+  *out = nullptr;
+  const char *const what = "window error onset";
+  if (const char *bad = sa_args::error_onset_args(k, flags)) return bad_args(g, SA_EINVAL, what, bad);
+  // (the members check the range against their rings; a range that passes has n <= n_windows)
+  const uint64_t n = first <= last && last - first < g->cfg.n_windows ? last - first + 1 : 0;
+  const std::vector<Part> parts = {{&g->cms_win, n ? n * g->cms_elems : 1, false}};
+  if (int rc = ensure_parts(g, parts)) return rc;
+  int rc = each_member(g, what, [&](uint32_t i) {
+    return sa_grp::window_cells_export_async(g->eng[i], first, last, buf<uint64_t>(g->cms_win, i), g->st[i]);
+  });
+  const int merged = rc ? SA_OK : sum_cells_everywhere(g, parts);
+  std::vector<sa_grp::ErrOnsetHost> eh(g->eng.size());
+  if (!rc && !merged)
+    rc = each_member(g, what, [&](uint32_t i) {
+      return sa_grp::window_error_onset_async(g->eng[i], buf<uint64_t>(g->cms_win, i), (uint32_t)n, k, min_count,
+                                              min_score, flags, g->st[i], &eh[i]);
+    });
+  if (int end = end_query(g, what, rc, merged, out, sa_error_onset_result_free)) return end;
+  if (int rc2 = sa_grp::error_onset_result(first, last, k, flags, eh.data(), (uint32_t)eh.size(), out))
+    return gfail(g, rc2, "window error onset: the result does not fit in host memory");
   return SA_OK;
 }
 

@@ -124,6 +124,18 @@ class sa_movers_result(C.Structure):
     ]
 
 
+SA_ERROR_ONSET_FALL = 1
+
+
+class sa_error_onset_result(C.Structure):
+    _fields_ = [
+        ("first_window", C.c_uint64), ("last_window", C.c_uint64), ("k", C.c_uint32), ("n", C.c_uint32),
+        ("flags", C.c_uint32), ("pad", C.c_uint32),
+        ("n_resident", C.c_uint64), ("n_eligible", C.c_uint64), ("n_matched", C.c_uint64), ("error_spans", C.c_uint64),
+        ("key_hash", u64p), ("onset_window", u64p), ("score", i64p), ("errors_before", u64p), ("errors_after", u64p),
+    ]
+
+
 SA_OVERLAP_MAX_SERVICES = OVERLAP_MAX_SERVICES = 64
 
 
@@ -260,6 +272,11 @@ SIGNATURES = [
     ("sa_group_window_movers", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
                                          C.c_uint64, C.c_uint32, C.POINTER(C.POINTER(sa_movers_result))]),
     ("sa_movers_result_free", None, [C.POINTER(sa_movers_result)]),
+    ("sa_window_error_onset", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64,
+                                        C.c_uint32, C.POINTER(C.POINTER(sa_error_onset_result))]),
+    ("sa_group_window_error_onset", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64,
+                                              C.c_uint32, C.POINTER(C.POINTER(sa_error_onset_result))]),
+    ("sa_error_onset_result_free", None, [C.POINTER(sa_error_onset_result)]),
     ("sa_window_overlap", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, u32p, C.c_uint32, C.c_uint32,
                                     C.POINTER(C.POINTER(sa_overlap_result))]),
     ("sa_group_window_overlap", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, u32p, C.c_uint32, C.c_uint32,

@@ -218,6 +218,31 @@ class MoversResult:
 
 
 @dataclass
+class ErrorOnsetResult:
+    """sa_error_onset_result: the series whose ERROR spans per window rose most
+    (fall: fell most) across their best split of windows first..last, among the
+    series resident in the engine's key table -- each with the window at which
+    "after" begins."""
+    first_window: int
+    last_window: int
+    fall: bool
+    keys: np.ndarray              # [n] u64, by score descending then key ascending
+    onset_window: np.ndarray      # [n] u64: the first window of "after"
+    score: np.ndarray             # [n] i64: after * t - before * (n - t) at the best split (negated when fall), >= 1
+    errors_before: np.ndarray     # [n] u64: window_range(first, onset_window - 1, [keys[i]]).errors[0]
+    errors_after: np.ndarray      # [n] u64: window_range(onset_window, last, [keys[i]]).errors[0]
+    n_resident: int               # series in the key table when the call ran: the candidates
+    n_eligible: int               # candidates with an estimate over the range >= max(min_count, 1)
+    n_matched: int                # eligible candidates with a best score >= max(min_score, 1)
+    error_spans: int              # ERROR spans the range's sketches counted, exact
+
+    def items(self):
+        """[(key, onset_window, score, errors_before, errors_after)]; sketch.error_onset's rows with t = onset_window - first."""
+        return [tuple(int(v) for v in row) for row in zip(self.keys, self.onset_window, self.score, self.errors_before,
+                                                          self.errors_after)]
+
+
+@dataclass
 class OverlapResult:
     """sa_overlap_result: for every pair of the selected services the traces
     both saw over windows first..last, by inclusion-exclusion on the merged
@@ -482,6 +507,23 @@ def _window_movers(obj, fn, what, base, cur, k, min_score, fall) -> MoversResult
                             int(r.error_spans_base), int(r.error_spans_cur))
     finally:
         obj.lib.sa_movers_result_free(out)
+
+
+def _window_error_onset(obj, fn, what, first, last, k, min_count, min_score, fall) -> ErrorOnsetResult:
+    """sa_window_error_onset / sa_group_window_error_onset -> ErrorOnsetResult (copies), freeing the library's result."""
+    out = C.POINTER(_lib.sa_error_onset_result)()
+    obj._check(fn(obj._h, int(first), int(last), int(k), int(min_count), int(min_score),
+                  _lib.SA_ERROR_ONSET_FALL if fall else 0, C.byref(out)), what)
+    try:
+        r = out.contents
+        n = int(r.n)
+        col = lambda p, dt=np.uint64: np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, dt)
+        return ErrorOnsetResult(int(r.first_window), int(r.last_window), bool(r.flags & _lib.SA_ERROR_ONSET_FALL),
+                                col(r.key_hash), col(r.onset_window), col(r.score, np.int64), col(r.errors_before),
+                                col(r.errors_after), int(r.n_resident), int(r.n_eligible), int(r.n_matched),
+                                int(r.error_spans))
+    finally:
+        obj.lib.sa_error_onset_result_free(out)
 
 
 def _window_overlap(obj, fn, what, first, last, services) -> OverlapResult:
@@ -811,6 +853,18 @@ class Engine:
         ranges' summed count-mins, selected and sorted on the device."""
         return _window_movers(self, self.lib.sa_window_movers, "sa_window_movers", base, cur, k, min_score, fall)
 
+    def window_error_onset(self, first: int, last: int, k: int = 10, min_count: int = 1, min_score: int = 1,
+                           fall: bool = False) -> ErrorOnsetResult:
+        """sa_window_error_onset: for every series resident in the key table
+        with at least min_count estimated ERROR spans over windows first..last,
+        the split of the range with the largest window_movers score (the
+        latest among equal ones), and the k series whose best score is largest
+        (>= min_score) with the window at which "after" begins -- one walk
+        over the ring's count-mins per series, selected and sorted on the
+        device."""
+        return _window_error_onset(self, self.lib.sa_window_error_onset, "sa_window_error_onset", first, last, k,
+                                   min_count, min_score, fall)
+
     def window_overlap(self, first: int, last: int, services=None) -> OverlapResult:
         """sa_window_overlap: the traces every pair of `services` (ids, at most
         OVERLAP_MAX_SERVICES; None: every service of an engine with no more
@@ -1068,6 +1122,14 @@ class Group:
         (n_resident and n_matched are summed over members)."""
         return _window_movers(self, self.lib.sa_group_window_movers, "sa_group_window_movers", base, cur, k, min_score,
                               fall)
+
+    def window_error_onset(self, first: int, last: int, k: int = 10, min_count: int = 1, min_score: int = 1,
+                           fall: bool = False) -> ErrorOnsetResult:
+        """sa_group_window_error_onset: Engine.window_error_onset over the
+        members' merge -- every window's cells summed across members, a scan
+        on every member, the rows merged on the host."""
+        return _window_error_onset(self, self.lib.sa_group_window_error_onset, "sa_group_window_error_onset", first,
+                                   last, k, min_count, min_score, fall)
 
     def window_overlap(self, first: int, last: int, services=None) -> OverlapResult:
         """sa_group_window_overlap: Engine.window_overlap over the members' merge."""

@@ -55,6 +55,44 @@ def movers(cms_base: np.ndarray, cms_cur: np.ndarray, n_base: int, n_cur: int, k
     return rows[:k]
 
 
+def error_onset(cms_windows, keys: Iterable[int], k: int = 10, min_count: int = 1, min_score: int = 1,
+                fall: bool = False):
+    """sa_window_error_onset over cms_windows [n][d][w], the cells of the
+    range's windows in order: (rows, n_eligible, n_matched).  A key's sums S_r
+    over the range give E = min_r S_r; it is eligible with E >= max(min_count,
+    1).  For every split t in 1 .. n - 1, B(t) = min_r of the key's cells
+    summed over windows 0 .. t - 1, A(t) = min_r of those summed over t .. n -
+    1 (the two minima may come from different rows), D(t) = A(t) * t - B(t) *
+    (n - t), negated when `fall`: movers' score of the two sides.  The best
+    split has the largest D, the latest among equal ones.  A key matches when
+    eligible with a best D >= max(min_score, 1).  rows: the first k matches by
+    D descending then key ascending, each (key, t, D, B(t), A(t))."""
+    x = np.asarray(cms_windows)
+    n, d, w = x.shape
+    shift = 64 - (w.bit_length() - 1)
+    mc, ms = max(int(min_count), 1), max(int(min_score), 1)
+    n_eligible, rows = 0, []
+    for key in keys:
+        cols = [_splitmix64(int(key) ^ CMS_SEEDS[r]) >> shift for r in range(d)]
+        cell = [[int(x[j, r, cols[r]]) for j in range(n)] for r in range(d)]
+        total = [sum(c) for c in cell]
+        if min(total) < mc:
+            continue
+        n_eligible += 1
+        best, prefix = None, [0] * d
+        for t in range(1, n):
+            prefix = [p + c[t - 1] for p, c in zip(prefix, cell)]
+            b, a = min(prefix), min(s - p for s, p in zip(total, prefix))
+            score = a * t - b * (n - t)
+            score = -score if fall else score
+            if best is None or score >= best[2]:
+                best = (int(key), t, score, b, a)
+        if best is not None and best[2] >= ms:
+            rows.append(best)
+    rows.sort(key=lambda r: (-r[2], r[0]))
+    return rows[:k], n_eligible, len(rows)
+
+
 def distinct_traces(hll: np.ndarray, p: int) -> np.ndarray:
     """[n_services] HLL estimates of distinct trace ids."""
     return np.array([hll_estimate(hll[s], p) for s in range(hll.shape[0])])
